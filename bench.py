@@ -3,7 +3,7 @@
 on MI355X, BASELINE.json config 3: 3-D, 1e7 scattered weighted points per GPU,
 64x64x64 nodes, real64.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one complete fit of this rank's points that are already resident in
 HBM: window binning, Gram assembly, (RCCL all-reduce of the normal equations when
@@ -18,14 +18,20 @@ and no host synchronisation in the loop; torch.distributed is the fallback and c
 bench's own barriers) -- and the nested-dissection factorisation is distributed by subtrees
 (the top of the tree replicated).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step,
+config, ...; at N > 1 also `strong`, config 3's 1e7 points in all, sharded, which is the headline there, and `weak`).
+--dump-outputs DIR writes the coefficients of the last timed fit as DIR/coef.npy (float64; the inputs
+are the seeded stream, identical from run to run).  --full adds everything else below: the evaluation throughput,
+per-kernel and roofline figures (HIP-event timing inside the timed region and one extra fit), the side configurations
+and the CPU baseline.
+
+Extra objects on the line of a --full run:
   roofline      the dominant kernel (nd_syrk_kernel<4,2,true,1,1>: f64-MFMA Schur-buffer passes of the
                 multifrontal factorisation): algorithmic flop / HIP-event time measured inside the timed region
   cpu_baseline  the reference itself (oracle/_ref, 1 core; it is single-threaded)
                 on a bounded sample -- the dense reference algorithm cannot run the
                 64^3 grid at all (550 GB workspace)
   eval          batched evaluation throughput (one thread per query) + its HBM roofline
-  strong        (N > 1) config 3's 1e7 points in all, sharded: the fixed-total line beside the weak headline
   c2, grid32, c5_eval, c5_fit, fit_incl_h2d, multi_gpu_one_process   guarded side legs (N = 1; the last one also at N > 1)
 """
 import argparse
@@ -70,11 +76,18 @@ def parse():
     ap.add_argument("--ndata", type=int, default=None,
                     help="points per GPU (default: 1e7 = BASELINE config 3; with --gpus 8 on the 3-D 64^3 grid 1.25e7 = config 4's 1e8 points in all)")
     ap.add_argument("--neval", type=int, default=50_000_000, help="evaluation queries per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: evaluation throughput, per-kernel timing and roofline, side legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the coefficients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-side-legs", action="store_true", help="skip the C2 and host-pointer (PCIe-inclusive) legs")
     ap.add_argument("--dist-child", type=str, default="", help=argparse.SUPPRESS)   # internal: "ngpus,nod,m,virtual"
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def default_ndata(world, nd, nod):
@@ -104,6 +117,21 @@ def guarded(fn, *a, **k):
         return fn(*a, **k)
     except Exception as exc:
         return {"error": f"{type(exc).__name__}: {exc}"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array; an array larger than DUMP_LIMIT_BYTES is replaced by a fixed,
+    seeded sample of its entries (in index order) so that two builds can still be compared entry for entry."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.nbytes > DUMP_LIMIT_BYTES // len(arrays):
+            keep = DUMP_LIMIT_BYTES // len(arrays) // a.itemsize
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def cpu_baseline(ndim):
@@ -556,7 +584,7 @@ def main():
     from splpak_amd.dist import ShardedFit
     sharded = ShardedFit(nd, nodes, lo, hi, 1.0, m, dev, dist if world > 1 else None)
     plan = sharded.plan
-    plan.enable_kernel_timing(not args.no_kernel_timing)
+    plan.enable_kernel_timing(args.full and not args.no_kernel_timing)      # (HIP events around the launches: --full's figures)
 
     def barrier():
         if world > 1:
@@ -581,6 +609,7 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     assert ierr == 0, f"fit failed with ierror {ierr}"
+    last = {"coef": coef.cpu().numpy()} if args.dump_outputs else None
     stages = plan.stage_timing()
     # parity gate at the size that is timed: the MEASURED optimality residual of the returned coefficients
     # (gradient of the least-squares functional, relative to |A^T W^2 y|) must be at rounding level
@@ -594,7 +623,7 @@ def main():
     # the roofline kernel with the chip to itself: one extra fit OUTSIDE the timed region with every launch of the
     # factorisation on one stream (the plan's option no_lookahead), so that no chain kernel shares the CUs with it
     kt_alone = None
-    if world == 1 and not args.no_kernel_timing:
+    if args.full and world == 1 and not args.no_kernel_timing:
         plan.set_option("no_lookahead", "1")                   # (a per-fit option of the plan: round 6, no getenv on the fit path)
         try:
             ierr_a, _ = plan.fit(x, y, w, coef, stream)
@@ -618,77 +647,19 @@ def main():
                 ierr_s, info_s = plan.fit(x[:cnt], y[:cnt], w[:cnt], coef, stream)
             barrier()
             el = time.perf_counter() - ts
+            if args.dump_outputs:
+                last = {"coef": coef.cpu().numpy()}                      # (the headline at N > 1 is this loop's)
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             strong = {"workload": f"C3's 1e7 points in all, sharded over {world} GPUs (fixed total)", "scaling": "strong",
                       "value": ms_tot * args.steps / float(t.item()), "unit": "points/s",
                       "ms_per_step": 1e3 * float(t.item()) / args.steps, "ierror": int(ierr_s)}
-            capi.synth_points_dev(nd, rank * m, m, x, y, w, stream)      # back to the weak-scaling shard
-            ierr, info = plan.fit(x, y, w, coef, stream)                 # coefficients of the headline workload for the evaluation leg
+            if args.full:
+                capi.synth_points_dev(nd, rank * m, m, x, y, w, stream)      # back to the weak-scaling shard
+                ierr, info = plan.fit(x, y, w, coef, stream)                 # coefficients of the headline workload for the evaluation leg
+    if rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last)
 
-    # ---- evaluation throughput (splfe), queries sharded, no collectives ---------
-    nq = args.neval
-    xq = torch.empty((nq, nd), dtype=torch.float64, device=dev)
-    out = torch.empty(nq, dtype=torch.float64, device=dev)
-    capi.synth_queries_dev(nd, world * m, rank * nq, nq, xq, stream)
-    def time_eval(mode):
-        capi.set_eval_mode(mode)
-        capi.evaluate_dev(nd, xq, None, coef, lo, hi, nodes, out, stream)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 20
-        barrier()
-        e0.record()
-        for _ in range(reps):
-            capi.evaluate_dev(nd, xq, None, coef, lo, hi, nodes, out, stream)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / reps
-        if world > 1:
-            t = torch.tensor([ms], dtype=torch.float64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            ms = float(t.item())
-        return ms
-
-    ev_direct_ms = time_eval(capi.EVAL_DIRECT)     # one thread per query, global (L2) gathers
-    ev_ms = time_eval(capi.EVAL_AUTO)              # library default: LDS-binned for batches like this one
-    evals_per_s = world * nq / (ev_ms * 1e-3)
-    ev_bytes = 8.0 * (nd + 1) * nq
-
-    # fabric bytes of the evaluation passes: PMC passes of an earlier run of the same workload, kept under profiles/ --
-    # NOT measured in this run
-    eval_traffic = None
-    eval_pmc = committed_profile("r06_eval_pmc.json", "r05_eval_pmc.json", "r04_eval_pmc.json")
-    try:
-        pm = json.load(open(eval_pmc))["3d_64"]
-        eval_traffic = {"kernel": "pr_eval_kernel<3,16,true,double> (evaluation pass of the persistent region path; all three passes in bytes_per_query_all_passes)", "bytes_per_launch": next(v for k, v in pm["kernels"].items() if k.startswith(("pr_eval_kernel<3", "eval_runs_kernel<3, true", "eval_binned_kernel<3, true")))["hbm_bytes"],
-                        "queries_per_launch": pm["queries_per_launch"],
-                        "bytes_per_query_all_passes": pm["hbm_bytes_per_query_all_passes"], "algorithmic_bytes_per_query": 8.0 * (nd + 1),
-                        "source": os.path.relpath(eval_pmc, ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same workload; not measured in this run)"}
-    except Exception:
-        pass
-    dist_leg = None
-    if world > 1 and not args.no_side_legs:
-        # strong scaling with a DISTRIBUTED factorisation: rank 0's process drives all `world` GPUs of the node
-        # (native peer copies, no Python in the loop); the other ranks free their plans and wait
-        if rank != 0:
-            plan.close()
-            torch.cuda.empty_cache()
-        barrier()
-        # the other ranks wait on the rendezvous store, not in a collective: an RCCL barrier would keep a kernel
-        # spinning on every GPU the child is about to drive
-        from datetime import timedelta
-        store = dist.distributed_c10d._get_default_store()
-        if rank == 0:
-            try:
-                # the headline's workload (every rank's m points: m * world in all) through the one-process route
-                dist_leg = dist_band_in_child(world, nd, nod, m * world, bool(os.environ.get("SPLPAK_BENCH_SINGLE_DEVICE")),
-                                              args.steps, 150)
-            finally:
-                store.set("splpak_dist_leg_done", "1")
-        else:
-            store.wait(["splpak_dist_leg_done"], timedelta(seconds=400))
-        barrier()
     if rank == 0:
         line = {
             "metric": (f"fitted points/sec (splcw) + evals/sec (splfe), {nd}-D {m:.0e} pts {nod}^{nd} nodes"
@@ -726,6 +697,82 @@ def main():
                 "phase_seconds_per_step": {"assembly": phase[0] / args.steps, "factor": phase[1] / args.steps,
                                            "solve_refine": phase[2] / args.steps},
             },
+        }
+        if strong is not None:
+            line["strong"] = strong
+            line["weak"] = {"workload": workload_label(world, nd, nod, m), "scaling": "weak", "value": value, "unit": "points/s",
+                            "ms_per_step": 1e3 * elapsed / args.steps, "points_per_gpu": m,
+                            "note": "the timed K steps of the contract ran on this workload too; the factorisation does not depend on the point count"}
+            line["config"]["workload"] = strong["workload"] + "; 3-D, 64^3 nodes, xtrap=1, real64 (BASELINE config 3's total)"
+            line["config"]["points_total"] = 10_000_000
+
+    # ---- a plain run ends here: everything below is --full's -------------------
+    if args.full:
+        # ---- evaluation throughput (splfe), queries sharded, no collectives ---------
+        nq = args.neval
+        xq = torch.empty((nq, nd), dtype=torch.float64, device=dev)
+        out = torch.empty(nq, dtype=torch.float64, device=dev)
+        capi.synth_queries_dev(nd, world * m, rank * nq, nq, xq, stream)
+        def time_eval(mode):
+            capi.set_eval_mode(mode)
+            capi.evaluate_dev(nd, xq, None, coef, lo, hi, nodes, out, stream)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            reps = 20
+            barrier()
+            e0.record()
+            for _ in range(reps):
+                capi.evaluate_dev(nd, xq, None, coef, lo, hi, nodes, out, stream)
+            e1.record()
+            torch.cuda.synchronize()
+            ms = e0.elapsed_time(e1) / reps
+            if world > 1:
+                t = torch.tensor([ms], dtype=torch.float64, device=dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                ms = float(t.item())
+            return ms
+
+        ev_direct_ms = time_eval(capi.EVAL_DIRECT)     # one thread per query, global (L2) gathers
+        ev_ms = time_eval(capi.EVAL_AUTO)              # library default: LDS-binned for batches like this one
+        evals_per_s = world * nq / (ev_ms * 1e-3)
+        ev_bytes = 8.0 * (nd + 1) * nq
+
+        # fabric bytes of the evaluation passes: PMC passes of an earlier run of the same workload, kept under profiles/ --
+        # NOT measured in this run
+        eval_traffic = None
+        eval_pmc = committed_profile("r06_eval_pmc.json", "r05_eval_pmc.json", "r04_eval_pmc.json")
+        try:
+            pm = json.load(open(eval_pmc))["3d_64"]
+            eval_traffic = {"kernel": "pr_eval_kernel<3,16,true,double> (evaluation pass of the persistent region path; all three passes in bytes_per_query_all_passes)", "bytes_per_launch": next(v for k, v in pm["kernels"].items() if k.startswith(("pr_eval_kernel<3", "eval_runs_kernel<3, true", "eval_binned_kernel<3, true")))["hbm_bytes"],
+                            "queries_per_launch": pm["queries_per_launch"],
+                            "bytes_per_query_all_passes": pm["hbm_bytes_per_query_all_passes"], "algorithmic_bytes_per_query": 8.0 * (nd + 1),
+                            "source": os.path.relpath(eval_pmc, ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same workload; not measured in this run)"}
+        except Exception:
+            pass
+    dist_leg = None
+    if args.full and world > 1 and not args.no_side_legs:
+        # strong scaling with a DISTRIBUTED factorisation: rank 0's process drives all `world` GPUs of the node
+        # (native peer copies, no Python in the loop); the other ranks free their plans and wait
+        if rank != 0:
+            plan.close()
+            torch.cuda.empty_cache()
+        barrier()
+        # the other ranks wait on the rendezvous store, not in a collective: an RCCL barrier would keep a kernel
+        # spinning on every GPU the child is about to drive
+        from datetime import timedelta
+        store = dist.distributed_c10d._get_default_store()
+        if rank == 0:
+            try:
+                # the headline's workload (every rank's m points: m * world in all) through the one-process route
+                dist_leg = dist_band_in_child(world, nd, nod, m * world, bool(os.environ.get("SPLPAK_BENCH_SINGLE_DEVICE")),
+                                              args.steps, 150)
+            finally:
+                store.set("splpak_dist_leg_done", "1")
+        else:
+            store.wait(["splpak_dist_leg_done"], timedelta(seconds=400))
+        barrier()
+    if rank == 0 and args.full:
+        line.update({
             "evals_per_s": evals_per_s,
             "eval": {
                 "value": evals_per_s, "unit": "evals/s", "queries_per_gpu": nq, "ms_per_batch": ev_ms,
@@ -733,7 +780,7 @@ def main():
                 "direct_path_evals_per_s": world * nq / (ev_direct_ms * 1e-3),
                 "roofline": {"bound": "hbm", "achieved": ev_bytes / (ev_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                              "unit": "GB/s", "frac": ev_bytes / (ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                             # scalars (the driver's parser keeps scalars only): HBM bytes per query over ALL passes, by the counters
+                             # scalars (for parsers that keep scalars only): HBM bytes per query over ALL passes, by the counters
                              "traffic": (eval_traffic or {}).get("bytes_per_query_all_passes"),
                              "algorithmic_bytes_per_query": 8.0 * (nd + 1),
                              "traffic_source": (eval_traffic or {}).get("source"),
@@ -742,7 +789,7 @@ def main():
             # the evaluation half of the headline metric as scalars of the line itself
             "eval_roofline_frac": ev_bytes / (ev_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
             "eval_hbm_bytes_per_query": (eval_traffic or {}).get("bytes_per_query_all_passes"),
-        }
+        })
         if stages["bin_ms"] > 0:
             # the HBM-bound stages around the factorisation: algorithmic bytes (8*(d+1+[weighted]) per point
             # and streaming pass) over the HIP-event time of the stage in the last timed fit
@@ -829,13 +876,6 @@ def main():
                 line["roofline"]["note"] = ("the panel updates of the chain (nd_syrk_kernel<4,2,false>, K = 256) and the diagonal-block / panel-solve "
                                             "kernels run beside these launches on other streams and share the CUs with them; "
                                             "the band factorisation of round 2 needed 4.1e13 flop for this grid")
-        if strong is not None:
-            line["strong"] = strong
-            line["weak"] = {"workload": workload_label(world, nd, nod, m), "scaling": "weak", "value": value, "unit": "points/s",
-                            "ms_per_step": 1e3 * elapsed / args.steps, "points_per_gpu": m,
-                            "note": "the timed K steps of the contract ran on this workload too; the factorisation does not depend on the point count"}
-            line["config"]["workload"] = strong["workload"] + "; 3-D, 64^3 nodes, xtrap=1, real64 (BASELINE config 3's total)"
-            line["config"]["points_total"] = 10_000_000
         if world == 1 and not args.no_side_legs:
             plan.close()                      # the side legs have the GPU to themselves
             # every side leg is guarded: a failure becomes {"error": ...} inside the line, the headline survives
@@ -868,6 +908,7 @@ def main():
             line["multi_gpu_one_process"] = dist_leg
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = guarded(cpu_baseline, nd)
+    if rank == 0:
         print(json.dumps(line), flush=True)
 
     sharded.close()                       # (the plan, and the native RCCL communicator if one was made)

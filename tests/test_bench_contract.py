@@ -80,13 +80,34 @@ def test_cpu_baseline_and_side_objects():
     assert d["c2"]["optimality_residual"] < 1e-9 and d["grid32"]["optimality_residual"] < 1e-9
 
 
-def test_multi_gpu_defaults_name_the_baseline_configs():
-    """`bench.py --gpus 8` without --ndata is BASELINE config 4 (1e8 points in all = 1.25e7 per GPU) and says so;
-    one GPU is config 3; other rank counts say what they are (VERDICT r02 #3)."""
+def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_are_float64_and_capped(tmp_path):
+    """--dump-outputs writes DIR/<name>.npy in float64; an array beyond the 64 MB cap becomes the same seeded sample every time."""
+    import numpy as np
+    bench = _bench_module()
+    small = np.arange(10, dtype=np.float32)
+    big = np.arange(bench.DUMP_LIMIT_BYTES // 8 + 1000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small})
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"big": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    b = np.load(tmp_path / "b" / "big.npy")
+    assert b.dtype == np.float64 and b.nbytes <= bench.DUMP_LIMIT_BYTES and np.all(np.diff(b) > 0)
+    assert np.array_equal(b, big[b.astype(np.int64)]) and np.array_equal(b, np.load(tmp_path / "c" / "big.npy"))
+
+
+def test_multi_gpu_defaults_name_the_baseline_configs():
+    """`bench.py --gpus 8` without --ndata is BASELINE config 4 (1e8 points in all = 1.25e7 per GPU) and says so;
+    one GPU is config 3; other rank counts say what they are (VERDICT r02 #3)."""
+    bench = _bench_module()
     assert bench.default_ndata(8, 3, 64) == 12_500_000 and 8 * bench.default_ndata(8, 3, 64) == 100_000_000
     for n in (1, 2, 4):
         assert bench.default_ndata(n, 3, 64) == 10_000_000
@@ -101,11 +122,12 @@ def test_multi_gpu_defaults_name_the_baseline_configs():
 
 @pytest.mark.gpu
 def test_live_bench_line_keeps_the_contract():
-    """A line produced NOW by `python bench.py --no-side-legs` on the GPU (not the committed profile): the contract's keys,
+    """A line produced NOW by `python bench.py --full --no-side-legs` on the GPU (not the committed profile): the contract's keys,
     a roofline object of scalars whose numbers are consistent, the CPU baseline (VERDICT r03 #6)."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-side-legs", "--neval", "20000000"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-side-legs",
+                        "--neval", "20000000"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-500:])
@@ -122,3 +144,31 @@ def test_live_bench_line_keeps_the_contract():
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] in ("reference", "port")
     assert 0 < d["eval_roofline_frac"] < 1
     assert r_["evals_per_s"] > 1e10 and 0 < r_["eval_frac"] < 1 and "collective_backend" in d["config"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --steps 2 --warmup 1 --dump-outputs DIR` without --full: the headline keys, exactly the steps asked for,
+    none of --full's measurements, and the coefficients of the last timed fit in DIR/coef.npy (float64), those of a second run
+    equal to rounding."""
+    import subprocess
+    import sys
+    import numpy as np
+    outs = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / str(k))], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-500:])
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert key in d, key
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "points/s" and d["dtype"] == "f64"
+        assert abs(d["value"] - d["config"]["points_total"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["config"]["optimality_residual"] < 1e-9
+        for key in ("roofline", "cpu_baseline", "eval", "evals_per_s", "assembly", "c2", "c5_fit"):
+            assert key not in d, key
+        c = np.load(tmp_path / str(k) / "coef.npy")
+        assert c.dtype == np.float64 and c.shape == (d["config"]["ncol"],) and np.all(np.isfinite(c))
+        outs.append(c)
+    assert np.max(np.abs(outs[0] - outs[1])) <= 1e-12 * np.max(np.abs(outs[0]))

@@ -105,11 +105,8 @@ def test_port_error_codes(port):
     assert e(nd=[3])[1] == 104
 
 
-def test_port_matches_live_reference(port, reference):
-    """Where the reference itself can be built (this container), compare directly on
-    inputs that are not in the golden set."""
-    if reference is None:
-        pytest.skip("oracle/_ref not available")
+def live_cases():
+    """Inputs that are not in the golden set (seeded): (key, ndim, nodes, x, y, w or None, xtrap)."""
     rng = np.random.default_rng(7)
     for nd, nodes, m in [(1, [9], 40), (2, [6, 11], 700), (3, [5, 4, 7], 900), (4, [4, 4, 5, 4], 1500)]:
         x = rng.random((m, nd)) * 1.2 - 0.1
@@ -117,9 +114,20 @@ def test_port_matches_live_reference(port, reference):
         w = rng.random(m)
         w[rng.random(m) < 0.1] = 0.0
         for wd, xtrap in [(w, 1.0), (None, 0.3)]:
-            c0, e0, w0 = reference.fit(nd, x, y, wd, [0.0] * nd, [1.0] * nd, nodes, xtrap)
-            c1, e1, w1 = port.fit(nd, x, y, wd, [0.0] * nd, [1.0] * nd, nodes, xtrap)
-            n = int(np.prod(nodes))
+            yield f"{nd}d_{'w' if wd is not None else 'u'}", nd, nodes, x, y, wd, xtrap
+
+
+def test_port_matches_live_reference(port, reference):
+    """The port against the reference on inputs that are not in the golden set: the reference's outputs stored in
+    tests/golden/live_ref.npz (oracle/gen_live_fixture.py), and the reference itself where it can be built (oracle/_ref)."""
+    gold = load_golden("live_ref")
+    for key, nd, nodes, x, y, wd, xtrap in live_cases():
+        n = int(np.prod(nodes))
+        refs = [(gold["coef_" + key], int(gold["ierror_" + key]), gold["hist_" + key])]
+        if reference is not None:
+            refs.append(reference.fit(nd, x, y, wd, [0.0] * nd, [1.0] * nd, nodes, xtrap))
+        c1, e1, w1 = port.fit(nd, x, y, wd, [0.0] * nd, [1.0] * nd, nodes, xtrap)
+        for c0, e0, w0 in refs:
             assert e0 == e1 == 0
             assert relmax(c1[:n], c0[:n]) < COEF_TOL
             assert relmax(w1[:n], w0[:n]) < 1e-13
