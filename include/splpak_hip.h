@@ -174,7 +174,7 @@ void    splpak_rccl_comm_destroy(void *nccl_comm);
 void    splpak_plan_set_refine(splpak_plan *plan, int32_t max_steps, double tol);
 
 /* The fit on resident data.  xdata_dev/ydata_dev/wdata_dev (wdata_dev may be
- * NULL) hold THIS rank's `ndata` points (with more than one rank a rank may hold none: ndata = 0,
+ * NULL; a negative first weight of this rank's points means no weights, as in splcw) hold THIS rank's `ndata` points (with more than one rank a rank may hold none: ndata = 0,
  * pointers ignored); coef_dev receives ncol coefficients (identical on every rank).  A rank whose
  * arguments are rejected still takes part in the first reduction, which carries an error flag: that
  * rank returns its status, the others SPLPAK_E_COMM -- nobody is left waiting in a collective.  Synchronises `stream` before returning (the error
@@ -344,6 +344,29 @@ int32_t splpak_synth_queries_f64(int32_t ndim, int64_t ndata_before, int64_t fir
  * solve, band sweeps) can be tested in isolation against LAPACK. */
 int32_t splpak_debug_spd_band_solve_f64(int32_t n, int32_t halfbw, const double *a_lower,
                                         const double *b, double *x);
+
+/* Diagnostics: the normal equations the plan's last fit assembled (after the all-reduce of a sharded fit), in the caller's
+ * column numbering and dimension order.  nst_ref: [ncol][(7^ndim + 1) / 2], row-major; slot `code` of row i holds N(i, i + o)
+ * for the column offset o in [-3,3]^ndim with code = sum_d (o_d + 3) 7^d (dimension 0 fastest), only the slots with
+ * code <= (7^ndim - 1) / 2; slots whose column lies outside the grid are 0.  rhs: [ncol], A^T W^2 y.  Returns 0,
+ * SPLPAK_E_BADARG for a null argument, SPLPAK_E_UNSUPPORTED when there is nothing assembled to return (a rows-only plan, no
+ * fit yet, a 4-D fit the iteration answered without assembling, a failed fit, or a splpak_debug_plan_solve since the fit). */
+int32_t splpak_debug_plan_normal_equations(const splpak_plan *plan, double *nst_ref, double *rhs);
+
+/* Diagnostics: loads the caller's matrix (layout of splpak_debug_plan_normal_equations) into the plan and solves N x = b with
+ * the plan's own factorisation, exactly as a fit runs it -- expansion into the factor storage, factorisation, one solve --
+ * without iterative refinement.  b, x: [ncol] in the caller's column order; minpiv (may be NULL): the smallest pivot.
+ * Returns 0; 107 if N is not positive definite (x = 0; the plan stays usable); SPLPAK_E_BADARG for a null argument;
+ * SPLPAK_E_UNSUPPORTED for a plan without a factorisation (iteration only) or a rank of a sharded / distributed fit. */
+int32_t splpak_debug_plan_solve(splpak_plan *plan, const double *nst_ref, const double *b, double *x, double *minpiv);
+
+/* Diagnostics (host only): the fronts of the nested-dissection elimination tree of a grid (as splpak_debug_nd_tree builds it),
+ * in elimination order (postorder, the root last).  *nfronts: their number F.  With max_fronts < F nothing else is written (a
+ * sizing call); otherwise per front depth (root 0), parent (-1 for the root), w (own variables) and h (border variables),
+ * unpadded; per node in the caller's column numbering (either may be NULL): the front that owns it and its elimination position.
+ * Returns 0, 101/102/103 (grid checks) or a negative SPLPAK_E_* code. */
+int32_t splpak_debug_nd_fronts(int32_t ndim, const int32_t *nodes, int32_t split_min, int32_t *nfronts, int32_t max_fronts,
+                               int32_t *depth, int32_t *parent, int32_t *w, int32_t *h, int32_t *front_of_node, int32_t *pos_of_node);
 
 /* Diagnostics (host only, no device needed): builds the nested-dissection elimination tree the fit uses for
  * large 3-D / 4-D grids (csrc/ndtree.hpp; separators 3 nodes thick because the normal equations of the

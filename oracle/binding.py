@@ -146,6 +146,11 @@ class Port(_Base):
         L.oracle_rows_gradient.restype = C.c_int
         L.oracle_rows_gradient.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip, C.c_double, _dp, C.c_int,
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        L.oracle_rows_gradient_vec.restype = C.c_int
+        L.oracle_rows_gradient_vec.argtypes = L.oracle_rows_gradient.argtypes + [_dp]
+        L.oracle_normal_equations.restype = C.c_int
+        L.oracle_normal_equations.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip, C.c_double, C.c_int,
+                                              _dp, _dp, _dp, _dp, C.POINTER(C.c_long)]
         L.oracle_bascmp.restype = C.c_double
         L.oracle_bascmp.argtypes = [C.c_int, _dp, _ip, _ip, _dp, _dp, _ip, _ip]
 
@@ -206,6 +211,55 @@ class Port(_Base):
         if rc != 0:
             raise MemoryError("oracle_rows_gradient")
         return om.value, float(np.sqrt(s2.value)), int(nr[0]), int(nr[1])
+
+    def rows_gradient_vec(self, ndim, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, coef, nthreads=0):
+        """rho = A^T (b - A x) over the reference's rows (as rows_gradient), as a vector in the reference's column order."""
+        xdata = np.ascontiguousarray(xdata, dtype=np.float64)
+        if xdata.ndim == 1:
+            xdata = xdata.reshape(-1, 1)
+        ydata = np.ascontiguousarray(ydata, dtype=np.float64)
+        w = np.ascontiguousarray(wdata, dtype=np.float64) if wdata is not None else np.array([-1.0])
+        xmin = np.ascontiguousarray(np.atleast_1d(xmin), dtype=np.float64)
+        xmax = np.ascontiguousarray(np.atleast_1d(xmax), dtype=np.float64)
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        rho = np.zeros(int(np.prod(nodes.astype(np.int64))))
+        om, s2 = C.c_double(0.0), C.c_double(0.0)
+        nr = (C.c_long * 2)()
+        rc = self.lib.oracle_rows_gradient_vec(ndim, _ptr(xdata, _dp), xdata.shape[1], _ptr(ydata, _dp), _ptr(w, _dp), xdata.shape[0],
+                                              _ptr(xmin, _dp), _ptr(xmax, _dp), _ptr(nodes, _ip), float(xtrap), _ptr(coef, _dp),
+                                              int(nthreads), C.byref(om), C.byref(s2), nr, _ptr(rho, _dp))
+        if rc != 0:
+            raise MemoryError("oracle_rows_gradient_vec")
+        return rho
+
+    def normal_equations(self, ndim, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, nthreads=0, ndata=None, l1xdat=None):
+        """The normal equations of the reference's rows, accumulated in long double (oracle_normal_equations) ->
+        dict(N, rhs, absN, absrhs, data_rows, constraint_rows).  N / absN: half stencils (ncol, (7^ndim + 1) // 2) in the
+        reference's column numbering, slot code = sum_d (o_d + 3) 7^d of the column offset o (dimension 0 fastest).
+        `xdata` is (ndata, l1xdat) row-major; `ndata` / `l1xdat` default to its shape."""
+        xdata = np.ascontiguousarray(xdata, dtype=np.float64)
+        if xdata.ndim == 1:
+            xdata = xdata.reshape(-1, 1)
+        ydata = np.ascontiguousarray(ydata, dtype=np.float64)
+        w = np.ascontiguousarray(wdata, dtype=np.float64) if wdata is not None else np.array([-1.0])
+        xmin = np.ascontiguousarray(np.atleast_1d(xmin), dtype=np.float64)
+        xmax = np.ascontiguousarray(np.atleast_1d(xmax), dtype=np.float64)
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+        ncol = int(np.prod(nodes.astype(np.int64)))
+        hst = (7 ** ndim + 1) // 2
+        N = np.zeros((ncol, hst))
+        A = np.zeros((ncol, hst))
+        rhs = np.zeros(ncol)
+        arhs = np.zeros(ncol)
+        nr = (C.c_long * 2)()
+        rc = self.lib.oracle_normal_equations(ndim, _ptr(xdata, _dp), int(xdata.shape[1] if l1xdat is None else l1xdat), _ptr(ydata, _dp),
+                                              _ptr(w, _dp), int(xdata.shape[0] if ndata is None else ndata), _ptr(xmin, _dp), _ptr(xmax, _dp),
+                                              _ptr(nodes, _ip), float(xtrap), int(nthreads), _ptr(N, _dp), _ptr(rhs, _dp), _ptr(A, _dp),
+                                              _ptr(arhs, _dp), nr)
+        if rc != 0:
+            raise MemoryError("oracle_normal_equations")
+        return dict(N=N, rhs=rhs, absN=A, absrhs=arhs, data_rows=int(nr[0]), constraint_rows=int(nr[1]))
 
     def evaluate(self, ndim, xq, nderiv, coef, xmin, xmax, nodes):
         xq = np.ascontiguousarray(xq, dtype=np.float64)

@@ -421,9 +421,21 @@ static int sink_grad(void *ctx, int nz, const int *col, const double *val, doubl
     return 0;
 }
 
+/* oracle_rows_gradient_vec: the same, and rho itself (in the reference's column order) into rho_out when it is not NULL */
+int oracle_rows_gradient_vec(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
+                             const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
+                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out);
 int oracle_rows_gradient(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
                          const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
                          int nthreads, double *omega_out, double *ssq_out, long *nrows_out)
+{
+    return oracle_rows_gradient_vec(ndim, xdata, l1xdat, ydata, wdata, ndata, xmin, xmax, nodes, xtrap, coef, nthreads,
+                                    omega_out, ssq_out, nrows_out, NULL);
+}
+
+int oracle_rows_gradient_vec(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
+                             const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
+                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out)
 {
     long ncol = 1;
     for (int d = 0; d < ndim; ++d) ncol *= nodes[d];
@@ -456,10 +468,112 @@ int oracle_rows_gradient(int ndim, const double *xdata, int l1xdat, const double
         double r = 0.0, d = 0.0;
         for (int t = 0; t < nthreads; ++t) { r += rho[(size_t)ncol * t + i]; d += den[(size_t)ncol * t + i]; }
         if (d > 0.0 && fabs(r) / d > omega) omega = fabs(r) / d;
+        if (rho_out) rho_out[i] = r;
     }
     free(rho); free(den); free(ssq); free(nr);
     if (omega_out) *omega_out = omega;
     if (ssq_out) *ssq_out = s2;
     if (nrows_out) { nrows_out[0] = ndat; nrows_out[1] = ncons; }
+    return bad;
+}
+
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The normal equations of the reference's rows, accumulated in long double:
+ *     N    = sum over rows  a_r a_r^T       = A^T W^2 A + C^T C        rhs    = sum a_r b_r   = A^T W^2 y
+ *     absN = sum over rows  |a_r| |a_r|^T                              absrhs = sum |a_r| |b_r|
+ * Rows are generated exactly as for oracle_splcw_banded and oracle_rows_gradient (emit_rows).  N and absN are half
+ * stencils [ncol][hst] in the REFERENCE's column numbering: slot `code` of row i holds N(i, i + o), o in [-3,3]^ndim,
+ * code = sum_d (o_d + 3) 7^d (reference dimension 0 fastest), kept only for code <= centre = (7^ndim - 1) / 2,
+ * hst = centre + 1.  Slots whose column lies outside the grid stay 0.  absN / absrhs are the scales of the rounding
+ * error of any summation of the same terms.  The data rows are spread over the host threads (each with its own
+ * accumulators, as many threads as 512 MB of them allow; summed in thread order), the constraint rows follow on one.
+ * Returns 0 or 1 (out of memory); nrows_out[2]: data rows, constraint rows. */
+typedef struct {
+    int ndim, hst;
+    int rnodes[BMAXD];
+    long double *N, *absN, *rhs, *absrhs;
+    long nrows;
+} ne_t;
+static int sink_ne(void *ctx, int nz, const int *col, const double *val, double rhs)
+{
+    ne_t *E = (ne_t *)ctx;
+    long lin[BMAXNZ];                 /* sum_d m_d 7^d of every entry's column: the code of a pair is lin_t - lin_s + centre */
+    const long centre = E->hst - 1;
+    for (int k = 0; k < nz; ++k) {
+        long c = col[k], l = 0, p7 = 1;
+        for (int d = 0; d < E->ndim; ++d) { l += (c % E->rnodes[d]) * p7; c /= E->rnodes[d]; p7 *= 7; }
+        lin[k] = l;
+    }
+    for (int s = 0; s < nz; ++s) {
+        const long double vs = val[s], as = fabsl(vs);
+        const size_t row = (size_t)col[s];
+        E->rhs[row] += vs * (long double)rhs;
+        E->absrhs[row] += as * fabsl((long double)rhs);
+        long double *Nr = E->N + row * (size_t)E->hst, *Ar = E->absN + row * (size_t)E->hst;
+        for (int t = 0; t < nz; ++t) {
+            const long code = lin[t] - lin[s] + centre;
+            if (code > centre) continue;
+            const long double vt = val[t];
+            Nr[code] += vs * vt;
+            Ar[code] += as * fabsl(vt);
+        }
+    }
+    ++E->nrows;
+    return 0;
+}
+
+int oracle_normal_equations(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
+                            const double *xmin, const double *xmax, const int *nodes, double xtrap, int nthreads,
+                            double *N_out, double *rhs_out, double *absN_out, double *absrhs_out, long *nrows_out)
+{
+    if (ndim < 1 || ndim > BMAXD) return 1;
+    long ncol = 1, hst = 1;
+    for (int d = 0; d < ndim; ++d) { ncol *= nodes[d]; hst *= 7; }
+    hst = (hst + 1) / 2;
+    const size_t per = (size_t)ncol * (size_t)(2 * hst + 2);          /* long doubles of one thread's accumulators */
+    if (nthreads < 1) nthreads = omp_get_max_threads();
+    long cap = (long)((512L << 20) / (per * sizeof(long double)));
+    if (cap < 1) cap = 1;
+    if (nthreads > cap) nthreads = (int)cap;
+    if (nthreads > ndata) nthreads = ndata > 0 ? ndata : 1;
+    long double *acc = calloc(per * (size_t)nthreads, sizeof(long double));
+    long *nr = calloc((size_t)nthreads, sizeof(long));
+    if (!acc || !nr) { free(acc); free(nr); return 1; }
+    int bad = 0;
+#pragma omp parallel num_threads(nthreads) reduction(|:bad)
+    {
+        const int t = omp_get_thread_num(), T = omp_get_num_threads();
+        const long i0 = (long)ndata * t / T, i1 = (long)ndata * (t + 1) / T;
+        long double *a = acc + per * (size_t)t;
+        ne_t E = {ndim, (int)hst, {0, 0, 0, 0}, a, a + (size_t)ncol * hst, a + (size_t)2 * ncol * hst, a + (size_t)2 * ncol * hst + ncol, 0};
+        for (int d = 0; d < ndim; ++d) E.rnodes[d] = nodes[d];
+        long nc = 0;
+        bad |= emit_rows(ndim, xdata, l1xdat, ydata, wdata, ndata, (int)i0, (int)i1, 0, xmin, xmax, nodes, xtrap, sink_ne, &E, &nc);
+        nr[t] = E.nrows;
+    }
+    /* constraint rows (the histogram of all points): one pass into thread 0's accumulators */
+    ne_t E = {ndim, (int)hst, {0, 0, 0, 0}, acc, acc + (size_t)ncol * hst, acc + (size_t)2 * ncol * hst, acc + (size_t)2 * ncol * hst + ncol, 0};
+    for (int d = 0; d < ndim; ++d) E.rnodes[d] = nodes[d];
+    long ncons = 0;
+    bad |= emit_rows(ndim, xdata, l1xdat, ydata, wdata, ndata, 0, 0, 1, xmin, xmax, nodes, xtrap, sink_ne, &E, &ncons);
+    const size_t nN = (size_t)ncol * hst;
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < nN; ++i) {
+        long double s = 0.0L, a = 0.0L;
+        for (int t = 0; t < nthreads; ++t) { s += acc[per * (size_t)t + i]; a += acc[per * (size_t)t + nN + i]; }
+        if (N_out) N_out[i] = (double)s;
+        if (absN_out) absN_out[i] = (double)a;
+    }
+    for (long i = 0; i < ncol; ++i) {
+        long double s = 0.0L, a = 0.0L;
+        for (int t = 0; t < nthreads; ++t) { s += acc[per * (size_t)t + 2 * nN + i]; a += acc[per * (size_t)t + 2 * nN + ncol + i]; }
+        if (rhs_out) rhs_out[i] = (double)s;
+        if (absrhs_out) absrhs_out[i] = (double)a;
+    }
+    long ndat = 0;
+    for (int t = 0; t < nthreads; ++t) ndat += nr[t];
+    if (nrows_out) { nrows_out[0] = ndat; nrows_out[1] = ncons; }
+    free(acc); free(nr);
     return bad;
 }

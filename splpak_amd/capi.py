@@ -33,7 +33,8 @@ SYMBOLS = [
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
     "splpak_mplan_create", "splpak_mplan_destroy", "splpak_mplan_device", "splpak_mplan_rank_bytes", "splpak_mplan_factorisation", "splpak_mplan_fit_dev", "splpak_fit_multi_f64",
     "splpak_plan_device_bytes", "splpak_plan_pcg_stats", "splpak_set_default_option", "splpak_plan_set_option", "splpak_plan_get_option",
-    "splpak_debug_spd_band_solve_f64", "splpak_debug_nd_tree", "splpak_debug_nd_partition", "splpak_debug_nd_schedule", "splpak_debug_window_values", "splpak_shutdown", "splpak_set_eval_mode",
+    "splpak_debug_spd_band_solve_f64", "splpak_debug_plan_normal_equations", "splpak_debug_plan_solve", "splpak_debug_nd_fronts",
+    "splpak_debug_nd_tree", "splpak_debug_nd_partition", "splpak_debug_nd_schedule", "splpak_debug_window_values", "splpak_shutdown", "splpak_set_eval_mode",
     "splpak_last_error_message", "splpak_device_name",
 ]
 
@@ -127,6 +128,12 @@ def lib() -> C.CDLL:
     L.splpak_synth_queries_f64.argtypes = [i32, i64, i64, i64, vp, vp]
     L.splpak_debug_spd_band_solve_f64.restype = i32
     L.splpak_debug_spd_band_solve_f64.argtypes = [i32, i32, _dp, _dp, _dp]
+    L.splpak_debug_plan_normal_equations.restype = i32
+    L.splpak_debug_plan_normal_equations.argtypes = [vp, _dp, _dp]
+    L.splpak_debug_plan_solve.restype = i32
+    L.splpak_debug_plan_solve.argtypes = [vp, _dp, _dp, _dp, _dp]
+    L.splpak_debug_nd_fronts.restype = i32
+    L.splpak_debug_nd_fronts.argtypes = [i32, _ip, i32, _ip, i32, _ip, _ip, _ip, _ip, _ip, _ip]
     L.splpak_debug_nd_tree.restype = i32
     L.splpak_debug_nd_tree.argtypes = [i32, _ip, i32, i32, _dp]
     L.splpak_debug_nd_schedule.restype = i32
@@ -518,6 +525,26 @@ class Plan:
     def hist_ptr(self):
         return self._L.splpak_plan_hist_dev(self._h)
 
+    def normal_equations(self):
+        """What the last fit assembled (diagnostics) -> (N, rhs): N the half stencil (ncol, (7^ndim + 1) // 2) in the caller's
+        column numbering (include/splpak_hip.h splpak_debug_plan_normal_equations)."""
+        hst = (7 ** self.ndim + 1) // 2
+        N = np.zeros((self.ncol, hst))
+        rhs = np.zeros(self.ncol)
+        _check(self._L.splpak_debug_plan_normal_equations(self._h, _p(N, _dp), _p(rhs, _dp)))
+        return N, rhs
+
+    def debug_solve(self, N, b):
+        """Solve N x = b once with the plan's own factorisation, no refinement (diagnostics) -> (x, ierror, minpiv);
+        ierror 0 or 107."""
+        N = np.ascontiguousarray(N, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        assert N.shape == (self.ncol, (7 ** self.ndim + 1) // 2) and b.shape == (self.ncol,)
+        x = np.zeros(self.ncol)
+        mp = C.c_double(0.0)
+        rc = _check(self._L.splpak_debug_plan_solve(self._h, _p(N, _dp), _p(b, _dp), _p(x, _dp), C.byref(mp)))
+        return x, rc, mp.value
+
 
 def evaluate_dev(ndim, xq, nderiv, coef, xmin, xmax, nodes, out, stream=0):
     """Batched evaluation on torch device tensors (asynchronous on `stream`); float32 tensors take the REAL32 entry."""
@@ -631,6 +658,25 @@ def debug_nd_partition(nodes, ngpus, chunk=0, split_min=0):
     summ = dict(dcut=int(out[0]), top_fronts=int(out[1]), top_steps=int(out[2]), max_panel_bytes=out[3], normal_eq_bytes=out[4],
                 fronts=int(out[5]), depth=int(out[6]), flop=out[7])
     return ranks, summ
+
+
+def debug_nd_fronts(nodes, split_min=0):
+    """Host-only: the fronts of the nested-dissection elimination tree (postorder, root last) -> dict(depth, parent, w, h: per
+    front; front_of, pos: per node in the caller's column numbering -- owning front and elimination position)."""
+    nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+    L = lib()
+    nf = np.zeros(1, dtype=np.int32)
+    rc = _check(L.splpak_debug_nd_fronts(len(nodes), _p(nodes, _ip), int(split_min), _p(nf, _ip), 0, None, None, None, None, None, None))
+    if rc != 0:
+        raise SplpakError(f"grid rejected: {rc}")
+    n = int(nf[0])
+    out = {k: np.zeros(n, dtype=np.int32) for k in ("depth", "parent", "w", "h")}
+    ncol = int(np.prod(nodes.astype(np.int64)))
+    out["front_of"] = np.zeros(ncol, dtype=np.int32)
+    out["pos"] = np.zeros(ncol, dtype=np.int32)
+    _check(L.splpak_debug_nd_fronts(len(nodes), _p(nodes, _ip), int(split_min), _p(nf, _ip), n,
+                                    *(_p(out[k], _ip) for k in ("depth", "parent", "w", "h", "front_of", "pos"))))
+    return out
 
 
 def debug_window_values(nodes, xmin, xmax, x):

@@ -617,3 +617,33 @@ extern "C" int32_t splpak_debug_nd_schedule(int32_t ndim, const int32_t *nodes, 
     out8[6] = out8[7] = 0;
     return 0;
 }
+
+extern "C" int32_t splpak_debug_nd_fronts(int32_t ndim, const int32_t *nodes, int32_t split_min, int32_t *nfronts, int32_t max_fronts,
+                                          int32_t *depth, int32_t *parent, int32_t *w, int32_t *h, int32_t *front_of_node, int32_t *pos_of_node)
+{
+    using namespace splpak;
+    double xmin[MAXD] = {0, 0, 0, 0}, xmax[MAXD] = {1, 1, 1, 1};
+    Grid g;
+    if (!nodes || !nfronts) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    const int v = build_grid(ndim, nodes, xmin, xmax, g, nullptr, true);
+    if (v != 0) return v;
+    NdTree t;
+    if (!nd_build(g, t, split_min > 0 ? split_min : nd_default_split_min(ndim))) { set_error("nested dissection: inconsistent tree"); return SPLPAK_E_BADARG; }
+    const int nf = (int)t.fr.size();
+    *nfronts = nf;
+    if (max_fronts < nf) return 0;                  // (sizing call: nothing else written)
+    if (!depth || !parent || !w || !h) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    for (int f = 0; f < nf; ++f) {
+        depth[f] = t.fr[(size_t)f].depth;
+        parent[f] = t.fr[(size_t)f].parent;
+        w[f] = t.fr[(size_t)f].w;
+        h[f] = t.fr[(size_t)f].h;
+    }
+    for (int i = 0; i < g.ncol; ++i) {
+        long long r = 0;
+        for (int d = 0; d < g.ndim; ++d) r += (long long)((i / g.colstride[d]) % g.nodes[d]) * g.refstride[d];
+        if (front_of_node) front_of_node[r] = t.front_of[(size_t)i];
+        if (pos_of_node) pos_of_node[r] = t.pos[(size_t)i];
+    }
+    return 0;
+}

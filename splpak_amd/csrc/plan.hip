@@ -501,6 +501,7 @@ int64_t splpak_plan_device_bytes(const splpak_plan *p)
 int32_t splpak_plan_factorisation(const splpak_plan *p, char *buf, int32_t buflen)
 {
     if (!p) return SPLPAK_E_BADARG;
+    OptionsScope opt_scope(&p->opt);                  // (the narrow limit as the plan's fits see it)
     int code = 0;
     const char *what = "band Cholesky, four-stream look-ahead pipeline (csrc/bandchol.hip)";
     if (p->solver_mode == 2) { code = 6; what = "preconditioned conjugate gradients on the rows, separable preconditioner (csrc/pcg.hip); no factorisation"; }
@@ -547,6 +548,41 @@ static int do_allreduce(splpak_plan *p, double *buf, long long count, hipStream_
 
 }  // extern "C" (the next function has C++ linkage: it is called from ndchol.hip)
 namespace splpak { int plan_allreduce(splpak_plan *p, double *buf, long long count, hipStream_t st) { return do_allreduce(p, buf, count, st); } }
+// a failure inside the factorisation / solve hooks: a communication failure is not a device fault (round-3 advice)
+#define SPLPAK_HOOK_TRY(expr)                                                        \
+    do {                                                                             \
+        const hipError_t he_ = (expr);                                               \
+        if (p->comm_failed) { (void)hipGetLastError(); return SPLPAK_E_COMM; }       \
+        if (!::splpak::hip_ok(he_, #expr)) return SPLPAK_E_NODEVICE;                 \
+    } while (0)
+
+// The plan's factorisation of the half stencil in p->nst, as the fit runs it and as splpak_debug_plan_solve runs it alone:
+// clear the pivot flag, expand into the factor storage, factor, read back the flag (0: positive definite) and the smallest
+// pivot.  e0 / e1: events recorded around the expansion (NULL: none).
+static int plan_factor(splpak_plan *p, hipStream_t st, int *hinfo, double *minpiv, hipEvent_t e0, hipEvent_t e1)
+{
+    const double inf = std::numeric_limits<double>::infinity();
+    SPLPAK_HIP_TRY(hipMemsetAsync(p->info, 0, 2 * sizeof(int), st), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemcpyAsync(p->small + 2, &inf, sizeof(double), hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+    if (e0) (void)hipEventRecord(e0, st);
+    SPLPAK_HIP_TRY(p->expand_fn ? p->expand_fn(p, st, p->fn_user) : launch_expand(p->g, p->nst, p->band, p->dm, st), SPLPAK_E_NODEVICE);
+    if (e1) (void)hipEventRecord(e1, st);
+    SPLPAK_HOOK_TRY(p->factor_fn ? p->factor_fn(p, p->info, p->small + 2, st, p->fn_user) : band_cholesky(p->band, p->info, p->small + 2, st, &p->stats));
+    *hinfo = 0;
+    *minpiv = 0.0;
+    SPLPAK_HIP_TRY(hipMemcpyAsync(hinfo, p->info, sizeof(int), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemcpyAsync(minpiv, p->small + 2, sizeof(double), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+    return 0;
+}
+
+// v <- N^-1 v with the factor plan_factor left (v: b.npad doubles, internal order, zero padding)
+static int plan_factor_solve(splpak_plan *p, double *v, hipStream_t st)
+{
+    SPLPAK_HOOK_TRY(p->solve_fn ? p->solve_fn(p, v, p->tmp, st, p->fn_user) : band_solve(p->band, v, p->tmp, st));
+    return 0;
+}
+
 extern "C" {
 
 int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, const double *y,
@@ -567,14 +603,15 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     if (lerr != 0 && p->world <= 1) return lerr;
     if (lerr != 0) ndata = 0;
     p->comm_failed = false;
-    // a failure inside the factorisation / solve hooks: a communication failure is not a device fault (round-3 advice)
-#define SPLPAK_HOOK_TRY(expr)                                                        \
-    do {                                                                             \
-        const hipError_t he_ = (expr);                                               \
-        if (p->comm_failed) { (void)hipGetLastError(); return SPLPAK_E_COMM; }       \
-        if (!::splpak::hip_ok(he_, #expr)) return SPLPAK_E_NODEVICE;                 \
-    } while (0)
+    p->ne_valid = false;
     hipStream_t st = (hipStream_t)stream;
+    if (lerr == 0 && w && ndata > 0) {
+        // a negative first weight means "no weights" (:796, :890), as in the host entry points: one value read back
+        double w0 = 0.0;
+        SPLPAK_HIP_TRY(hipMemcpyAsync(&w0, w, sizeof(double), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+        if (w0 < 0.0) w = nullptr;
+    }
     const Grid &g = p->g;
     const Band &b = p->band;
     const bool smooth = p->xtrap != 0.0;                              // swght, :769
@@ -613,6 +650,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         SPLPAK_HIP_TRY(launch_sparse_mark(g, p->hist, p->scalH, p->xtrap, p->dcw, p->spf, st), SPLPAK_E_NODEVICE);
         SPLPAK_HIP_TRY(launch_constraint_rows(g, p->dcw, p->spf, p->ctab, p->nst, p->scalG, st), SPLPAK_E_NODEVICE);
         rows_fit = false;
+        p->ne_valid = true;
         return 0;
     };
     if (rows_fit) {
@@ -648,6 +686,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     }
     stamp(3);
     if (int r = do_allreduce(p, p->rows_only ? p->rhs : p->nst, p->lenG, st)) return r;
+    p->ne_valid = !rows_fit;
 
     SPLPAK_HIP_TRY(hipMemcpyAsync(hs, p->scalG, sizeof(double) * SC_COUNT, hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
     // scalG and scalH are not adjacent (hist sits between): fetch scalH separately
@@ -793,17 +832,9 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     if (!solved && rows_fit && lazy)
         if (int r = assemble_now()) return r;
     if (!solved) {
-        SPLPAK_HIP_TRY(hipMemsetAsync(p->info, 0, 2 * sizeof(int), st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(hipMemcpyAsync(p->small + 2, &inf, sizeof(double), hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
-        stamp(4);
-        SPLPAK_HIP_TRY(p->expand_fn ? p->expand_fn(p, st, p->fn_user) : launch_expand(g, p->nst, b, p->dm, st), SPLPAK_E_NODEVICE);
-        stamp(5);
-        SPLPAK_HOOK_TRY(p->factor_fn ? p->factor_fn(p, p->info, p->small + 2, st, p->fn_user) : band_cholesky(b, p->info, p->small + 2, st, &p->stats));
         int hinfo = 0;
         double minpiv = 0.0;
-        SPLPAK_HIP_TRY(hipMemcpyAsync(&hinfo, p->info, sizeof(int), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(hipMemcpyAsync(&minpiv, p->small + 2, sizeof(double), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+        if (int r = plan_factor(p, st, &hinfo, &minpiv, stamps ? p->evStage[4] : nullptr, stamps ? p->evStage[5] : nullptr)) return r;
         t2 = clk::now();
         if (info) {
             info[4] = minpiv;
@@ -816,10 +847,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
             set_error("normal equations not positive definite (suprls 34)");
             return 107;
         }
-        const int r = solve_and_refine([&](double *v, bool) -> int {
-            SPLPAK_HOOK_TRY(p->solve_fn ? p->solve_fn(p, v, p->tmp, st, p->fn_user) : band_solve(b, v, p->tmp, st));
-            return 0;
-        });
+        const int r = solve_and_refine([&](double *v, bool) -> int { return plan_factor_solve(p, v, st); });
         if (r != 0) return r;
     }
     // estimated error left after the last step (exact 0 when it met the tolerance outright)
@@ -1346,6 +1374,107 @@ int32_t splpak_debug_spd_band_solve_f64(int32_t n, int32_t halfbw, const double 
     band_pipeline_destroy(b.pipe);
     for (void *q : holder.owned) (void)hipFree(q);
     return rc;
+}
+
+}  // extern "C"
+
+// Where every entry of the plan's half stencil (internal dimension order, nst[i][code], code <= centre) lives in the half stencil
+// of the caller's (reference) column numbering and dimension order: index into [ncol][hstencil], or -1 for a slot whose column lies
+// outside the grid.  The two layouts hold the same entries of the symmetric N: an entry whose reference code lies above the centre
+// is stored in the row of its column, at the mirrored offset.
+static std::vector<long long> ref_stencil_map(const Grid &g)
+{
+    const int nd = g.ndim, hs = g.hstencil, centre = hs - 1;
+    std::vector<long long> map((size_t)g.ncol * (size_t)hs, -1);
+    int p7[MAXD];
+    for (int d = 0, m = 1; d < MAXD; ++d, m *= 7) p7[d] = m;
+    for (int i = 0; i < g.ncol; ++i) {
+        int id[MAXD];
+        long long iref = 0;
+        for (int d = 0; d < nd; ++d) {
+            id[d] = (i / g.colstride[d]) % g.nodes[d];
+            iref += (long long)id[d] * g.refstride[d];
+        }
+        for (int c = 0; c < hs; ++c) {
+            int cref = 0;
+            long long jref = iref;
+            bool in = true;
+            for (int d = 0; d < nd; ++d) {
+                const int o = (c / p7[d]) % 7 - 3;
+                if (id[d] + o < 0 || id[d] + o >= g.nodes[d]) in = false;
+                cref += (o + 3) * p7[g.perm[d]];
+                jref += (long long)o * g.refstride[d];
+            }
+            if (!in) continue;
+            map[(size_t)i * hs + c] = cref <= centre ? iref * hs + cref : jref * hs + (2 * centre - cref);
+        }
+    }
+    return map;
+}
+
+static long long ref_column(const Grid &g, int i)
+{
+    long long r = 0;
+    for (int d = 0; d < g.ndim; ++d) r += (long long)((i / g.colstride[d]) % g.nodes[d]) * g.refstride[d];
+    return r;
+}
+
+extern "C" {
+
+int32_t splpak_debug_plan_normal_equations(const splpak_plan *p, double *nst_ref, double *rhs)
+{
+    if (!p || !nst_ref || !rhs) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (p->rows_only || !p->nst) { set_error("the plan never assembles the normal equations (rows-only plan)"); return SPLPAK_E_UNSUPPORTED; }
+    if (!p->ne_valid) {
+        set_error("the plan's last fit did not assemble the normal equations (no fit yet, an iteration that answered without them, or a failure)");
+        return SPLPAK_E_UNSUPPORTED;
+    }
+    if (int r = device_ready()) return r;
+    const Grid &g = p->g;
+    const size_t nst_n = (size_t)g.ncol * (size_t)g.hstencil;
+    std::vector<double> h(nst_n), r((size_t)g.ncol);
+    SPLPAK_HIP_TRY(hipMemcpy(h.data(), p->nst, sizeof(double) * nst_n, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemcpy(r.data(), p->rhs, sizeof(double) * (size_t)g.ncol, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    const std::vector<long long> map = ref_stencil_map(g);
+    std::memset(nst_ref, 0, sizeof(double) * nst_n);
+    for (size_t t = 0; t < nst_n; ++t)
+        if (map[t] >= 0) nst_ref[map[t]] = h[t];
+    for (int i = 0; i < g.ncol; ++i) rhs[ref_column(g, i)] = r[(size_t)i];
+    return 0;
+}
+
+int32_t splpak_debug_plan_solve(splpak_plan *p, const double *nst_ref, const double *b, double *x, double *minpiv)
+{
+    if (!p || !nst_ref || !b || !x) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    OptionsScope opt_scope(&p->opt);
+    if (p->rows_only || !p->nst || p->solver_mode == 2 || !p->band.ab) { set_error("the plan has no factorisation"); return SPLPAK_E_UNSUPPORTED; }
+    if (p->world > 1 || p->dm.R > 1) { set_error("not for a rank of a sharded or distributed fit"); return SPLPAK_E_UNSUPPORTED; }
+    if (int r = device_ready()) return r;
+    const Grid &g = p->g;
+    const size_t nst_n = (size_t)g.ncol * (size_t)g.hstencil;
+    const std::vector<long long> map = ref_stencil_map(g);
+    std::vector<double> h(nst_n), v((size_t)p->band.npad, 0.0);
+    for (size_t t = 0; t < nst_n; ++t) h[t] = map[t] >= 0 ? nst_ref[map[t]] : 0.0;
+    for (int i = 0; i < g.ncol; ++i) v[(size_t)i] = b[ref_column(g, i)];
+    hipStream_t st = nullptr;
+    p->comm_failed = false;
+    p->ne_valid = false;                  // (the half stencil now holds the caller's matrix)
+    SPLPAK_HIP_TRY(hipMemcpy(p->nst, h.data(), sizeof(double) * nst_n, hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemcpy(p->xvec, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
+    if (p->prefit_fn) SPLPAK_HIP_TRY(p->prefit_fn(p, st, p->fn_user), SPLPAK_E_NODEVICE);
+    int hinfo = 0;
+    double mp = 0.0;
+    if (int r = plan_factor(p, st, &hinfo, &mp, nullptr, nullptr)) return r;
+    if (minpiv) *minpiv = mp;
+    if (hinfo != 0) {
+        std::memset(x, 0, sizeof(double) * (size_t)g.ncol);
+        set_error("normal equations not positive definite (suprls 34)");
+        return 107;
+    }
+    if (int r = plan_factor_solve(p, p->xvec, st)) return r;
+    SPLPAK_HIP_TRY(hipMemcpy(v.data(), p->xvec, sizeof(double) * (size_t)g.ncol, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    for (int i = 0; i < g.ncol; ++i) x[ref_column(g, i)] = v[(size_t)i];
+    return 0;
 }
 
 void splpak_shutdown(void)
