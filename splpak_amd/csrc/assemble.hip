@@ -27,7 +27,7 @@
 //                          fixed order, into its stencil row, right-hand side and histogram entry
 //   constraint_rows_kernel derivative-constraint rows of data-sparse nodes (:921-1046), gathered
 //                          per stencil row from the <= 3^d sparse neighbours
-//   residual_block_kernel / constraint_dots_kernel / rho_gather_kernel
+//   residual_wave_kernel (1-D .. 3-D), residual_cell4_kernel (4-D) / constraint_dots_kernel / rho_gather_kernel
 //                          rho = A^T W (W y - W A x) - C^T C x for iterative refinement, same
 //                          owner-gathers structure
 //   expand_kernel          half stencil -> band storage of the Cholesky factorisation
@@ -1425,67 +1425,10 @@ hist_total_kernel(const double *__restrict__ hist, int n, double *__restrict__ s
     if (t == 0) scal[SC_TOTLWT] = part[0];
 }
 
-template <int D>
-struct ResCfg;
-template <> struct ResCfg<4> { static constexpr int NB = 256, NT = 256, PCH = 16; };
-
 // per-cell share of rho = A^T W (W y - W A x): rcell[cell][c] (plain stores; empty cells are skipped by the gather).
-// Workgroup per cell: the 4-D form (256 window functions); 1-D .. 3-D grids use residual_wave_kernel below.
-template <int D>
-__global__ void __launch_bounds__(ResCfg<D>::NT)
-residual_block_kernel(Grid g, const int *__restrict__ offset, const double *__restrict__ xs,
-                      const double *__restrict__ ys, const double *__restrict__ ws, long long cap,
-                      const double *__restrict__ xvec, double *__restrict__ rcell, double *__restrict__ ssq)
-{
-    using C = ResCfg<D>;
-    constexpr int NB = C::NB, NT = C::NT, PCH = C::PCH, LDB = NB + 1;
-    const int cell = blockIdx.x;
-    const long long beg = offset[cell], end = offset[cell + 1];
-    if (beg == end) return;
-
-    __shared__ double tab[PCH * D * 4];
-    __shared__ double bw[PCH * LDB];
-    __shared__ double wy[PCH];
-    __shared__ double wt[PCH];
-    __shared__ double xloc[NB];
-
-    const int tid = threadIdx.x;
-    int colbase = 0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) colbase += ((cell / g.cellstride[d]) % g.cells[d]) * g.colstride[d];
-    if (tid < NB) xloc[tid] = xvec[local_col<D>(g, colbase, tid)];
-    double racc = 0.0, e2 = 0.0;
-    for (long long p0 = beg; p0 < end; p0 += PCH) {
-        const int np = (int)((end - p0 < PCH) ? (end - p0) : PCH);
-        stage_points<D, NB, LDB, NT>(g, xs, ys, ws, cap, p0, np, tab, bw, wy, wt, nullptr, nullptr);
-        // e_p = w y - (w b) . x   (row residual)
-        for (int p = tid; p < np; p += NT) {
-            double dot = 0.0;
-            for (int c = 0; c < NB; ++c) dot += bw[p * LDB + c] * xloc[c];
-            wy[p] = wy[p] - dot;
-            e2 += wy[p] * wy[p];
-        }
-        __syncthreads();
-        if (tid < NB)
-            for (int p = 0; p < np; ++p) racc += bw[p * LDB + tid] * wy[p];
-        __syncthreads();
-    }
-    if (tid < NB) rcell[(long long)cell * NB + tid] = racc;
-    if (ssq) {                                   // sum of squared row residuals (the reference's errsum; a diagnostic):
-        e2 = wave_sum(e2);                       // the cell's share, its waves added in a fixed order (no atomics: reproducible)
-        if ((tid & 63) == 0) wt[tid >> 6] = e2;
-        __syncthreads();
-        if (tid == 0) {
-            double t = 0.0;
-            for (int wv = 0; wv < NT / 64; ++wv) t += wt[wv];
-            ssq[cell] = t;
-        }
-    }
-}
-
-// The same per-cell share for 1-D .. 3-D grids (NB = 4^D <= 64), ONE WAVE per cell, four cells per workgroup, no
-// workgroup barriers (round 3: the workgroup-per-cell form above spent 1.67 ms per pass at C3 -- 227 000 workgroups of 256
-// threads for 44 points each, staged through five __syncthreads -- for 0.4 GB of points; four passes per fit).
+// 1-D .. 3-D grids (NB = 4^D <= 64): ONE WAVE per cell, four cells per workgroup, no workgroup barriers (round 3: the
+// workgroup-per-cell form of rounds 1-2 spent 1.67 ms per pass at C3 -- 227 000 workgroups of 256 threads for 44 points
+// each, staged through five __syncthreads -- for 0.4 GB of points; four passes per fit).
 //   phase 1  lane = point:  the D window tables (parked in the wave's LDS slice), t = (w b) . x against the cell's 4^D
 //            coefficients (LDS broadcast reads), e = w y - t
 //   phase 2  lane = (window function c, point group):  racc_c += (w b)_c * e  over the points
@@ -1593,8 +1536,8 @@ residual_wave_kernel(Grid g, const int *__restrict__ offset, const double *__res
     }
 }
 
-// The 4-D form of the same share (256 window functions), one workgroup of four waves per cell (round 3: the staged form above,
-// which builds the full 16 x 256 row image of a chunk in LDS, took 7.5 ms per pass at 16^4 / 10^7 points):
+// The 4-D form of the same share (256 window functions), one workgroup of four waves per cell (round 3: the staged form of
+// rounds 1-2, which built the full 16 x 256 row image of a chunk in LDS, took 7.5 ms per pass at 16^4 / 10^7 points):
 //   phase 1  wave k3, lane = point: b3[k3] * (factorised window sum of the slab k3 of the cell's coefficients) -> 4 partials
 //   phase 2  thread = window function: racc_c += (w b)_c * e over the points
 template <int D>
@@ -2329,7 +2272,7 @@ hipError_t launch_gram(const Grid &g, const SortScratch &s, double *scratch, lon
         double *rblk = blk + (long long)ncells * gram_tri(g.nb);
         double *hblk = smooth ? rblk + (long long)ncells * g.nb : nullptr;
         DISPATCH_D(g.ndim, {
-            const bool zeroed = gram_cells<D>(g, s, blk, rblk, hblk, hist, cell0, ncells, st) && !splpak::opt_get("SPLPAK_GATHER_LOOKUP");
+            const bool zeroed = gram_cells<D>(g, s, blk, rblk, hblk, hist, cell0, ncells, st);
             const dim3 gg((unsigned)((node1 - node0 + 3) / 4));
             if (zeroed)
                 hipLaunchKernelGGL((stencil_gather_kernel<D, true>), gg, dim3(256), 0, st, g,
@@ -2410,15 +2353,9 @@ static void residual_cells(const Grid &g, const SortScratch &s, const double *xv
                            (const int *)s.offset, (const double *)s.xs, (const double *)s.ys, (const double *)s.ws,
                            s.cap, xvec, rcell, e2c);
     } else {
-        const bool old_form = splpak::opt_get("SPLPAK_RESIDUAL_STAGED") != nullptr;      // A/B switch
-        if (old_form)
-            hipLaunchKernelGGL(residual_block_kernel<D>, dim3((unsigned)g.ncell), dim3(ResCfg<D>::NT), 0, st, g,
-                               (const int *)s.offset, (const double *)s.xs, (const double *)s.ys, (const double *)s.ws,
-                               s.cap, xvec, rcell, e2c);
-        else
-            hipLaunchKernelGGL(residual_cell4_kernel<D>, dim3((unsigned)g.ncell), dim3(256), 0, st, g,
-                               (const int *)s.offset, (const double *)s.xs, (const double *)s.ys, (const double *)s.ws,
-                               s.cap, xvec, rcell, e2c);
+        hipLaunchKernelGGL(residual_cell4_kernel<D>, dim3((unsigned)g.ncell), dim3(256), 0, st, g,
+                           (const int *)s.offset, (const double *)s.xs, (const double *)s.ys, (const double *)s.ws,
+                           s.cap, xvec, rcell, e2c);
     }
 }
 

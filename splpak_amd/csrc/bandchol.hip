@@ -927,11 +927,9 @@ hipError_t band_cholesky(const Band &b, int *info_dev, double *minpiv_dev, hipSt
     if (nfinish < 0 || nfinish > b.nblk) nfinish = b.nblk;
     if (kbeg < 0 || kbeg >= kend) return hipErrorInvalidValue;
     const bool partial = kend < b.nblk;
-    {   // narrow bands: the two-stream form below (SPLPAK_NO_NARROW keeps the four-stream pipeline, for comparison)
-        if (b.bw < narrow_band_limit() && !splpak::opt_get("SPLPAK_NO_NARROW")) {
-            if (stats) *stats = CholStats{stats->enabled};
-            return band_cholesky_narrow(b, info_dev, minpiv_dev, st, kbeg, kend, nfinish);
-        }
+    if (b.bw < narrow_band_limit()) {               // narrow bands: the two-stream form
+        if (stats) *stats = CholStats{stats->enabled};
+        return band_cholesky_narrow(b, info_dev, minpiv_dev, st, kbeg, kend, nfinish);
     }
     const bool timing = stats && stats->enabled;
     const auto t_enq = std::chrono::steady_clock::now();
@@ -966,7 +964,6 @@ hipError_t band_cholesky(const Band &b, int *info_dev, double *minpiv_dev, hipSt
     // bulk = true: the launch that carries ~92 % of the flops; it is a separate template
     // instantiation (ABL bit 8, no functional difference) so that profilers list it under its own
     // name, and it alone feeds the roofline statistics
-    const bool bulk_stop_event = splpak::opt_get("SPLPAK_NO_STOPEV") == nullptr;
     auto syrk = [&](hipStream_t s, int k, int cb, int ce, int rb, int re, bool bulk = false) {
         const int k0 = k * NBLK;
         long long items = 0;
@@ -976,10 +973,10 @@ hipError_t band_cholesky(const Band &b, int *info_dev, double *minpiv_dev, hipSt
         // Timed bulk launches carry their HIP events in the dispatch itself (hipExtLaunchKernelGGL:
         // start/stop are taken from the kernel's own dispatch packet), so timing adds no packet to
         // the stream; events recorded around the launch cost ~4 us each between two launches.
-        const bool timed = timing && bulk && bulk_stop_event;
+        const bool timed = timing && bulk;
         if (timed) a = pl.evA[k];
         // the bulk launch's completion IS evU[k]: no separate event record behind it in the stream
-        if (bulk && bulk_stop_event) c = pl.evU[k];
+        if (bulk) c = pl.evU[k];
         const bool queued = pl.reserved != ~0u && qnext < pl.nqueues;
         const int margin = queued ? 512 : 0;
         int *queue = queued ? pl.queues + 2 * (qnext++) : nullptr;
@@ -1001,7 +998,6 @@ hipError_t band_cholesky(const Band &b, int *info_dev, double *minpiv_dev, hipSt
             stats->bulk_flop += 2.0 * (double)items * 64 * 64 * NBLK;
         }
     };
-    const bool top32 = splpak::opt_get("SPLPAK_TOPA64") == nullptr;          // topA in 32x32 pieces (36 waves) unless asked otherwise
     auto potrf = [&](int k) {        // potrf(k) (+ the 16x16 leaf inverses) pinned to the reserved CU
         const int k0 = k * NBLK;
         if (sR != sP) {
@@ -1054,9 +1050,8 @@ hipError_t band_cholesky(const Band &b, int *info_dev, double *minpiv_dev, hipSt
             (void)hipStreamWaitEvent(sP, pl.evU[k - 1], 0);
             (void)hipStreamWaitEvent(sC, pl.evU[k - 1], 0);
         }
-        if (top32)                                      // topA: block (k+1,k+1), in 36 32x32 pieces
-            hipLaunchKernelGGL(syrk32_kernel, dim3(36), dim3(64), 0, sP, b.ab, b.lda, k * NBLK, k * NBLK + NBLK, 8);
-        else syrk(sP, k, 0, 4, 0, 4);
+        // topA: block (k+1,k+1), in 36 32x32 pieces
+        hipLaunchKernelGGL(syrk32_kernel, dim3(36), dim3(64), 0, sP, b.ab, b.lda, k * NBLK, k * NBLK + NBLK, 8);
         if (next) potrf(k + 1);
         (void)hipStreamWaitEvent(sC, pl.evP[k], 0);
         syrk(sC, k, 0, 4, 4, n64 < 8 ? n64 : 8);        // topB: block (k+2,k+1)
@@ -1072,7 +1067,6 @@ hipError_t band_cholesky(const Band &b, int *info_dev, double *minpiv_dev, hipSt
         }
         (void)hipStreamWaitEvent(sU, pl.evP[k], 0);
         syrk(sU, k, 4, n64, 0, n64, true);              // bulk: block columns >= k+2
-        if (!bulk_stop_event) (void)hipEventRecord(pl.evU[k], sU);
     }
     if (partial) {                                 // the last step's chain and column pieces are not followed by a panel
         (void)hipEventRecord(pl.evT[kend], sP);

@@ -984,7 +984,6 @@ struct NdState {
     int xmode = 1;                                 // XCD-aware item map of the Schur passes (SPLPAK_ND_XCD=0: off)
     int full_diag = 0;                             // (A/B: diagonal items compute all 16 tiles)
     bool small_queue = false;                      // (A/B: small launches take the item queue too)
-    int pinned_split = 4;                          // most waves per item of a small launch that runs beside a bulk update
     int wg4 = 0;                                   // 1: Schur launches in 4-wave workgroups, 2: the panel updates too
     int small_grid = 1024;                         // update launches of at most this many items are split over 4 waves per item, a quarter of it: 16
     int *queues = nullptr;                         // [nqueues][2] item counters of the update launches of one factorisation
@@ -1529,7 +1528,7 @@ void launch_syrk(NdState *s, const JobTable<SyrkJob> &tab, const Launch &l, hipS
     // (beside a bulk update that fills every wave slot -- `pinned` -- the waves of this launch are placed as slots retire,
     // ~37 per us at 64^3: sixteen waves per item then wait longer than they save; four per item there)
     int split = (int)l.grid * 4 <= s->small_grid ? 16 : ((int)l.grid <= s->small_grid ? 4 : 1);
-    if (pinned && split > s->pinned_split) split = s->pinned_split;
+    if (pinned && split > 4) split = 4;
     const int nit = (int)l.grid * split;
     const bool wg4 = split == 1 && (s->wg4 >= 2 || (s->wg4 == 1 && schur));
     unsigned gx = wg4 ? (l.grid + 3) / 4 : l.grid * (unsigned)split;
@@ -1698,7 +1697,7 @@ hipError_t nd_factor(splpak_plan *p, int *info_dev, double *minpiv_dev, hipStrea
             const long long tiles = trapezoid_items(nt, nt);
             if (s->sc.packed) {
                 if (plan_allreduce(p, s_ptr(s, id), nd_schur_doubles(f, true), st) != 0) comm_failed = true;
-            } else if (tiles * 4096 <= scap && !splpak::opt_get("SPLPAK_ND_JOIN_SQUARE")) {
+            } else if (tiles * 4096 <= scap) {
                 hipLaunchKernelGGL(nd_tripack_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, st, s_ptr(s, id), f.lds, nt, scratch);
                 if (plan_allreduce(p, scratch, tiles * 4096, st) != 0) comm_failed = true;
                 hipLaunchKernelGGL(nd_tripack_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, st, s_ptr(s, id), f.lds, nt, scratch);
@@ -2060,14 +2059,6 @@ bool nd_make_schedule(NdState *s, int cut, size_t other_bytes)
         s->starts[(size_t)S.first].push_back(i);
         if (S.ids.size() == 1 && t.fr[(size_t)S.ids[0]].parent < 0 && !s->mdist) s->root_stage = i;
     }
-    if (splpak::opt_get("SPLPAK_ND_DEBUG_STAGES"))
-        for (int i = 0; i < ns; ++i) {
-            const NdStage &S = s->sc.st[(size_t)i];
-            long long pd = 0, cols = 0;
-            for (int id : S.ids) { const NdFront &f = t.fr[(size_t)id]; pd += f.ld * (long long)f.wp; cols += f.wp; }
-            fprintf(stderr, "[nd stage %d] depth %d, %zu fronts, first %d, dep %d, panels %.3f GB in %lld columns, Schur %.3f GB\n", i, S.depth, S.ids.size(), S.first, S.dep,
-                    8e-9 * (double)pd, cols, 8e-9 * (double)S.doubles);
-        }
     s->istarts.assign((size_t)std::max(ns, 1), {});
     for (int i = 0; i < ns; ++i) {
         const NdStage &S = s->sc.st[(size_t)i];
@@ -2324,8 +2315,6 @@ int nd_attach(splpak_plan *p, double **factor_arena, long long *factor_doubles, 
     std::vector<int>().swap(t.bvar);
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (const char *e = splpak::opt_get("SPLPAK_ND_DUMMY_STREAMS"))        // (experiment: how the streams fall onto the hardware queues)
-        for (int i = 0; i < atoi(e); ++i) { hipStream_t q; (void)hipStreamCreateWithFlags(&q, hipStreamNonBlocking); }
     (void)hipStreamCreateWithPriority(&s->sP, hipStreamNonBlocking, hi);
     (void)hipStreamCreateWithFlags(&s->sU, hipStreamNonBlocking);
     for (hipEvent_t *e : {&s->ev0, &s->evJ, &s->evU, &s->evZlast, &s->evDone, &s->evPre, &s->evTail, &s->evR0}) (void)hipEventCreateWithFlags(e, hipEventDisableTiming);
@@ -2333,7 +2322,6 @@ int nd_attach(splpak_plan *p, double **factor_arena, long long *factor_doubles, 
     s->nqueues = 8 * t.nblocks + 64;
     if (const char *e = splpak::opt_get("SPLPAK_ND_SMALL_GRID")) s->small_grid = atoi(e);
     if (const char *e = splpak::opt_get("SPLPAK_ND_WG4")) s->wg4 = atoi(e);
-    if (const char *e = splpak::opt_get("SPLPAK_ND_PINNED_SPLIT")) s->pinned_split = atoi(e);
     s->small_queue = splpak::opt_get("SPLPAK_ND_SMALL_QUEUE") != nullptr;
     if (const char *e = splpak::opt_get("SPLPAK_ND_POTRF_WAVES")) s->potrf_waves = atoi(e);
     if (!nd_alloc(s, &s->queues, (size_t)ND_QSTRIDE * s->nqueues) || !nd_alloc(s, &s->resmap, (size_t)128)) return SPLPAK_E_NOMEM;

@@ -19,10 +19,6 @@ const Known KNOWN[] = {
     {"SPLPAK_DEBUG_SUMS", 0},
     {"SPLPAK_DEBUG_TWOEND", 0},
     {"SPLPAK_DIST_CHUNK", 0},
-    {"SPLPAK_EVAL_NO_PERSISTENT", 0},
-    {"SPLPAK_EVAL_RUNS_MAXBINS", 0},
-    {"SPLPAK_EVAL_SORT", 0},
-    {"SPLPAK_GATHER_LOOKUP", 0},
     {"SPLPAK_GRAM_SCRATCH_MB", 1},
     {"SPLPAK_GRAM_VALU", 0},
     {"SPLPAK_MPLAN_BAND", 0},
@@ -33,18 +29,14 @@ const Known KNOWN[] = {
     {"SPLPAK_ND_CHUNK", 0},
     {"SPLPAK_ND_CLEAR_WGS", 0},
     {"SPLPAK_ND_CUT", 1},
-    {"SPLPAK_ND_DEBUG_STAGES", 0},
     {"SPLPAK_ND_DIST", 0},
-    {"SPLPAK_ND_DUMMY_STREAMS", 0},
     {"SPLPAK_ND_FULL_DIAG", 0},
     {"SPLPAK_ND_HALVES", 0},
-    {"SPLPAK_ND_JOIN_SQUARE", 0},
     {"SPLPAK_ND_KB", 1},
     {"SPLPAK_ND_NO_EARLY_CLEAR", 0},
     {"SPLPAK_ND_NO_FUSE", 0},
     {"SPLPAK_ND_NO_OUTER", 0},
     {"SPLPAK_ND_NO_ROOT_LOOKAHEAD", 0},
-    {"SPLPAK_ND_PINNED_SPLIT", 0},
     {"SPLPAK_ND_PIN_FIRST", 0},
     {"SPLPAK_ND_PIN_ROUNDS", 0},
     {"SPLPAK_ND_POTRF_WAVES", 0},
@@ -58,44 +50,32 @@ const Known KNOWN[] = {
     {"SPLPAK_ND_STAGED_INIT", 0},
     {"SPLPAK_ND_WG4", 0},
     {"SPLPAK_ND_XCD", 0},
-    {"SPLPAK_NO_CONSTRAINT_TABLE", 0},
     {"SPLPAK_NO_LOOKAHEAD", 0},
-    {"SPLPAK_NO_NARROW", 0},
     {"SPLPAK_NO_PANEL_CU", 0},
     {"SPLPAK_NO_PLAN_CACHE", 1},
     {"SPLPAK_NO_REORDER", 1},
-    {"SPLPAK_NO_STOPEV", 0},
     {"SPLPAK_NO_TWOEND", 0},
     {"SPLPAK_PCG_ALWAYS", 0},
     {"SPLPAK_PCG_ASSEMBLE", 0},
-    {"SPLPAK_PCG_BLOCKS_F64", 0},
-    {"SPLPAK_PCG_BLOCKS_UNPACKED", 0},
     {"SPLPAK_PCG_EAGER", 0},
     {"SPLPAK_PCG_MAXIT", 1},
     {"SPLPAK_PCG_NO_BLOCKS", 0},
     {"SPLPAK_PCG_NO_PAIRS", 0},
     {"SPLPAK_PCG_PAIRS_VALU", 0},
     {"SPLPAK_PCG_TOL1", 1},
-    {"SPLPAK_PCG_TRI_PAIRS", 0},
     {"SPLPAK_PCG_TOL2", 1},
     {"SPLPAK_PIN_BW", 0},
-    {"SPLPAK_PR_C0", 0},
-    {"SPLPAK_PR_DEAL4", 0},
-    {"SPLPAK_PR_NODEAL", 0},
     {"SPLPAK_RCCL_JOB", 0},
     {"SPLPAK_RCCL_LIB", 1},
     {"SPLPAK_RCCL_ONE_RANK_CALLS", 0},
     {"SPLPAK_RESIDUAL_CELLS", 0},
-    {"SPLPAK_RESIDUAL_STAGED", 0},
     {"SPLPAK_ROWS_ONE_STREAM", 0},
     {"SPLPAK_ROWS_TILES", 0},
     {"SPLPAK_SOLVER", 1},
-    {"SPLPAK_TOPA64", 0},
     {"SPLPAK_VIRTUAL_GPUS", 0},
 };
 std::mutex g_mu;
-std::map<std::string, std::string> g_defaults;      // set through the API; "" with g_unset = hidden
-std::map<std::string, bool> g_hidden;
+std::map<std::string, std::string> g_defaults;      // set through the API
 thread_local const Options *t_current = nullptr;
 thread_local Options t_fallback;
 thread_local unsigned long long t_fallback_gen = ~0ull;
@@ -113,13 +93,6 @@ bool option_canonical(const char *name, std::string &canon)
     return false;
 }
 
-int option_documented(const std::string &canon)
-{
-    for (const Known &k : KNOWN)
-        if (canon == k.name) return k.documented;
-    return 0;
-}
-
 Options options_snapshot()
 {
     Options o;
@@ -130,7 +103,6 @@ Options options_snapshot()
         o.kv[std::string(*e, (size_t)(eq - *e))] = std::string(eq + 1);
     }
     std::lock_guard<std::mutex> lk(g_mu);
-    for (const auto &h : g_hidden) o.kv.erase(h.first);
     for (const auto &d : g_defaults) o.kv[d.first] = d.second;
     return o;
 }
@@ -141,8 +113,8 @@ int options_set_default(const char *name, const char *value)
     if (!option_canonical(name, canon)) return -1;
     std::lock_guard<std::mutex> lk(g_mu);
     ++g_gen;
-    if (value) { g_defaults[canon] = value; g_hidden.erase(canon); }
-    else { g_defaults.erase(canon); g_hidden.erase(canon); }
+    if (value) g_defaults[canon] = value;
+    else g_defaults.erase(canon);
     return 0;
 }
 

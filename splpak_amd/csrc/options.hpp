@@ -21,8 +21,6 @@ struct Options {
 
 // canonical name of a switch given as "nd_kb", "ND_KB" or "SPLPAK_ND_KB"; false = unknown
 bool option_canonical(const char *name, std::string &canon);
-// what kind of switch it is: 1 = one of the documented options, 0 = an internal A/B switch of the tests
-int option_documented(const std::string &canon);
 // process defaults over the environment
 Options options_snapshot();
 int options_set_default(const char *name, const char *value);      // value NULL: back to the environment's

@@ -385,26 +385,6 @@ update_p_kernel(long long n, const double *__restrict__ sc, double *__restrict__
 
 __global__ void advance_kernel(double *__restrict__ sc) { sc[S_RZ] = sc[S_RZNEW]; }
 
-// out[0] = sum of w^2 over the sorted points [0, offset[ncell]) -- the zero-weight points sit behind them (fixed order)
-__global__ void __launch_bounds__(1024)
-fd_sumw2_kernel(const double *__restrict__ ws, const int *__restrict__ offset, int ncell, double *__restrict__ out)
-{
-    __shared__ double red[1024];
-    const int t = threadIdx.x;
-    const long long m = offset[ncell];
-    double s0 = 0.0, s1 = 0.0;
-    long long i = t;
-    for (; i + 1024 < m; i += 2048) { s0 = fma(ws[i], ws[i], s0); s1 = fma(ws[i + 1024], ws[i + 1024], s1); }
-    if (i < m) s0 = fma(ws[i], ws[i], s0);
-    red[t] = s0 + s1;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (t < o) red[t] += red[t + o];
-        __syncthreads();
-    }
-    if (t == 0) out[0] = red[0];
-}
-
 // out[0] = sum over the nodes of (data sparse ? dcw^2 : 0)  (fixed order)
 __global__ void __launch_bounds__(1024)
 fd_lambda_kernel(const double *__restrict__ dcw, const unsigned char *__restrict__ spf, int ncol, double *__restrict__ out)
@@ -913,7 +893,7 @@ int pcg_attach(splpak_plan *p, PcgState **out)
     ok = ok && pcg_alloc(s, &s->mband, (size_t)mbtot) && hip_ok(hipMemcpy(s->mband, hmband.data(), sizeof(double) * (size_t)mbtot, hipMemcpyHostToDevice), "pcg: upload");
     for (int k = 0; k < MAXD; ++k) s->mbands.m[k] = s->mband + (k < g.ndim ? mboffs[k] : 0);
     // (also for the plans that have a factorisation behind the iteration: their fits assemble nothing until it is needed, plan.hip "lazy")
-    if (ok && g.ndim == 4 && p->rowsop && p->ctab && (p->rows_only || p->solver_mode == 3)) {
+    if (ok && g.ndim == 4 && p->rowsop && (p->rows_only || p->solver_mode == 3)) {
         if (p->rows_only) ok = pcg_alloc(s, &s->ddiag, n);
         else if (!pcg_alloc(s, &s->ddiag, n)) { (void)hipGetLastError(); s->ddiag = nullptr; }
     }
@@ -955,12 +935,13 @@ int pcg_attach(splpak_plan *p, PcgState **out)
                 }
                 okb = hip_ok(block_chol_prepare(s->bj_jobs, s->bg.nb, s->bj_blocks, s->bj_inv16, s->bj_dinv, s->bj_dinvt, ncols.data()), "pcg: block jobs");
             }
-            if (okb && !splpak::opt_get("SPLPAK_PCG_BLOCKS_F64") && !splpak::opt_get("SPLPAK_PCG_BLOCKS_UNPACKED")) {
+            // the blocks of the apply: packed floats; where they do not fit, unpacked floats, else the doubles themselves
+            if (okb) {
                 double *f = nullptr;
                 if (pcg_alloc(s, &f, nb * 20480)) s->bj_pk32 = reinterpret_cast<float *>(f);         // nb * 40 960 floats
                 else (void)hipGetLastError();
             }
-            if (okb && !s->bj_pk32 && !splpak::opt_get("SPLPAK_PCG_BLOCKS_F64")) {
+            if (okb && !s->bj_pk32) {
                 double *f = nullptr;
                 if (pcg_alloc(s, &f, nb * 65536)) {            // two float arrays of nb * 65536 = one double array of that length
                     s->bj_dinv32 = reinterpret_cast<float *>(f);

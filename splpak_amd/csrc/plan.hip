@@ -222,7 +222,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     {   // per-cell shares of the residual passes of assemble.hip: 1-D .. 3-D grids; a 4-D grid's passes go tile by tile (rowsop.hip)
         // and leave this scratch out (1.45 GB at 32^4) unless the A/B switches ask for the cell-by-cell forms
         const char *rt = splpak::opt_get("SPLPAK_ROWS_TILES");
-        const bool tiled = g.ndim == 4 && !splpak::opt_get("SPLPAK_NO_CONSTRAINT_TABLE") && !(rt && atoi(rt) == 0) && !splpak::opt_get("SPLPAK_RESIDUAL_CELLS");
+        const bool tiled = g.ndim == 4 && !(rt && atoi(rt) == 0) && !splpak::opt_get("SPLPAK_RESIDUAL_CELLS");
         if (!tiled) ok = ok && dev_alloc(p, &p->rcell, (size_t)g.ncell * g.nb);
     }
     ok = ok && dev_alloc(p, &p->tbuf, (size_t)g.ncol * (g.ndim * (g.ndim + 1) / 2));
@@ -290,8 +290,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     // (0.30 of the 0.32 s of config 5's assembly).  pcg_assemble = 1 keeps the assembled form (A/B).
     {
         const char *rt = splpak::opt_get("SPLPAK_ROWS_TILES");
-        p->rows_only = !direct && g.ndim == 4 && !splpak::opt_get("SPLPAK_NO_CONSTRAINT_TABLE") && !(rt && atoi(rt) == 0) &&
-                       !splpak::opt_get("SPLPAK_PCG_ASSEMBLE");
+        p->rows_only = !direct && g.ndim == 4 && !(rt && atoi(rt) == 0) && !splpak::opt_get("SPLPAK_PCG_ASSEMBLE");
     }
     {
         // scratch of the per-cell Gram blocks: everything at once if <= 8 GB (or if the band storage, which is
@@ -353,18 +352,14 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     p->hist = p->scalG + SC_COUNT;
     p->scalH = p->hist + g.ncol;
     p->rho = p->scalH + SC_COUNT;
-    if (splpak::opt_get("SPLPAK_NO_CONSTRAINT_TABLE")) p->ctab = nullptr;      // (A/B switch; the allocation stays with the plan's list)
-    else if (!hip_ok(launch_constraint_table(g, p->ctab, nullptr), "constraint table") ||
-             !hip_ok(hipStreamSynchronize(nullptr), "constraint table")) {
+    if (!hip_ok(launch_constraint_table(g, p->ctab, nullptr), "constraint table") ||
+        !hip_ok(hipStreamSynchronize(nullptr), "constraint table")) {
         splpak_plan_destroy(p);
         return SPLPAK_E_NODEVICE;
     }
-    if (p->ctab) {
-        const int rc = rowsop_create(g, !direct, &p->rowsop);
-        if (rc != 0) {
-            splpak_plan_destroy(p);
-            return rc;
-        }
+    if (const int rc = rowsop_create(g, !direct, &p->rowsop)) {
+        splpak_plan_destroy(p);
+        return rc;
     }
     if (direct) twoend_attach(p);
     p->solver_mode = !direct ? 2 : (mode == 3 ? 3 : 0);
@@ -629,7 +624,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     // going to need them (round 6): the iteration applies the rows, its boxes are built from the rows (bj_build_kernel), and whether
     // it is tried at all is known from the histogram -- so the fit starts as an iteration-only plan's does (3 ms) and falls back to
     // the assembly (62 ms at 24^4: 40 % of such a fit) where the iteration is not tried or gives up.  One rank, no reduction hook.
-    const bool lazy = !p->rows_only && p->pcg && p->solver_mode == 3 && p->rowsop && p->ctab && smooth && p->world <= 1 && !p->ar &&
+    const bool lazy = !p->rows_only && p->pcg && p->solver_mode == 3 && p->rowsop && smooth && p->world <= 1 && !p->ar &&
                       pcg_boxes_from_rows(p->pcg) && !splpak::opt_get("SPLPAK_PCG_EAGER");
     {   // (lazy: the half stencil is cleared when -- if -- it is assembled)
         const long long skip = lazy ? (long long)(p->rhs - p->comm) : 0;
@@ -879,7 +874,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         SPLPAK_HIP_TRY(hipMemsetAsync(p->rho, 0, sizeof(double) * (size_t)(b.npad + SC_COUNT), st), SPLPAK_E_NODEVICE);
         hipEvent_t r0 = stamps ? p->evStage[8] : nullptr, r1 = stamps ? p->evStage[9] : nullptr;   // (created with the other stage events)
         if (r0 && r1) (void)hipEventRecord(r0, st);
-        if (p->rowsop && p->ctab && (!p->rcell || !splpak::opt_get("SPLPAK_RESIDUAL_CELLS")))      // (4-D: tile by tile, as the refinement's passes; 8.3 -> 1 ms at 32^4)
+        if (p->rowsop && (!p->rcell || !splpak::opt_get("SPLPAK_RESIDUAL_CELLS")))      // (4-D: tile by tile, as the refinement's passes; 8.3 -> 1 ms at 32^4)
             SPLPAK_HIP_TRY(rowsop_residual(g, p->rowsop, p->s, p->xvec, p->dcw, p->spf, p->ctab, smooth && p->rank == 0, p->rho, scalR, p->e2buf, st),
                            SPLPAK_E_NODEVICE);
         else

@@ -165,7 +165,7 @@ hipError_t rowsop_residual(const Grid &g, RowsOp *r, const SortScratch &rows, co
                            const double *ctab, bool constraints, double *rho, double *ssq, double *e2buf, hipStream_t st);
 inline hipError_t plan_rows_residual(splpak_plan *p, const SortScratch &rows, const double *xvec, bool constraints, double *rho, hipStream_t st)
 {
-    if (p->rowsop && p->ctab) return rowsop_apply(p->g, p->rowsop, rows, xvec, p->dcw, p->spf, p->ctab, constraints, rho, st);
+    if (p->rowsop) return rowsop_apply(p->g, p->rowsop, rows, xvec, p->dcw, p->spf, p->ctab, constraints, rho, st);
     return launch_residual(p->g, rows, xvec, p->rcell, p->dcw, p->spf, p->ctab, constraints, p->tbuf, rho, nullptr, nullptr, st);
 }
 // ndchol.hip: batched Cholesky + triangular inverses of independent dense 256 x 256 blocks

@@ -424,90 +424,6 @@ tri_pass_kernel(Grid g, int k, int ctbase, PassTable tabl, const double *__restr
     outpool[(long long)blockIdx.y * ncol + node] = acc;
 }
 
-// Two forward passes in one (dimensions k, k + 1): output j of the second pass straight from the input of the first --
-//   out_j[n] = w(n) sum_{ob} F_{k+1}(n, ob) sum_{oa} F_k(n, oa) in[n + oa e_k + ob e_{k+1}]
-// (nine cached reads per output instead of writing and re-reading the first pass's arrays: 8 launches per product -> 4)
-template <bool ABS>
-__global__ void __launch_bounds__(256)
-tri_fwd2_kernel(Grid g, int k, int ctb0, int ctb1, PassTable ta, PassTable tb, const double *__restrict__ ctab, const double *__restrict__ inpool,
-                double *__restrict__ outpool, const double *__restrict__ dcw, const unsigned char *__restrict__ spf)
-{
-    const int node = blockIdx.x * 256 + threadIdx.x;
-    if (node >= g.ncol) return;
-    const PassJob &jb = tb.job[blockIdx.y];
-    const PassJob &ja = ta.job[jb.src[0]];
-    const int na = g.nodes[k], sa = g.colstride[k], nb = g.nodes[k + 1], sb = g.colstride[k + 1];
-    const int ia = (node / sa) % na, ib = (node / sb) % nb;
-    const double *__restrict__ in = inpool + (long long)ja.src[0] * g.ncol;
-    double fa[3], acc = 0.0;
-#pragma unroll
-    for (int o = -1; o <= 1; ++o) {
-        const bool ok = ia + o >= 0 && ia + o <= na - 1;
-        double f = ok ? node_factor(g, ctab, ctb0, k, ia, o, ja.ord[0]) : 0.0;
-        fa[o + 1] = ABS ? fabs(f) : f;
-    }
-#pragma unroll
-    for (int ob = -1; ob <= 1; ++ob) {
-        if (ib + ob < 0 || ib + ob > nb - 1) continue;
-        double f = node_factor(g, ctab, ctb1, k + 1, ib, ob, jb.ord[0]);
-        if (ABS) f = fabs(f);
-        const double *__restrict__ row = in + node + ob * sb;
-        double u = 0.0;
-#pragma unroll
-        for (int oa = -1; oa <= 1; ++oa)
-            if (fa[oa + 1] != 0.0) u = fma(fa[oa + 1], row[oa * sa], u);
-        acc = fma(f, u, acc);
-    }
-    if (jb.wsel != 0) {
-        double wgt = 0.0;
-        if (spf[node]) {
-            const double dc = jb.wsel == 1 ? dcw[node] : 2.0 * dcw[node];      // :983
-            wgt = dc * dc;
-        }
-        acc *= wgt;
-    }
-    outpool[(long long)blockIdx.y * g.ncol + node] = acc;
-}
-
-// Two transposed passes in one (dimension k + 1, then k): output j of the pass over dimension k from the inputs of the pass over k + 1
-template <bool ABS>
-__global__ void __launch_bounds__(256)
-tri_bwd2_kernel(Grid g, int k, int ctb0, int ctb1, PassTable t0, PassTable t1, const double *__restrict__ ctab, const double *__restrict__ inpool,
-                double *__restrict__ outpool)
-{
-    const int node = blockIdx.x * 256 + threadIdx.x;
-    if (node >= g.ncol) return;
-    const PassJob &j0 = t0.job[blockIdx.y];
-    const int n0 = g.nodes[k], s0 = g.colstride[k], n1 = g.nodes[k + 1], s1 = g.colstride[k + 1];
-    const int i0 = (node / s0) % n0, i1 = (node / s1) % n1;
-    const long long ncol = g.ncol;
-    double acc = 0.0;
-    for (int a = 0; a < j0.nsrc; ++a) {
-        const PassJob &j1 = t1.job[j0.src[a]];
-#pragma unroll
-        for (int o0 = -1; o0 <= 1; ++o0) {
-            const int m0 = i0 + o0;
-            if (m0 < 0 || m0 > n0 - 1) continue;
-            double f0 = node_factor(g, ctab, ctb0, k, m0, -o0, j0.ord[a]);
-            if (ABS) f0 = fabs(f0);
-            double inter = 0.0;             // the pass over dimension k + 1 at the node m + o0 e_k (same coordinate along k + 1)
-            for (int c = 0; c < j1.nsrc; ++c) {
-                const double *__restrict__ in = inpool + (long long)j1.src[c] * ncol + node + o0 * s0;
-#pragma unroll
-                for (int o1 = -1; o1 <= 1; ++o1) {
-                    const int m1 = i1 + o1;
-                    if (m1 < 0 || m1 > n1 - 1) continue;
-                    double f1 = node_factor(g, ctab, ctb1, k + 1, m1, -o1, j1.ord[c]);
-                    if (ABS) f1 = fabs(f1);
-                    inter = fma(f1, in[o1 * s1], inter);
-                }
-            }
-            acc = fma(f0, inter, acc);
-        }
-    }
-    outpool[(long long)blockIdx.y * ncol + node] = acc;
-}
-
 }  // namespace
 
 // share[node] = sum over the node's constraint rows of (row weight x row . x)^2 from the last forward pass's arrays, which hold
@@ -541,7 +457,6 @@ struct RowsOp {
     PassTable fwd[MAXD], bwd[MAXD];
     int nfwd[MAXD] = {0, 0, 0, 0}, nbwd[MAXD] = {0, 0, 0, 0};
     size_t bytes = 0;
-    bool no_pairs = false;            // A/B: the passes of the constraint rows one dimension at a time
     // the constraint rows' passes run BESIDE the data rows' tile kernel, on a stream of their own: the tile kernel is bound by the
     // issue of vector / matrix instructions and leaves wave slots and the memory system to them (0.26 of an iteration's 1.29 ms at
     // 32^4 were these passes behind it).  NULL: one stream (SPLPAK_ROWS_ONE_STREAM, or the stream could not be had)
@@ -574,9 +489,6 @@ int rowsop_create(const Grid &g, bool side_stream, RowsOp **out)
     const char *sw = splpak::opt_get("SPLPAK_ROWS_TILES");           // A/B switch: 0 = the cell-by-cell passes
     if (g.ndim != 4 || (sw && atoi(sw) == 0)) return 0;
     RowsOp *r = new RowsOp();
-    // (the passes in pairs -- tri_fwd2 / tri_bwd2 -- were measured at 32^4: 144 + 157 us per product against 142 + 126 us one dimension at
-    //  a time: nine cached reads per output cost what the saved arrays gain.  Kept behind a switch.)
-    r->no_pairs = splpak::opt_get("SPLPAK_PCG_TRI_PAIRS") == nullptr;
     r->ntiles = 1;
     for (int d = 0; d < 4; ++d) {
         r->nt[d] = (g.cells[d] + TCS[d] - 1) / TCS[d];
@@ -680,28 +592,15 @@ static hipError_t rowsop_apply_t(const Grid &g, RowsOp *r, const SortScratch &ro
         const double *in = xvec;
         double *pools[2] = {r->poolA, r->poolB};
         int which = 0;
-        const bool pairs = D == 4 && !r->no_pairs;
-        if (pairs) {
-            for (int k = 0; k < D; k += 2) {
-                if (abs_factors) hipLaunchKernelGGL(tri_fwd2_kernel<true>, dim3(gx, (unsigned)r->nfwd[k + 1]), bl, 0, st, g, k, r->ctbase[k], r->ctbase[k + 1], r->fwd[k], r->fwd[k + 1], ctab, in, pools[which], dcw, spf);
-                else hipLaunchKernelGGL(tri_fwd2_kernel<false>, dim3(gx, (unsigned)r->nfwd[k + 1]), bl, 0, st, g, k, r->ctbase[k], r->ctbase[k + 1], r->fwd[k], r->fwd[k + 1], ctab, in, pools[which], dcw, spf);
-                in = pools[which];
-                which ^= 1;
-            }
-            for (int k = D - 2; k >= 0; k -= 2) {
-                if (abs_factors) hipLaunchKernelGGL(tri_bwd2_kernel<true>, dim3(gx, (unsigned)r->nbwd[k]), bl, 0, st, g, k, r->ctbase[k], r->ctbase[k + 1], r->bwd[k], r->bwd[k + 1], ctab, in, pools[which]);
-                else hipLaunchKernelGGL(tri_bwd2_kernel<false>, dim3(gx, (unsigned)r->nbwd[k]), bl, 0, st, g, k, r->ctbase[k], r->ctbase[k + 1], r->bwd[k], r->bwd[k + 1], ctab, in, pools[which]);
-                in = pools[which];
-                which ^= 1;
-            }
-        }
-        for (int k = 0; k < D && !pairs; ++k) {
+        // (one dimension per launch: two per launch measured 144 + 157 us per product at 32^4 against 142 + 126 us -- nine cached
+        //  reads per output cost what the saved arrays gain)
+        for (int k = 0; k < D; ++k) {
             if (abs_factors) hipLaunchKernelGGL((tri_pass_kernel<false, true>), dim3(gx, (unsigned)r->nfwd[k]), bl, 0, st, g, k, r->ctbase[k], r->fwd[k], ctab, in, pools[which], dcw, spf);
             else hipLaunchKernelGGL((tri_pass_kernel<false, false>), dim3(gx, (unsigned)r->nfwd[k]), bl, 0, st, g, k, r->ctbase[k], r->fwd[k], ctab, in, pools[which], dcw, spf);
             in = pools[which];
             which ^= 1;
         }
-        for (int k = D - 1; k >= 0 && !pairs; --k) {
+        for (int k = D - 1; k >= 0; --k) {
             if (k == D - 1 && e2nodes) {             // (between the forward and the transposed passes: `in` = the weighted row products)
                 WeightSel ws{};
                 for (int j = 0; j < r->nfwd[D - 1]; ++j) ws.w[j] = r->fwd[D - 1].job[j].wsel;
@@ -732,16 +631,12 @@ hipError_t rowsop_apply(const Grid &g, RowsOp *r, const SortScratch &rows, const
 
 // The same pass with the sum of the squared row residuals (data and constraint rows: the reference's `reserr`^2, suprls :1693) into
 // ssq[0]: e2buf [ncell + ncol] takes the shares -- tiles first, nodes from ncell on -- and one workgroup adds them in a fixed order.
-// (Tiled pairs of passes, the A/B form, leave no array of row products: they take the single passes here.)
 hipError_t rowsop_residual(const Grid &g, RowsOp *r, const SortScratch &rows, const double *xvec, const double *dcw, const unsigned char *spf,
                            const double *ctab, bool constraints, double *rho, double *ssq, double *e2buf, hipStream_t st)
 {
     hipError_t e = hipMemsetAsync(e2buf, 0, sizeof(double) * ((size_t)g.ncell + (size_t)g.ncol), st);
     if (e != hipSuccess) return e;
-    const bool keep = r->no_pairs;
-    r->no_pairs = true;
     e = rowsop_apply_t(g, r, rows, xvec, dcw, spf, ctab, constraints, false, rho, st, e2buf, constraints ? e2buf + g.ncell : nullptr);
-    r->no_pairs = keep;
     if (e != hipSuccess) return e;
     return launch_sum_fixed(e2buf, (long long)g.ncell + g.ncol, ssq, st);
 }

@@ -1,7 +1,8 @@
 """Options of the library (round 6, include/splpak_hip.h): named switches instead of environment variables read at every fit.
-CPU tier: the process defaults (no GPU needed).  GPU tier: a plan's snapshot, per-fit options, and the goldens over every
+CPU tier: the process defaults, and the option table against the sources (no GPU needed).  GPU tier: a plan's snapshot, per-fit options, and the goldens over every
 documented boolean option."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -9,6 +10,15 @@ import pytest
 from splpak_amd import capi
 from tests.cases import CASES, make_inputs
 from tests.conftest import load_golden, relmax
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "splpak_amd", "csrc")
+
+# internal switches that no test or tool sets, each with its reason (test_every_internal_switch_is_exercised)
+UNEXERCISED_SWITCHES = {
+    "SPLPAK_MPLAN_BAND": "dist.hip's no-peer-access error and include/splpak_hip.h name it as the user's way out",
+    "SPLPAK_DEBUG_NO_PEER": "rehearses that error on a multi-GPU node, where this suite never runs",
+}
 
 
 def test_default_options_know_their_names():
@@ -24,15 +34,52 @@ def test_default_options_know_their_names():
 def test_no_getenv_on_the_fit_path():
     """The library's sources read the environment in ONE place (csrc/options.hip: the snapshot a plan takes at creation and the
     fallback outside of any plan); everything else goes through the calling thread's current options."""
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "splpak_amd", "csrc")
     hits = []
-    for f in sorted(os.listdir(src)):
+    for f in sorted(os.listdir(CSRC)):
         if not f.endswith((".hip", ".hpp", ".inc")) or f.startswith("options."):
             continue
-        for i, line in enumerate(open(os.path.join(src, f)), 1):
+        for i, line in enumerate(open(os.path.join(CSRC, f)), 1):
             if "getenv(" in line and "opt_get" not in line:
                 hits.append(f"{f}:{i}")
     assert hits == [], hits
+
+
+def _option_table():
+    """KNOWN of csrc/options.hip: name -> documented (1: an option of INTEGRATION.md, 0: an internal switch)."""
+    src = open(os.path.join(CSRC, "options.hip")).read()
+    return {n: int(d) for n, d in re.findall(r'\{"(SPLPAK_[A-Z0-9_]+)", ([01])\}', src)}
+
+
+def test_option_table_matches_its_readers():
+    """Every row of the option table is read somewhere in the library, and every name the library reads is in the table."""
+    table = _option_table()
+    read = set()
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith((".hip", ".hpp", ".inc")) and not f.startswith("options."):
+            read |= set(re.findall(r'"(SPLPAK_[A-Z0-9_]+)"', open(os.path.join(CSRC, f)).read()))
+    assert sorted(set(table) - read) == [], "rows of the option table that nothing reads"
+    assert sorted(read - set(table)) == [], "names read that the option table lacks"
+
+
+def test_every_internal_switch_is_exercised():
+    """An internal switch selects a form that must give the same bits: a test or a tool has to set it, or it goes with the code
+    it guards.  The long name or the short lower-case one, as a whole word."""
+    texts = [open(os.path.join(ROOT, "bench.py")).read()]
+    pkg = os.path.join(ROOT, "splpak_amd")
+    texts += [open(os.path.join(pkg, f)).read() for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    for d in ("tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, d)):
+            texts += [open(os.path.join(dirpath, f), errors="replace").read() for f in sorted(files)
+                      if f.endswith((".py", ".sh", ".hip", ".hpp", ".md", ".txt"))]
+    corpus = "\n".join(texts)
+    table = _option_table()
+    unused = []
+    for name, documented in sorted(table.items()):
+        short = name[len("SPLPAK_"):].lower()
+        if not documented and name not in UNEXERCISED_SWITCHES and not re.search(rf"\b({name}|{short})\b", corpus):
+            unused.append(name)
+    assert unused == [], "internal switches that no test or tool sets"
+    assert all(table.get(n) == 0 for n in UNEXERCISED_SWITCHES), "stale entries of UNEXERCISED_SWITCHES"
 
 
 @pytest.mark.gpu

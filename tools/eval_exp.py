@@ -24,4 +24,4 @@ for _ in range(40):
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 40
-print(f"exp={os.environ.get('SPLPAK_PR_EXP', '0')}: {ms:.3f} ms per {nq} queries = {nq / ms / 1e6:.2f} Gevals/s", flush=True)
+print(f"{ms:.3f} ms per {nq} queries = {nq / ms / 1e6:.2f} Gevals/s", flush=True)
