@@ -62,6 +62,9 @@ extern "C" {
  *       recomputed from the rows, as the componentwise backward error
  *       max_i |rho_i| / ((|N| |x|)_i + |A^T W^2 y|_i), N = A^T W^2 A + C^T C; 0 at the minimiser the reference
  *       computes, ~1e-14 when the fit is converged, ~cond(N) eps for plain normal equations.
+ *       Fits that never assemble N (iteration-only 4-D plans, and 4-D fits the iteration answers before the assembly) normalise
+ *       by (|A|^T W^2 |A| |x| + |C|^T |C| |x|)_i + |A^T W^2 y|_i from the rows instead: entry by entry at least |N| |x|, so their
+ *       info[9] is the smaller (more lenient) of the two measures for the same coefficients.
  * The band-Cholesky solution is refined against the rows until the estimated remaining error
  * |dx|/|x| is below 1e-11 (2 steps at 64^3: corrections 9e-5, 1e-8, then an estimated 2e-12); a solve that is still contracting after the nominal
  * number of steps continues (up to 30), and one that then still misses 1e-10, or whose corrections
@@ -359,6 +362,36 @@ int32_t splpak_debug_plan_normal_equations(const splpak_plan *plan, double *nst_
  * Returns 0; 107 if N is not positive definite (x = 0; the plan stays usable); SPLPAK_E_BADARG for a null argument;
  * SPLPAK_E_UNSUPPORTED for a plan without a factorisation (iteration only) or a rank of a sharded / distributed fit. */
 int32_t splpak_debug_plan_solve(splpak_plan *plan, const double *nst_ref, const double *b, double *x, double *minpiv);
+
+/* Diagnostics: the passes over the ROWS of the plan's last successful single-rank fit (its binned points, constraint weights and
+ * data-sparse flags are still in the plan), evaluated at the caller's coefficients.  coef, rho, den: [ncol] on the host, in the
+ * caller's column order.  rho = A^T W (W y - W A coef) - C^T C coef, computed by
+ *   which = 0: the pass the refinement calls (and the iteration, as its operator), with y;
+ *   which = 1: the diagnostics pass a fit ends with for info[8] / info[9] (tile form or cell by cell, honouring
+ *              SPLPAK_RESIDUAL_CELLS); only this one also returns *ssq, the sum of squared row residuals (info[8]^2), and in den
+ *              the backward error's denominators the fit would use (from the half stencil, or from the rows where the fit did
+ *              not assemble the normal equations);
+ *   which = 2: the operator form of the iteration, y = 0.
+ * den and ssq may be NULL; for which = 0 and 2 they are set to 0.  The entry calls the functions the fit calls.  It overwrites only
+ * scratch every fit rewrites.  Returns 0; SPLPAK_E_BADARG for a null plan, coef or rho or another `which`; SPLPAK_E_UNSUPPORTED when
+ * there is no completed fit (none yet, a failed one, or a splpak_debug_plan_solve since) or the plan is a rank of a sharded /
+ * multi-GPU fit. */
+int32_t splpak_debug_plan_rows_gradient(splpak_plan *plan, const double *coef, int32_t which, double *rho, double *den, double *ssq);
+
+/* Diagnostics: z = M^-1 r with the iteration's preconditioner as the plan's last fit prepared it; r, z: [ncol] on the host, in the
+ * caller's column order.  part = 0: the whole of it, as the iteration applies it; 1: the separable part alone; 2: the block-Jacobi
+ * boxes alone (zero when the fit dropped them or the plan has none).  Returns 0; SPLPAK_E_BADARG for a null argument or another
+ * `part`; SPLPAK_E_UNSUPPORTED for a plan without the iteration or a last fit that never prepared it. */
+int32_t splpak_debug_plan_precondition(splpak_plan *plan, int32_t part, const double *r, double *z);
+
+/* Diagnostics: host copies of what the separable part multiplies by.  _pcg_tables: for dimension `dim` of the CALLER's dimension
+ * order, *n_out = its node count n, V: [n][n] row-major (component i of eigenvector j at V[i * n + j]) and VT, the transposed copy
+ * the kernels read in the other direction; V and VT may be NULL (a sizing call).  _pcg_diagonal: dinv [ncol], caller's column
+ * order, the reciprocal diagonal in the eigenbasis as the last fit prepared it:
+ *     separable part:  z = (kron_k V_k) (dinv * ((kron_k V_k^T) r)).
+ * Return 0, SPLPAK_E_BADARG (null argument, dim outside the grid), SPLPAK_E_UNSUPPORTED (no iteration / never prepared). */
+int32_t splpak_debug_plan_pcg_tables(const splpak_plan *plan, int32_t dim, double *V, double *VT, int32_t *n_out);
+int32_t splpak_debug_plan_pcg_diagonal(const splpak_plan *plan, double *dinv);
 
 /* Diagnostics (host only): the fronts of the nested-dissection elimination tree of a grid (as splpak_debug_nd_tree builds it),
  * in elimination order (postorder, the root last).  *nfronts: their number F.  With max_fronts < F nothing else is written (a

@@ -148,6 +148,10 @@ class Port(_Base):
                                            C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long)]
         L.oracle_rows_gradient_vec.restype = C.c_int
         L.oracle_rows_gradient_vec.argtypes = L.oracle_rows_gradient.argtypes + [_dp]
+        L.oracle_rows_gradient_den.restype = C.c_int
+        L.oracle_rows_gradient_den.argtypes = L.oracle_rows_gradient_vec.argtypes + [_dp]
+        L.oracle_set_exact_histogram_total.restype = None
+        L.oracle_set_exact_histogram_total.argtypes = [C.c_int]
         L.oracle_normal_equations.restype = C.c_int
         L.oracle_normal_equations.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _ip, C.c_double, C.c_int,
                                               _dp, _dp, _dp, _dp, C.POINTER(C.c_long)]
@@ -232,6 +236,34 @@ class Port(_Base):
         if rc != 0:
             raise MemoryError("oracle_rows_gradient_vec")
         return rho
+
+    def rows_gradient_den(self, ndim, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, coef, nthreads=0, exact_total=False):
+        """As rows_gradient_vec, with the vector omega is measured against beside it -> (rho, den, ssq, data rows, constraint
+        rows); den_i = (|A|^T (|A||x| + |b|))_i over data and constraint rows, the size of the terms that cancel in rho_i.
+        exact_total: the histogram's total, which the reference adds up point by point in double, in long double instead."""
+        xdata = np.ascontiguousarray(xdata, dtype=np.float64)
+        if xdata.ndim == 1:
+            xdata = xdata.reshape(-1, 1)
+        ydata = np.ascontiguousarray(ydata, dtype=np.float64)
+        w = np.ascontiguousarray(wdata, dtype=np.float64) if wdata is not None else np.array([-1.0])
+        xmin = np.ascontiguousarray(np.atleast_1d(xmin), dtype=np.float64)
+        xmax = np.ascontiguousarray(np.atleast_1d(xmax), dtype=np.float64)
+        nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        ncol = int(np.prod(nodes.astype(np.int64)))
+        rho, den = np.zeros(ncol), np.zeros(ncol)
+        om, s2 = C.c_double(0.0), C.c_double(0.0)
+        nr = (C.c_long * 2)()
+        self.lib.oracle_set_exact_histogram_total(1 if exact_total else 0)
+        try:
+            rc = self.lib.oracle_rows_gradient_den(ndim, _ptr(xdata, _dp), xdata.shape[1], _ptr(ydata, _dp), _ptr(w, _dp), xdata.shape[0],
+                                                  _ptr(xmin, _dp), _ptr(xmax, _dp), _ptr(nodes, _ip), float(xtrap), _ptr(coef, _dp),
+                                                  int(nthreads), C.byref(om), C.byref(s2), nr, _ptr(rho, _dp), _ptr(den, _dp))
+        finally:
+            self.lib.oracle_set_exact_histogram_total(0)
+        if rc != 0:
+            raise MemoryError("oracle_rows_gradient_den")
+        return rho, den, s2.value, int(nr[0]), int(nr[1])
 
     def normal_equations(self, ndim, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, nthreads=0, ndata=None, l1xdat=None):
         """The normal equations of the reference's rows, accumulated in long double (oracle_normal_equations) ->

@@ -76,6 +76,12 @@ static int build_rows(int ndim, const double *xdata, int l1xdat, const double *y
     return emit_rows(ndim, xdata, l1xdat, ydata, wdata, ndata, 0, ndata, 1, xmin, xmax, nodes, xtrap, sink_push, R, ncons);
 }
 
+/* The reference adds the histogram's total up point by point in working precision (:886-907), and so does emit_rows.  That sum
+ * carries an error of its own (1.9e-14 relative over 2e5 weights), which every constraint weight xtrap (expect - have) inherits.
+ * A comparison that is to see errors of 1e-13 in what is compared WITH the oracle switches the total to long double here. */
+static int g_exact_total = 0;
+void oracle_set_exact_histogram_total(int on) { g_exact_total = on; }
+
 static int emit_rows(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata,
                      int ndata, int i0, int i1, int with_constraints, const double *xmin, const double *xmax,
                      const int *nodes, double xtrap, row_sink sink, void *R, long *ncons)
@@ -128,6 +134,7 @@ static int emit_rows(int ndim, const double *xdata, int l1xdat, const double *yd
         double *hist = calloc((size_t)ncol, sizeof(double));
         if (!hist) return 1;
         double totlwt = 0.0;
+        long double totlwt_ld = 0.0L;
         for (int idata = 0; idata < ndata; ++idata) {
             double bump = weighted ? wdata[idata] : 1.0;
             if (bump == 0.0) continue;
@@ -140,7 +147,9 @@ static int emit_rows(int ndim, const double *xdata, int l1xdat, const double *yd
             }
             hist[iin] += bump;
             totlwt += bump;
+            totlwt_ld += bump;
         }
+        if (g_exact_total) totlwt = (double)totlwt_ld;
         const double wtprrc = totlwt / (double)nrect;
         long iin = 0;
         for (;;) {
@@ -421,10 +430,18 @@ static int sink_grad(void *ctx, int nz, const int *col, const double *val, doubl
     return 0;
 }
 
-/* oracle_rows_gradient_vec: the same, and rho itself (in the reference's column order) into rho_out when it is not NULL */
+/* oracle_rows_gradient_vec: the same, and rho itself (in the reference's column order) into rho_out when it is not NULL;
+ * oracle_rows_gradient_den: and denom beside it, into den_out */
+int oracle_rows_gradient_den(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
+                             const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
+                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out, double *den_out);
 int oracle_rows_gradient_vec(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
                              const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
-                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out);
+                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out)
+{
+    return oracle_rows_gradient_den(ndim, xdata, l1xdat, ydata, wdata, ndata, xmin, xmax, nodes, xtrap, coef, nthreads,
+                                    omega_out, ssq_out, nrows_out, rho_out, NULL);
+}
 int oracle_rows_gradient(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
                          const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
                          int nthreads, double *omega_out, double *ssq_out, long *nrows_out)
@@ -433,9 +450,9 @@ int oracle_rows_gradient(int ndim, const double *xdata, int l1xdat, const double
                                     omega_out, ssq_out, nrows_out, NULL);
 }
 
-int oracle_rows_gradient_vec(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
+int oracle_rows_gradient_den(int ndim, const double *xdata, int l1xdat, const double *ydata, const double *wdata, int ndata,
                              const double *xmin, const double *xmax, const int *nodes, double xtrap, const double *coef,
-                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out)
+                             int nthreads, double *omega_out, double *ssq_out, long *nrows_out, double *rho_out, double *den_out)
 {
     long ncol = 1;
     for (int d = 0; d < ndim; ++d) ncol *= nodes[d];
@@ -469,6 +486,7 @@ int oracle_rows_gradient_vec(int ndim, const double *xdata, int l1xdat, const do
         for (int t = 0; t < nthreads; ++t) { r += rho[(size_t)ncol * t + i]; d += den[(size_t)ncol * t + i]; }
         if (d > 0.0 && fabs(r) / d > omega) omega = fabs(r) / d;
         if (rho_out) rho_out[i] = r;
+        if (den_out) den_out[i] = d;
     }
     free(rho); free(den); free(ssq); free(nr);
     if (omega_out) *omega_out = omega;

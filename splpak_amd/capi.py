@@ -34,6 +34,7 @@ SYMBOLS = [
     "splpak_mplan_create", "splpak_mplan_destroy", "splpak_mplan_device", "splpak_mplan_rank_bytes", "splpak_mplan_factorisation", "splpak_mplan_fit_dev", "splpak_fit_multi_f64",
     "splpak_plan_device_bytes", "splpak_plan_pcg_stats", "splpak_set_default_option", "splpak_plan_set_option", "splpak_plan_get_option",
     "splpak_debug_spd_band_solve_f64", "splpak_debug_plan_normal_equations", "splpak_debug_plan_solve", "splpak_debug_nd_fronts",
+    "splpak_debug_plan_rows_gradient", "splpak_debug_plan_precondition", "splpak_debug_plan_pcg_tables", "splpak_debug_plan_pcg_diagonal",
     "splpak_debug_nd_tree", "splpak_debug_nd_partition", "splpak_debug_nd_schedule", "splpak_debug_window_values", "splpak_shutdown", "splpak_set_eval_mode",
     "splpak_last_error_message", "splpak_device_name",
 ]
@@ -132,6 +133,14 @@ def lib() -> C.CDLL:
     L.splpak_debug_plan_normal_equations.argtypes = [vp, _dp, _dp]
     L.splpak_debug_plan_solve.restype = i32
     L.splpak_debug_plan_solve.argtypes = [vp, _dp, _dp, _dp, _dp]
+    L.splpak_debug_plan_rows_gradient.restype = i32
+    L.splpak_debug_plan_rows_gradient.argtypes = [vp, _dp, i32, _dp, _dp, _dp]
+    L.splpak_debug_plan_precondition.restype = i32
+    L.splpak_debug_plan_precondition.argtypes = [vp, i32, _dp, _dp]
+    L.splpak_debug_plan_pcg_tables.restype = i32
+    L.splpak_debug_plan_pcg_tables.argtypes = [vp, i32, _dp, _dp, _ip]
+    L.splpak_debug_plan_pcg_diagonal.restype = i32
+    L.splpak_debug_plan_pcg_diagonal.argtypes = [vp, _dp]
     L.splpak_debug_nd_fronts.restype = i32
     L.splpak_debug_nd_fronts.argtypes = [i32, _ip, i32, _ip, i32, _ip, _ip, _ip, _ip, _ip, _ip]
     L.splpak_debug_nd_tree.restype = i32
@@ -544,6 +553,39 @@ class Plan:
         mp = C.c_double(0.0)
         rc = _check(self._L.splpak_debug_plan_solve(self._h, _p(N, _dp), _p(b, _dp), _p(x, _dp), C.byref(mp)))
         return x, rc, mp.value
+
+    def rows_gradient(self, coef, which=0):
+        """The rows pass of the last fit at `coef` (diagnostics, splpak_debug_plan_rows_gradient) -> (rho, den, ssq); which: 0 the
+        refinement's pass, 1 the fit's closing diagnostics pass (the only one that fills den and ssq), 2 the operator form y = 0."""
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        assert coef.shape == (self.ncol,)
+        rho, den = np.zeros(self.ncol), np.zeros(self.ncol)
+        ssq = C.c_double(0.0)
+        _check(self._L.splpak_debug_plan_rows_gradient(self._h, _p(coef, _dp), int(which), _p(rho, _dp), _p(den, _dp), C.byref(ssq)))
+        return rho, den, ssq.value
+
+    def precondition(self, r, part=0):
+        """z = M^-1 r with the preconditioner of the last fit (diagnostics); part: 0 whole, 1 separable part, 2 boxes."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        assert r.shape == (self.ncol,)
+        z = np.zeros(self.ncol)
+        _check(self._L.splpak_debug_plan_precondition(self._h, int(part), _p(r, _dp), _p(z, _dp)))
+        return z
+
+    def pcg_tables(self):
+        """-> ([V_k], [VT_k], dinv): per dimension of the caller's order the (n_k, n_k) matrices of the separable part, and the
+        reciprocal diagonal in the eigenbasis (ncol, caller's column order) as the last fit prepared it."""
+        Vs, VTs = [], []
+        for d in range(self.ndim):
+            n = C.c_int32(0)
+            _check(self._L.splpak_debug_plan_pcg_tables(self._h, d, None, None, C.byref(n)))
+            V, VT = np.zeros((n.value, n.value)), np.zeros((n.value, n.value))
+            _check(self._L.splpak_debug_plan_pcg_tables(self._h, d, _p(V, _dp), _p(VT, _dp), C.byref(n)))
+            Vs.append(V)
+            VTs.append(VT)
+        dinv = np.zeros(self.ncol)
+        _check(self._L.splpak_debug_plan_pcg_diagonal(self._h, _p(dinv, _dp)))
+        return Vs, VTs, dinv
 
 
 def evaluate_dev(ndim, xq, nderiv, coef, xmin, xmax, nodes, out, stream=0):

@@ -1040,7 +1040,8 @@ hipError_t pcg_prepare(splpak_plan *p, PcgState *s, double sumw2, bool smooth, b
 
 // z = M^-1 r.  (The boxes' term on a stream of its own beside the separable part's mode products was tried -- the way the constraint passes
 // run beside the rows' tile kernel, rowsop.hip -- and bought nothing: 0.281 s per fit at 32^4 either way; both parts live on the memory system.)
-static hipError_t pcg_precondition(PcgState *s, const double *r, double *z, hipStream_t st)
+// part (diagnostics, pcg_debug_precondition): 0 both terms -- what the iteration applies; 1 the separable term alone; 2 the boxes' alone
+static hipError_t pcg_precondition(PcgState *s, const double *r, double *z, hipStream_t st, int part = 0)
 {
     const Grid &g = s->g;
     const long long total = g.ncol;
@@ -1083,8 +1084,14 @@ static hipError_t pcg_precondition(PcgState *s, const double *r, double *z, hipS
             k = kend + 1;
         }
     };
-    sweep(s->V, s->dinv, nullptr);           // V_k^T along every dimension, the last one scaled by 1 / diag
-    sweep(s->VT, nullptr, z);                // V_k along every dimension
+    if (part == 2) {
+        const hipError_t e = hipMemsetAsync(z, 0, sizeof(double) * (size_t)total, st);
+        if (e != hipSuccess) return e;
+    } else {
+        sweep(s->V, s->dinv, nullptr);           // V_k^T along every dimension, the last one scaled by 1 / diag
+        sweep(s->VT, nullptr, z);                // V_k along every dimension
+    }
+    if (part == 1) return hipGetLastError();
     if (s->bj_ready && s->bj_pk32)
         hipLaunchKernelGGL(bj_apply_packed_kernel, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const float *)s->bj_pk32, r, z);
     else if (s->bj_ready && s->bj_dinv32)
@@ -1172,6 +1179,32 @@ int pcg_solve(splpak_plan *p, PcgState *s, double *v, double tol, bool smooth, h
     SPLPAK_HIP_TRY(hipMemcpyAsync(v, s->x, nb, hipMemcpyDeviceToDevice, st), SPLPAK_E_NODEVICE);
     if (status != 0) s->failed = true;
     return status;
+}
+
+// ---- diagnostics: the preconditioner applied to a caller's vector, and its tables (host copies; internal column order) ----
+int pcg_debug_precondition(PcgState *s, int part, const double *r_host, double *z_host)
+{
+    const size_t nb = sizeof(double) * (size_t)s->g.ncol;
+    hipStream_t st = nullptr;
+    SPLPAK_HIP_TRY(hipMemcpy(s->r, r_host, nb, hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(pcg_precondition(s, s->r, s->z, st, part), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemcpy(z_host, s->z, nb, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    return 0;
+}
+
+int pcg_debug_tables(const PcgState *s, int k, double *V_host, double *VT_host)
+{
+    const size_t nb = sizeof(double) * (size_t)s->g.nodes[k] * (size_t)s->g.nodes[k];
+    if (V_host) SPLPAK_HIP_TRY(hipMemcpy(V_host, s->V[k], nb, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    if (VT_host) SPLPAK_HIP_TRY(hipMemcpy(VT_host, s->VT[k], nb, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    return 0;
+}
+
+int pcg_debug_diagonal(const PcgState *s, double *dinv_host)
+{
+    SPLPAK_HIP_TRY(hipMemcpy(dinv_host, s->dinv, sizeof(double) * (size_t)s->g.ncol, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    return 0;
 }
 
 }  // namespace splpak

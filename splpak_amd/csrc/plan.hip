@@ -192,6 +192,20 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
         set_error("max_ndata per plan (= per GPU) is limited to 2^31 - 1025 points; shard the points over more plans");
         return SPLPAK_E_UNSUPPORTED;
     }
+    // How the least-squares problem is solved: SPLPAK_SOLVER = direct | pcg | pcg+direct names it; auto, an empty value or no value
+    // leave the choice to the plan (below).  Anything else is a mistake the caller hears about, not a silent "auto".
+    int mode = 0;
+    bool named = false;
+    if (const char *e = splpak::opt_get("SPLPAK_SOLVER")) {
+        if (!std::strcmp(e, "direct")) mode = 1;
+        else if (!std::strcmp(e, "pcg")) mode = 2;
+        else if (!std::strcmp(e, "pcg+direct")) mode = 3;
+        else if (*e && std::strcmp(e, "auto")) {
+            set_error(std::string("SPLPAK_SOLVER=") + e + ": the accepted values are direct, pcg, pcg+direct and auto (the same as unset or empty)");
+            return SPLPAK_E_BADARG;
+        }
+        named = mode != 0;
+    }
     if (int r = device_ready()) return r;
 
     splpak_plan *p = new splpak_plan();
@@ -245,19 +259,13 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     // How the least-squares problem is solved (round 6): a factorisation (band / nested dissection) whenever one fits the device;
     // the iteration of pcg.hip for the grids none fits (4-D from about 29^4 on one GPU) or by request -- SPLPAK_SOLVER =
     // direct | pcg | pcg+direct (the iteration first, the factorisation when it stagnates) | auto.
-    int mode = 0;
-    if (const char *e = splpak::opt_get("SPLPAK_SOLVER")) {
-        if (!std::strcmp(e, "direct")) mode = 1;
-        else if (!std::strcmp(e, "pcg")) mode = 2;
-        else if (!std::strcmp(e, "pcg+direct")) mode = 3;
-    }
     if (p->dm.R > 1) mode = 1;                      // (the one-process multi-GPU plans distribute a factorisation)
     // Left to itself a LARGE 4-D grid (from 20^4 columns on: the factorisation takes seconds) tries the iteration first: where the
     // constraint rows are dense (>= 2 per column: config 5's density of points) or absent it answers in a fraction of the
     // factorisation's time (24^4: 0.5 s against 4.6 s, 28^4: ~1.4 s against 18 s); where it stagnates (1.2 .. 1.7 rows per column)
     // the attempt costs 0.6 .. 1.4 s before the factorisation takes over (tools/pcg/density_sweep.py).
     if (mode == 0 && g.ndim == 4 && g.ncol >= 160000) mode = 3;
-    const bool auto_mode = mode == 0 || (mode == 3 && !splpak::opt_get("SPLPAK_SOLVER"));
+    const bool auto_mode = !named && p->dm.R == 1;      // the plan chose: what does not fit or is not supported is replaced, not reported
     bool direct = mode != 2;
     const bool use_nd = direct && allow_nd && (p->dm.R == 1 || ndgrp != nullptr) && nd_wanted(g, p->band);
     if (use_nd && ok) {
@@ -365,7 +373,16 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     p->solver_mode = !direct ? 2 : (mode == 3 ? 3 : 0);
     if (!direct || mode == 3) {
         const int rc = pcg_attach(p, &p->pcg);
-        if (rc != 0) {
+        if (rc != 0 && direct && auto_mode) {
+            // the iteration in front of a factorisation the plan chose by itself (more than 512 nodes in a dimension, or no memory
+            // for its tables): the factorisation alone -- fatal only where the iteration was asked for by name or is all there is
+            if (splpak::opt_get("SPLPAK_DEBUG"))
+                fprintf(stderr, "[splpak] the iteration could not be set up (status %d: %s): the factorisation alone\n", rc, g_err.c_str());
+            p->pcg = nullptr;
+            p->solver_mode = 0;
+            (void)hipGetLastError();
+            set_error("");
+        } else if (rc != 0) {
             splpak_plan_destroy(p);
             return rc;
         }
@@ -578,6 +595,38 @@ static int plan_factor_solve(splpak_plan *p, double *v, hipStream_t st)
     return 0;
 }
 
+// The pass over the rows a fit ends with, at the coefficients in p->xvec (internal order), as the fit runs it and as
+// splpak_debug_plan_rows_gradient runs it alone: the backward error's denominators into p->tmp, then rho into p->rho and the sum of
+// squared row residuals behind it (p->rho + npad).  rows_fit: the normal equations of this fit are not assembled.  e0: recorded
+// before the residual pass (NULL: none).
+static int plan_diagnostics_pass(splpak_plan *p, bool rows_fit, hipStream_t st, hipEvent_t e0)
+{
+    const Grid &g = p->g;
+    const Band &b = p->band;
+    const bool smooth = p->xtrap != 0.0;
+    double *scalR = p->rho + b.npad;
+    // the backward error's denominators (|N| |x| + |rhs|: a pass over the half stencil) need the coefficients only; into the
+    // solves' scratch vector.  (On a stream of their own beside the residual pass they gained nothing -- the two kernels
+    // slowed each other down by what the overlap saved -- and one more stream per plan is not free: round 5)
+    if (rows_fit) {
+        // from the rows: |A|^T W^2 |A| |x| + |C|^T |C| |x| + |rhs| (this rank's points; the residual's all-reduce below does not
+        // carry it -- a sharded rows-only fit normalises by its own shard's terms + the constraint rows on rank 0, a lower bound
+        // of the sum, i.e. a pessimistic backward error)
+        SPLPAK_HIP_TRY(rowsop_backward_denominators(g, p->rowsop, p->s, p->xvec, p->rhs, p->dcw, p->spf, p->ctab, smooth && p->rank == 0,
+                                                    pcg_scratch(p->pcg, 0), pcg_scratch(p->pcg, 1), p->tmp, st), SPLPAK_E_NODEVICE);
+    } else
+        SPLPAK_HIP_TRY(launch_backward_denominators(g, p->nst, p->xvec, p->rhs, p->tmp, st), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemsetAsync(p->rho, 0, sizeof(double) * (size_t)(b.npad + SC_COUNT), st), SPLPAK_E_NODEVICE);
+    if (e0) (void)hipEventRecord(e0, st);
+    if (p->rowsop && (!p->rcell || !splpak::opt_get("SPLPAK_RESIDUAL_CELLS")))      // (4-D: tile by tile, as the refinement's passes; 8.3 -> 1 ms at 32^4)
+        SPLPAK_HIP_TRY(rowsop_residual(g, p->rowsop, p->s, p->xvec, p->dcw, p->spf, p->ctab, smooth && p->rank == 0, p->rho, scalR, p->e2buf, st),
+                       SPLPAK_E_NODEVICE);
+    else
+        SPLPAK_HIP_TRY(launch_residual(g, p->s, p->xvec, p->rcell, p->dcw, p->spf, p->ctab, smooth && p->rank == 0,
+                                       p->tbuf, p->rho, scalR, p->e2buf, st), SPLPAK_E_NODEVICE);
+    return 0;
+}
+
 extern "C" {
 
 int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, const double *y,
@@ -599,6 +648,8 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     if (lerr != 0) ndata = 0;
     p->comm_failed = false;
     p->ne_valid = false;
+    p->fit_valid = false;
+    p->pcg_prepared = false;
     hipStream_t st = (hipStream_t)stream;
     if (lerr == 0 && w && ndata > 0) {
         // a negative first weight means "no weights" (:796, :890), as in the host entry points: one value read back
@@ -785,6 +836,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         if (int r = assemble_now()) return r;
     if (try_iteration) {
         SPLPAK_HIP_TRY(pcg_prepare(p, p->pcg, hs[SC_COUNT + SC_SUMW2], smooth, rows_fit, st), SPLPAK_E_NODEVICE);
+        p->pcg_prepared = true;
         if (pcg_singular(p->pcg)) {
             // A box taken out of the ASSEMBLED normal equations -- a principal submatrix of N -- is not positive definite by the pivot
             // test of the factorisations: neither is N (a column without data and, with xtrap = 0, without a constraint row; the
@@ -860,26 +912,8 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     double ssq = 0.0, omega = 0.0;
     if (info || stagnated) {
         double *scalR = p->rho + b.npad;
-        // the backward error's denominators (|N| |x| + |rhs|: a pass over the half stencil) need the coefficients only; into the
-        // solves' scratch vector.  (On a stream of their own beside the residual pass they gained nothing -- the two kernels
-        // slowed each other down by what the overlap saved -- and one more stream per plan is not free: round 5)
-        if (rows_fit) {
-            // from the rows: |A|^T W^2 |A| |x| + |C|^T |C| |x| + |rhs| (this rank's points; the residual's all-reduce below does not
-            // carry it -- a sharded rows-only fit normalises by its own shard's terms + the constraint rows on rank 0, a lower bound
-            // of the sum, i.e. a pessimistic backward error)
-            SPLPAK_HIP_TRY(rowsop_backward_denominators(g, p->rowsop, p->s, p->xvec, p->rhs, p->dcw, p->spf, p->ctab, smooth && p->rank == 0,
-                                                        pcg_scratch(p->pcg, 0), pcg_scratch(p->pcg, 1), p->tmp, st), SPLPAK_E_NODEVICE);
-        } else
-            SPLPAK_HIP_TRY(launch_backward_denominators(g, p->nst, p->xvec, p->rhs, p->tmp, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(hipMemsetAsync(p->rho, 0, sizeof(double) * (size_t)(b.npad + SC_COUNT), st), SPLPAK_E_NODEVICE);
         hipEvent_t r0 = stamps ? p->evStage[8] : nullptr, r1 = stamps ? p->evStage[9] : nullptr;   // (created with the other stage events)
-        if (r0 && r1) (void)hipEventRecord(r0, st);
-        if (p->rowsop && (!p->rcell || !splpak::opt_get("SPLPAK_RESIDUAL_CELLS")))      // (4-D: tile by tile, as the refinement's passes; 8.3 -> 1 ms at 32^4)
-            SPLPAK_HIP_TRY(rowsop_residual(g, p->rowsop, p->s, p->xvec, p->dcw, p->spf, p->ctab, smooth && p->rank == 0, p->rho, scalR, p->e2buf, st),
-                           SPLPAK_E_NODEVICE);
-        else
-            SPLPAK_HIP_TRY(launch_residual(g, p->s, p->xvec, p->rcell, p->dcw, p->spf, p->ctab, smooth && p->rank == 0,
-                                           p->tbuf, p->rho, scalR, p->e2buf, st), SPLPAK_E_NODEVICE);
+        if (int r = plan_diagnostics_pass(p, rows_fit, st, r0 && r1 ? r0 : nullptr)) return r;
         if (r0 && r1) {
             (void)hipEventRecord(r1, st);
             (void)hipEventSynchronize(r1);
@@ -929,6 +963,8 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         set_error(buf);
         return 107;
     }
+    p->fit_valid = p->world <= 1 && !p->ar && p->dm.R == 1;
+    p->fit_rows = rows_fit;
     return 0;
 #undef SPLPAK_HOOK_TRY
 }
@@ -1454,6 +1490,7 @@ int32_t splpak_debug_plan_solve(splpak_plan *p, const double *nst_ref, const dou
     hipStream_t st = nullptr;
     p->comm_failed = false;
     p->ne_valid = false;                  // (the half stencil now holds the caller's matrix)
+    p->fit_valid = false;
     SPLPAK_HIP_TRY(hipMemcpy(p->nst, h.data(), sizeof(double) * nst_n, hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
     SPLPAK_HIP_TRY(hipMemcpy(p->xvec, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
     if (p->prefit_fn) SPLPAK_HIP_TRY(p->prefit_fn(p, st, p->fn_user), SPLPAK_E_NODEVICE);
@@ -1469,6 +1506,86 @@ int32_t splpak_debug_plan_solve(splpak_plan *p, const double *nst_ref, const dou
     if (int r = plan_factor_solve(p, p->xvec, st)) return r;
     SPLPAK_HIP_TRY(hipMemcpy(v.data(), p->xvec, sizeof(double) * (size_t)g.ncol, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
     for (int i = 0; i < g.ncol; ++i) x[ref_column(g, i)] = v[(size_t)i];
+    return 0;
+}
+
+int32_t splpak_debug_plan_rows_gradient(splpak_plan *p, const double *coef, int32_t which, double *rho, double *den, double *ssq)
+{
+    if (!p || !coef || !rho || which < 0 || which > 2) { set_error("null argument, or `which` outside 0 .. 2"); return SPLPAK_E_BADARG; }
+    OptionsScope opt_scope(&p->opt);
+    if (p->world > 1 || p->dm.R > 1 || p->ar) { set_error("not for a rank of a sharded or distributed fit"); return SPLPAK_E_UNSUPPORTED; }
+    if (!p->fit_valid) { set_error("the plan holds no rows: no completed fit (or a splpak_debug_plan_solve since)"); return SPLPAK_E_UNSUPPORTED; }
+    if (int r = device_ready()) return r;
+    const Grid &g = p->g;
+    const Band &b = p->band;
+    const bool smooth = p->xtrap != 0.0;
+    hipStream_t st = nullptr;
+    std::vector<double> v((size_t)b.npad, 0.0);
+    for (int i = 0; i < g.ncol; ++i) v[(size_t)i] = coef[ref_column(g, i)];
+    SPLPAK_HIP_TRY(hipMemcpy(p->xvec, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
+    if (which == 1) {
+        if (int r = plan_diagnostics_pass(p, p->fit_rows, st, nullptr)) return r;
+    } else {
+        SortScratch rows = p->s;
+        if (which == 2) rows.ys = nullptr;              // the operator form of pcg_solve
+        SPLPAK_HIP_TRY(hipMemsetAsync(p->rho, 0, sizeof(double) * (size_t)(b.npad + SC_COUNT), st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(plan_rows_residual(p, rows, p->xvec, smooth && p->rank == 0, p->rho, st), SPLPAK_E_NODEVICE);
+    }
+    SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipMemcpy(v.data(), p->rho, sizeof(double) * (size_t)g.ncol, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    for (int i = 0; i < g.ncol; ++i) rho[ref_column(g, i)] = v[(size_t)i];
+    if (den) {
+        std::memset(den, 0, sizeof(double) * (size_t)g.ncol);
+        if (which == 1) {
+            SPLPAK_HIP_TRY(hipMemcpy(v.data(), p->tmp, sizeof(double) * (size_t)g.ncol, hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+            for (int i = 0; i < g.ncol; ++i) den[ref_column(g, i)] = v[(size_t)i];
+        }
+    }
+    if (ssq) {
+        *ssq = 0.0;
+        if (which == 1) SPLPAK_HIP_TRY(hipMemcpy(ssq, p->rho + b.npad, sizeof(double), hipMemcpyDeviceToHost), SPLPAK_E_NODEVICE);
+    }
+    return 0;
+}
+
+int32_t splpak_debug_plan_precondition(splpak_plan *p, int32_t part, const double *r, double *z)
+{
+    if (!p || !r || !z || part < 0 || part > 2) { set_error("null argument, or `part` outside 0 .. 2"); return SPLPAK_E_BADARG; }
+    OptionsScope opt_scope(&p->opt);
+    if (!p->pcg) { set_error("the plan has no iteration"); return SPLPAK_E_UNSUPPORTED; }
+    if (!p->pcg_prepared) { set_error("the plan's last fit did not prepare the preconditioner (no fit yet, or one that went to the factorisation directly)"); return SPLPAK_E_UNSUPPORTED; }
+    if (int rc = device_ready()) return rc;
+    const Grid &g = p->g;
+    std::vector<double> v((size_t)g.ncol), w((size_t)g.ncol);
+    for (int i = 0; i < g.ncol; ++i) v[(size_t)i] = r[ref_column(g, i)];
+    if (int rc = pcg_debug_precondition(p->pcg, part, v.data(), w.data())) return rc;
+    for (int i = 0; i < g.ncol; ++i) z[ref_column(g, i)] = w[(size_t)i];
+    return 0;
+}
+
+int32_t splpak_debug_plan_pcg_tables(const splpak_plan *p, int32_t dim, double *V, double *VT, int32_t *n_out)
+{
+    if (!p || !n_out) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (dim < 0 || dim >= p->g.ndim) { set_error("dimension outside the grid"); return SPLPAK_E_BADARG; }
+    if (!p->pcg) { set_error("the plan has no iteration"); return SPLPAK_E_UNSUPPORTED; }
+    int k = 0;
+    while (p->g.perm[k] != dim) ++k;
+    *n_out = p->g.nodes[k];
+    if (!V && !VT) return 0;
+    if (int rc = device_ready()) return rc;
+    return pcg_debug_tables(p->pcg, k, V, VT);
+}
+
+int32_t splpak_debug_plan_pcg_diagonal(const splpak_plan *p, double *dinv)
+{
+    if (!p || !dinv) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (!p->pcg) { set_error("the plan has no iteration"); return SPLPAK_E_UNSUPPORTED; }
+    if (!p->pcg_prepared) { set_error("the plan's last fit did not prepare the preconditioner"); return SPLPAK_E_UNSUPPORTED; }
+    if (int rc = device_ready()) return rc;
+    const Grid &g = p->g;
+    std::vector<double> v((size_t)g.ncol);
+    if (int rc = pcg_debug_diagonal(p->pcg, v.data())) return rc;
+    for (int i = 0; i < g.ncol; ++i) dinv[ref_column(g, i)] = v[(size_t)i];
     return 0;
 }
 

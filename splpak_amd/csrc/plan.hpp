@@ -110,6 +110,9 @@ struct splpak_plan {
     bool rows_only = false;       // iteration-only 4-D plans: the normal equations are never assembled (right-hand side, histogram and
                                   // backward-error denominators come from the rows: rowsop.hip); no half stencil, no Gram scratch
     bool ne_valid = false;        // nst / rhs hold what the last fit assembled (splpak_debug_plan_normal_equations)
+    bool fit_valid = false;       // the binned points, dcw, spf and rhs are those of a completed single-rank fit (splpak_debug_plan_rows_gradient)
+    bool fit_rows = false;        // ... which never assembled the normal equations (a rows-only plan, or a lazy fit the iteration answered)
+    bool pcg_prepared = false;    // the last fit prepared the preconditioner (splpak_debug_plan_precondition)
     const char *fn_name = nullptr;                 // what the hooks are (splpak_plan_factorisation); fn_code: 2 two-ended band, 4 nested dissection, 3 distributed band
     int fn_code = 0;
 };
@@ -183,5 +186,10 @@ hipError_t pcg_sum_w2(splpak_plan *p, hipStream_t st);
 hipError_t pcg_prepare(splpak_plan *p, PcgState *s, double sumw2, bool smooth, bool from_rows, hipStream_t st);
 bool pcg_boxes_from_rows(const PcgState *s);      // the state can build its boxes from the rows (4-D: the fit may leave the normal equations unassembled)
 int pcg_solve(splpak_plan *p, PcgState *s, double *v, double tol, bool smooth, hipStream_t st);
+// diagnostics (splpak_debug_plan_precondition / _pcg_tables / _pcg_diagonal): host vectors in the plan's INTERNAL column order.
+// part: 0 the whole preconditioner, 1 its separable part, 2 its boxes (zero when the fit dropped them)
+int pcg_debug_precondition(PcgState *s, int part, const double *r_host, double *z_host);
+int pcg_debug_tables(const PcgState *s, int k, double *V_host, double *VT_host);      // either may be NULL
+int pcg_debug_diagonal(const PcgState *s, double *dinv_host);
 int twoend_debug_solve(int n, int halfbw, const double *a_lower, const double *bvec, double *x_out, int *hinfo_out);
 }  // namespace splpak

@@ -1,0 +1,860 @@
+"""The rows pass, the preconditioner and the solver choice on their own.
+
+Every fit, whichever solver answers it, is refined against the ROWS (plan.hpp plan_rows_residual): a pass that is linearly wrong
+moves the fixed point of every solver together, and info[9] -- measured with the same kernels -- stays small.  These tests
+evaluate the passes at arbitrary vectors and compare them, column by column, with the oracle's rows (oracle_rows_gradient_den),
+and the preconditioner with plain arithmetic on the host.
+
+CPU tier: the oracle's new vector against its own long-double normal equations; the tile-residue cover of the 4-D grids; the
+          constructed cell counts; the new diagnostic entries' argument checks; unknown SPLPAK_SOLVER values.
+GPU tier:
+  A. splpak_debug_plan_rows_gradient (which = 0 refinement / operator pass, 1 the closing diagnostics pass with ssq and the
+     backward error's denominators, 2 the operator form y = 0) against the oracle at two seeded vectors, at 0 (the right-hand
+     side) and at the fitted coefficients;
+  B. what only rows-only plans compute: the histogram from the rows, a REAL32 fit through an iteration-only plan;
+  C. splpak_debug_plan_precondition: the separable part against the exported tables in long double with the running error
+     bound of its dot products, the boxes against a host solve whose inverse factor is rounded to float32, the sum of both;
+  D. the conjugate-gradient loop against a textbook one on the host that uses the dense M^-1 (from unit vectors through the
+     entry) and the oracle's N: iteration counts, backward error of the unrefined coefficients, spectrum of M^-1 N;
+  7. the solver choice: unset = auto = empty, [513, 7, 7, 7] left to itself.
+"""
+import ctypes as C
+import functools
+import time
+
+import numpy as np
+import pytest
+
+from splpak_amd import capi
+from tests.cases import CASES, make_inputs
+from tests.conftest import load_golden, relmax
+from tests.test_normal_equations import (EXTRA, NE_CEIL, NE_TOL, ORACLE_CASES, _busiest_cell, _oracle_ne, _seeded, _tensors,
+                                         stencil_matvec, stencil_to_sparse)
+
+TILE = (3, 3, 3, 2)          # cells of a workgroup's tile of the 4-D rows pass, internal dimension order (rowsop.hip TCS)
+U53 = 2.0 ** -53
+_dp = C.POINTER(C.c_double)
+
+
+def _args(inp):
+    return [inp[k] for k in ("ndim", "xdata", "ydata", "wdata", "xmin", "xmax", "nodes", "xtrap")]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# cases
+def _cell_points(nd, nodes, counts, seed, xmin=None, xmax=None):
+    """counts[k] points strictly inside window k of the grid (k row-major over the nodes - 3 windows per dimension, dimension 0
+    fastest): window j of a dimension is entered through node interval j + 1, which belongs to it alone."""
+    nodes = np.asarray(nodes)
+    cells = nodes - 3
+    assert len(counts) == int(np.prod(cells))
+    xmin = np.zeros(nd) if xmin is None else np.asarray(xmin, dtype=np.float64)
+    xmax = np.ones(nd) if xmax is None else np.asarray(xmax, dtype=np.float64)
+    dx = (xmax - xmin) / (nodes - 1)
+    rng = np.random.default_rng(seed)
+    xs = []
+    for k, cnt in enumerate(counts):
+        j = np.array(np.unravel_index(k, cells[::-1]))[::-1]          # dimension 0 fastest
+        u = 0.05 + 0.9 * rng.random((cnt, nd))
+        xs.append(xmin + (j + 1 + u) * dx)
+    x = np.ascontiguousarray(rng.permutation(np.vstack(xs)))
+    y = np.cos(3.0 * ((x - xmin) / (xmax - xmin)).sum(axis=1)) + 0.25
+    w = 0.5 + rng.random(x.shape[0])
+    return dict(ndim=nd, xdata=x, ydata=y, wdata=w, xmin=xmin, xmax=xmax, nodes=np.array(nodes, dtype=np.int32), xtrap=1.0)
+
+
+EDGE_COUNTS = [63, 0, 64, 0, 65, 0, 1023, 0, 1024, 0, 1025, 0]
+CELL_CASES = {"cells_1d16": (1, [16], EDGE_COUNTS + [9]), "cells_2d_7_6": (2, [7, 6], EDGE_COUNTS), "cells_3d_5_6_5": (3, [5, 6, 5], EDGE_COUNTS)}
+
+GOLDEN_ROWS = ["c1_1d16_xt0", "1d_sparse", "2d16_zero_w", "2d16_outside", "2d_aniso_box", "2d32_cc_xt0", "3d8_cc_clust", "3d_aniso", "4d4",
+               "4d5_cc", "4d6"]
+# 4-D grids whose cell counts cover every residue of the tile shape in every position of the plan's dimension order
+# (test_4d_grids_cover_the_tile_residues); 4d5_cc and 4d6 above and perm_4d_7_4_6_5 of EXTRA belong to the cover
+TILE_GRIDS = {"4d_13_12_14_11": [13, 12, 14, 11], "4d_9_16_5_17_box_cc": [9, 16, 5, 17], "4d_4_4_4_4": [4, 4, 4, 4], "4d_5_21_4_6": [5, 21, 4, 6]}
+COVER_GRIDS = list(TILE_GRIDS.values()) + [[7, 4, 6, 5], [5, 5, 5, 5], [6, 6, 6, 6]]
+NEW_4D = ["4d_xtrap0", "4d_zero_w_tile", "4d_far_outside", "4d_big_cell"]
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(name):
+    if name in CASES:
+        return make_inputs(CASES[name])
+    if name in EXTRA:
+        return EXTRA[name]
+    if name in CELL_CASES:
+        nd, nodes, counts = CELL_CASES[name]
+        return _cell_points(nd, nodes, counts, 31 + nd)
+    if name == "4d_13_12_14_11":
+        return _seeded(4, [13, 12, 14, 11], 200000, 41)
+    if name == "4d_9_16_5_17_box_cc":
+        return _seeded(4, [9, 16, 5, 17], 150000, 42, weighted=False, xmin=[-1.0, 0.0, 2.0, -3.0], xmax=[1.0, 3.0, 2.5, -1.0])
+    if name == "4d_4_4_4_4":
+        return _seeded(4, [4, 4, 4, 4], 3000, 43)
+    if name == "4d_5_21_4_6":
+        return _seeded(4, [5, 21, 4, 6], 30000, 44)
+    if name == "4d_xtrap0":
+        return _seeded(4, [7, 6, 5, 8], 40000, 45, xtrap=0.0)
+    if name == "4d_zero_w_tile":          # every weight zero in the windows 0 .. 2 of every dimension: the whole first tile, whatever the order
+        inp = _seeded(4, [10, 9, 8, 7], 40000, 46)
+        dx = (inp["xmax"] - inp["xmin"]) / (inp["nodes"] - 1)
+        inp["wdata"] = np.where(np.all(inp["xdata"] < inp["xmin"] + 4.0 * dx, axis=1), 0.0, inp["wdata"])
+        return inp
+    if name == "4d_far_outside":
+        inp = _seeded(4, [6, 5, 6, 5], 5000, 47)
+        inp["xdata"] = inp["xdata"].copy()
+        inp["xdata"][17] = [0.9, 0.1, 7.5, 0.8]
+        return inp
+    if name == "4d_big_cell":             # 1 500 more points in one window of a grid with ~35 per window
+        inp = _seeded(4, [8, 7, 6, 9], 30000, 48)
+        extra = _cell_points(4, [8, 7, 6, 9], [1500 if k == 77 else 0 for k in range(5 * 4 * 3 * 6)], 49)
+        inp["xdata"] = np.ascontiguousarray(np.vstack([inp["xdata"], extra["xdata"]]))
+        inp["ydata"] = np.concatenate([inp["ydata"], extra["ydata"]])
+        inp["wdata"] = np.concatenate([inp["wdata"], extra["wdata"]])
+        return inp
+    raise KeyError(name)
+
+
+ROWS_CASES = list(EXTRA) + GOLDEN_ROWS + list(TILE_GRIDS) + NEW_4D + list(CELL_CASES)
+
+
+def _window_counts(inp):
+    nodes = np.asarray(inp["nodes"])
+    x = inp["xdata"][:, :inp["ndim"]]
+    dx = (inp["xmax"] - inp["xmin"]) / (nodes - 1)
+    it = np.clip(np.floor((x - inp["xmin"]) / dx).astype(np.int64) - 1, 0, nodes - 4)
+    return np.bincount(np.ravel_multi_index(it[:, ::-1].T, (nodes - 3)[::-1]), minlength=int(np.prod(nodes - 3)))
+
+
+def _internal_order(nodes):
+    """Grid::perm's rule (plan.hip build_grid): ascending node counts, stable."""
+    return sorted(range(len(nodes)), key=lambda d: (nodes[d], d))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# CPU tier
+@pytest.mark.parametrize("name", ORACLE_CASES)
+def test_oracle_gradient_denominators_are_the_absolute_normal_equations(port, name):
+    """oracle_rows_gradient_den's second vector is absrhs + |absN| |c| of oracle_normal_equations, entry by entry."""
+    inp = _inputs(name)
+    ne = port.normal_equations(*_args(inp))
+    worst = 0.0
+    for seed in (1, 2):
+        c = np.random.default_rng(seed).uniform(-1.0, 1.0, ne["rhs"].size)
+        rho, den, ssq, nrow, ncons = port.rows_gradient_den(*_args(inp), c)
+        assert np.array_equal(rho, port.rows_gradient_vec(*_args(inp), c))
+        ref = ne["absrhs"].astype(np.longdouble) + stencil_matvec(ne["absN"], inp["nodes"], c, absolute=True)
+        err = np.abs(np.asarray(ref - den, dtype=np.float64))
+        assert np.all(den[ref == 0] == 0)
+        worst = max(worst, float(np.max(err / np.where(ref > 0, np.asarray(ref, dtype=np.float64), 1.0))))
+        assert (nrow, ncons) == (ne["data_rows"], ne["constraint_rows"])
+        assert abs(np.sqrt(ssq) - port.rows_gradient(*_args(inp), c)[1]) <= 1e-15 * np.sqrt(ssq)
+    print(f"{name}: |den - (absrhs + absN |c|)| / den <= {worst:.1e}")
+    assert worst <= 1e-13
+
+
+def test_4d_grids_cover_the_tile_residues():
+    """Cell counts of the 4-D cases, in the plan's internal dimension order, modulo the tile shape: every residue in every
+    position, one cell in a dimension, and a grid smaller than one tile."""
+    seen = [set() for _ in TILE]
+    for nodes in COVER_GRIDS:
+        cells = [nodes[d] - 3 for d in _internal_order(nodes)]
+        for pos, (c, t) in enumerate(zip(cells, TILE)):
+            seen[pos].add(c % t)
+    for pos, t in enumerate(TILE):
+        assert seen[pos] == set(range(t)), (pos, seen[pos])
+    assert any(min(n) == 4 for n in COVER_GRIDS)
+    assert any(all(n[d] - 3 < t for d, t in zip(_internal_order(n), TILE)) for n in COVER_GRIDS)
+    for name, nodes in list(TILE_GRIDS.items()) + [("perm_4d_7_4_6_5", [7, 4, 6, 5]), ("4d5_cc", [5] * 4), ("4d6", [6] * 4)]:
+        assert list(_inputs(name)["nodes"]) == nodes and name in ROWS_CASES
+
+
+def test_constructed_cells_hold_the_counts_they_were_built_for():
+    for name, (nd, nodes, counts) in CELL_CASES.items():
+        assert list(_window_counts(_inputs(name))) == counts, name
+    inp = _inputs("4d_big_cell")
+    assert _window_counts(inp).max() > 1024 and _busiest_cell(inp) == _window_counts(inp).max()
+    inp = _inputs("4d_zero_w_tile")
+    nz = _window_counts(dict(inp, xdata=inp["xdata"][inp["wdata"] > 0]))
+    cells = inp["nodes"] - 3
+    first = [k for k in range(nz.size) if all(j < 3 for j in np.unravel_index(k, cells[::-1]))]
+    assert len(first) == 81 and not nz[first].any() and np.count_nonzero(nz) == nz.size - 81
+
+
+def test_new_debug_entries_reject_null_arguments_without_gpu():
+    L = capi.lib()
+    d = np.zeros(16)
+    p = d.ctypes.data_as(_dp)
+    n = C.c_int32(0)
+    assert L.splpak_debug_plan_rows_gradient(None, p, 0, p, p, None) == capi.E_BADARG
+    assert L.splpak_debug_plan_precondition(None, 0, p, p) == capi.E_BADARG
+    assert L.splpak_debug_plan_pcg_tables(None, 0, p, p, C.byref(n)) == capi.E_BADARG
+    assert L.splpak_debug_plan_pcg_diagonal(None, p) == capi.E_BADARG
+
+
+@pytest.mark.parametrize("value", ["PCG", "cg", "direct "])
+def test_unknown_solver_is_refused_at_plan_creation(value, monkeypatch):
+    """A value that is none of direct | pcg | pcg+direct | auto | empty used to be read as "auto" without its out-of-memory fallback."""
+    monkeypatch.setenv("SPLPAK_SOLVER", value)
+    L = capi.lib()
+    nodes = np.array([8, 8], dtype=np.int32)
+    lo, hi = np.zeros(2), np.ones(2)
+    h = C.c_void_p()
+    rc = L.splpak_plan_create(2, nodes.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp), 1.0, 100, None, 0,
+                              C.byref(h))
+    msg = capi.last_error()
+    assert rc == capi.E_BADARG and not h.value, (rc, msg)
+    assert value in msg and all(f" {v}" in msg for v in ("direct", "pcg", "pcg+direct", "auto")), msg
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU tier, shared
+class _Env:
+    def __init__(self, monkeypatch, env):
+        self.mp, self.env = monkeypatch, env
+
+    def __enter__(self):
+        for k, v in self.env.items():
+            self.mp.setenv(k, v)
+
+    def __exit__(self, *a):
+        for k in self.env:
+            self.mp.delenv(k, raising=False)
+
+
+def _fit_plan(inp, env, monkeypatch):
+    """One fit through a plan created under `env` -> (plan, ierror, info, coef); the plan stays open."""
+    import torch
+    x, y, w = _tensors(inp)
+    with _Env(monkeypatch, env):
+        plan = capi.Plan(inp["ndim"], inp["nodes"], inp["xmin"], inp["xmax"], inp["xtrap"], x.shape[0])
+    try:
+        coef = torch.zeros(plan.ncol, dtype=torch.float64, device=x.device)
+        ierr, info = plan.fit(x, y, w, coef)
+        torch.cuda.synchronize()
+        return plan, ierr, info, coef.cpu().numpy()
+    except Exception:
+        plan.close()
+        raise
+
+
+def _iteration_answered(info):
+    return info[4] == 0.0 and info[6] == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU tier A
+SOLVERS_4D = [("direct", {"SPLPAK_SOLVER": "direct"}), ("pcg", {"SPLPAK_SOLVER": "pcg"}),
+              ("pcg+direct", {"SPLPAK_SOLVER": "pcg+direct", "SPLPAK_PCG_ALWAYS": "1"})]
+NE_MAX_4D_COLS = 4096        # oracle_normal_equations of a 4-D grid (1 201 slots per column, long double) beyond this costs minutes
+
+
+class _Oracle:
+    """The oracle's rows at given coefficients, each vector computed once per case.  The histogram's total in long double
+    (exact_total): the reference's point-by-point sum in double is off by 1.9e-14 over the 2e5 weights of 4d_13_12_14_11, every
+    constraint weight xtrap (expect - have) inherits up to four times that, and the oracle's gradient and denominators moved by
+    4.6e-14 and 1.3e-13 of their scale when the total was made exact -- the whole of what the library, which adds the total in a
+    tree, had differed by."""
+
+    def __init__(self, port, inp):
+        self.port, self.inp = port, inp
+        self.zero_y = dict(inp, ydata=np.zeros_like(inp["ydata"]))
+        self.cache = {}
+
+    def at(self, key, c, y0=False):
+        if (key, y0) not in self.cache:
+            self.cache[(key, y0)] = self.port.rows_gradient_den(*_args(self.zero_y if y0 else self.inp), c, exact_total=True)
+        return self.cache[(key, y0)]
+
+
+def _check_gradient(label, fails, worst, plan, orc, key, c, tol, which, rows_total, nd, fitted=False):
+    rho_o, den_o, ssq_o, _, _ = orc.at(key, c, y0=(which == 2))
+    rho, den, ssq = plan.rows_gradient(c, which)
+    err = np.abs(rho - rho_o)
+    zero = den_o == 0
+    rel = float(np.max(np.where(zero, 0.0, err / np.where(zero, 1.0, den_o))))
+    worst["grad"] = max(worst["grad"], rel)
+    if not rel <= tol:
+        fails.append(f"{label} which={which} c={key}: |rho - oracle| / den = {rel:.2e} > {tol:.2e} at column {int(np.argmax(np.where(zero, 0.0, err / np.where(zero, 1.0, den_o))))}")
+    if np.any(rho[zero] != 0):
+        fails.append(f"{label} which={which} c={key}: {int(np.count_nonzero(rho[zero]))} nonzeros where the rows have no term")
+    if which != 1:
+        return None
+    if fitted:
+        s_rel = abs(np.sqrt(ssq) - np.sqrt(ssq_o)) / np.sqrt(ssq_o) if ssq_o > 0 else abs(ssq)
+        worst["reserr"] = max(worst["reserr"], s_rel)
+        if not s_rel <= 1e-9:
+            fails.append(f"{label} c=fitted: reserr {np.sqrt(ssq):.12e} against {np.sqrt(ssq_o):.12e} ({s_rel:.1e} > 1e-9)")
+    else:
+        bound = (rows_total + 4 ** nd) * 2.0 ** -52
+        s_rel = abs(ssq - ssq_o) / ssq_o if ssq_o > 0 else abs(ssq)
+        worst["ssq"] = max(worst["ssq"], s_rel / bound)
+        if not s_rel <= bound:
+            fails.append(f"{label} c={key}: |ssq - oracle| / ssq = {s_rel:.2e} > (rows + 4^d) 2^-52 = {bound:.2e}")
+    return den
+
+
+def _rows_case(port, name, monkeypatch, solvers, forms=({},)):
+    inp = _inputs(name)
+    nd, nodes = inp["ndim"], [int(n) for n in inp["nodes"]]
+    ncol = int(np.prod(nodes))
+    big = _busiest_cell(inp)
+    tol = min(max(NE_TOL, (4 ** nd + big) * U53), NE_CEIL)
+    t0 = time.perf_counter()
+    orc = _Oracle(port, inp)
+    _, _, _, nrow_o, ncons_o = orc.at("zero", np.zeros(ncol))
+    port.lib.oracle_set_exact_histogram_total(1)
+    try:
+        ne = _oracle_ne(port, inp) if (nd < 4 or ncol <= NE_MAX_4D_COLS) else None
+    finally:
+        port.lib.oracle_set_exact_histogram_total(0)
+    vecs = [("seed1", np.random.default_rng(1).uniform(-1.0, 1.0, ncol)), ("seed2", np.random.default_rng(2).uniform(-1.0, 1.0, ncol)),
+            ("zero", np.zeros(ncol))]
+    tol_den = NE_TOL          # the denominators: the issue's bar as it stands, not widened by the summation length
+    fails, worst = [], dict(grad=0.0, ssq=0.0, reserr=0.0, den=0.0, den_self=0.0)
+    for sname, senv in solvers:
+        for form in forms:
+            label = f"{name} [{sname}{' ' + str(form) if form else ''}]"
+            plan, ierr, info, coef = _fit_plan(inp, dict(senv, **form), monkeypatch)
+            try:
+                assert ierr == 0, f"{label}: ierror {ierr}: {capi.last_error()}"
+                # (a node exactly on the sparse-area threshold would change the constraint rows: the cases' seeds are those where
+                #  the counts agree)
+                assert (info[0], info[1]) == (nrow_o, ncons_o), f"{label}: rows {info[0]:.0f} + {info[1]:.0f}, oracle {nrow_o} + {ncons_o}"
+                # the fit never assembled: an iteration-only 4-D plan, or a 4-D plan with both solvers whose iteration answered --
+                # unless the cell-by-cell form of the pass was asked for, which leaves the plan without the tiled rows operator
+                tiled = nd == 4 and "SPLPAK_ROWS_TILES" not in form
+                rows_fit = tiled and (sname == "pcg" or (sname == "pcg+direct" and _iteration_answered(info)))
+                fkey = f"fitted {sname} {sorted(form.items())}"
+                for key, c in vecs + [(fkey, coef)]:
+                    fitted = key == fkey
+                    _check_gradient(label, fails, worst, plan, orc, key, c, tol, 0, nrow_o + ncons_o, nd)
+                    den = _check_gradient(label, fails, worst, plan, orc, key, c, tol, 1, nrow_o + ncons_o, nd, fitted=fitted)
+                    _check_gradient(label, fails, worst, plan, orc, key, c, tol, 2, nrow_o + ncons_o, nd)
+                    # the backward error's denominators
+                    if rows_fit:
+                        # what rowsop_backward_denominators forms: |A|^T W^2 |A| |c| + |C|^T |C| |c| (the oracle's vector for y = 0)
+                        # + |rhs| (the oracle's gradient at 0).  The oracle's vector for the fit's own y has sum |a_r| |b_r| in the
+                        # place of |sum a_r b_r|: equal only where y keeps one sign over a node's support, an upper bound otherwise
+                        den_ref = orc.at(key, c, y0=True)[1] + np.abs(orc.at("zero", np.zeros(ncol))[0])
+                        upper = scale = orc.at(key, c)[1]
+                        worst["den_gap"] = max(worst.get("den_gap", 0.0), float(np.max((upper - den) / np.where(upper > 0, upper, 1.0))))
+                        if np.any(den > upper * (1.0 + tol)):
+                            fails.append(f"{label} c={key}: denominators above the oracle's |A|^T (|A||c| + |b|)")
+                    elif ne is not None:
+                        den_ref = np.asarray(stencil_matvec(ne["N"], nodes, c, absolute=True) + np.abs(ne["rhs"]).astype(np.longdouble), dtype=np.float64)
+                        scale = np.asarray(stencil_matvec(ne["absN"], nodes, c, absolute=True) + ne["absrhs"].astype(np.longdouble), dtype=np.float64)
+                    else:
+                        den_ref = None
+                    if den_ref is not None:
+                        # NE_TOL as tests/test_normal_equations.py defines it: |dN_ij| <= tol absN_ij, |drhs_i| <= tol absrhs_i, so
+                        # |d(|N||c| + |rhs|)_i| <= tol (absN |c| + absrhs)_i -- the sums of absolute values, not the cancelled |rhs_i|
+                        z = scale == 0
+                        drel = float(np.max(np.where(z, 0.0, np.abs(den - den_ref) / np.where(z, 1.0, scale))))
+                        worst["den"] = max(worst["den"], drel)
+                        zs = den_ref == 0
+                        worst["den_self"] = max(worst["den_self"], float(np.max(np.where(zs, 0.0, np.abs(den - den_ref) / np.where(zs, 1.0, den_ref)))))
+                        if not drel <= tol_den or np.any(den[z] != 0):
+                            fails.append(f"{label} c={key}: denominators ({'rows' if rows_fit else 'N'}) {drel:.2e} > {tol_den:.2e}")
+                print(f"{label}: rows {nrow_o} + {ncons_o}, busiest cell {big}; {'rows-only / lazy' if rows_fit else 'assembled'}"
+                      f"{'' if rows_fit or ne is not None else ' (denominators not compared: no oracle N at this size)'}")
+            finally:
+                plan.close()
+    print(f"{name}: worst |rho - oracle| / den {worst['grad']:.2e} (bound {tol:.2e}); ssq error / bound {worst['ssq']:.2f}; reserr at the fit {worst['reserr']:.1e} "
+          f"(1e-9); denominators {worst['den']:.2e} of the sums of absolute values (bound {tol_den:.2e}; {worst['den_self']:.2e} of the denominator itself; rows-only: up to {worst.get('den_gap', 0.0):.2f} below the oracle's |A|^T (|A||c| + |b|)); {time.perf_counter() - t0:.1f} s")
+    assert not fails, "\n".join(fails)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ROWS_CASES)
+def test_rows_pass_matches_oracle(port, name, monkeypatch):
+    """|rho_gpu - rho_oracle|_i <= tol den_oracle_i with exact zeros where the rows have no term, for the refinement / operator
+    pass, the diagnostics pass (with ssq and the denominators) and the operator form, at two seeded vectors, at 0 and at the
+    fitted coefficients; tol = NE_TOL widened by the summation length (4^d + busiest cell) 2^-53, never above NE_CEIL.
+
+    The denominators of which = 1 at plain NE_TOL, in NE_TOL's own sense (tests/test_normal_equations.py): relative to the sums of
+    absolute values absN |c| + absrhs, not to the cancelled |rhs_i| (relative to the denominator itself the worst is printed; it
+    reaches 5e-12 at c = 0, where den = |rhs| and y changes sign).  Fits that assembled N: |N||c| + |rhs| from the oracle's N.
+    Rows-only and lazy fits: rowsop_backward_denominators adds |rhs_i|, not sum |a||b| -- the reference is the oracle's vector for
+    y = 0 plus |oracle gradient at 0|, and the oracle's vector for the fit's own y, up to 100 % larger, is kept as an upper bound."""
+    nd = _inputs(name)["ndim"]
+    _rows_case(port, name, monkeypatch, SOLVERS_4D if nd == 4 else SOLVERS_4D[:1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["4d_13_12_14_11", "4d_5_21_4_6", "4d_big_cell"])
+def test_rows_pass_cell_by_cell_forms_match_oracle(port, name, monkeypatch):
+    """The 4-D passes in their cell-by-cell forms (assemble.hip): rows_tiles = 0 for the refinement pass, residual_cells for the
+    diagnostics pass."""
+    _rows_case(port, name, monkeypatch, SOLVERS_4D[:2], forms=({"SPLPAK_ROWS_TILES": "0"}, {"SPLPAK_RESIDUAL_CELLS": "1"}))
+
+
+@pytest.mark.gpu
+def test_rows_pass_on_one_stream_gives_the_same_bits(monkeypatch):
+    inp = _inputs("4d_13_12_14_11")
+    c = np.random.default_rng(5).uniform(-1.0, 1.0, int(np.prod(inp["nodes"])))
+    got = []
+    for env in ({}, {"SPLPAK_ROWS_ONE_STREAM": "1"}):
+        plan, ierr, info, coef = _fit_plan(inp, dict(env, SPLPAK_SOLVER="pcg"), monkeypatch)
+        try:
+            assert ierr == 0
+            got.append([coef] + [plan.rows_gradient(c, which)[0] for which in (0, 1, 2)])
+        finally:
+            plan.close()
+    for a, b in zip(*got):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.gpu
+def test_debug_entries_leave_the_next_fit_alone_and_refuse_what_there_is_not(monkeypatch):
+    import torch
+    L = capi.lib()
+    inp = _inputs("perm_4d_7_4_6_5")
+    ncol = int(np.prod(inp["nodes"]))
+    x, y, w = _tensors(inp)
+    c = np.random.default_rng(7).uniform(-1.0, 1.0, ncol)
+    buf = np.zeros(ncol)
+    n = C.c_int32(0)
+    for env in ({"SPLPAK_SOLVER": "pcg+direct", "SPLPAK_PCG_ALWAYS": "1"}, {"SPLPAK_SOLVER": "direct"}):
+        with _Env(monkeypatch, env):
+            plan = capi.Plan(4, inp["nodes"], inp["xmin"], inp["xmax"], 1.0, x.shape[0])
+        try:
+            has_pcg = env["SPLPAK_SOLVER"] != "direct"
+            # nothing there yet
+            assert L.splpak_debug_plan_rows_gradient(plan._h, c.ctypes.data_as(_dp), 0, buf.ctypes.data_as(_dp), None, None) == capi.E_UNSUPPORTED
+            assert L.splpak_debug_plan_precondition(plan._h, 0, c.ctypes.data_as(_dp), buf.ctypes.data_as(_dp)) == capi.E_UNSUPPORTED
+            assert L.splpak_debug_plan_pcg_diagonal(plan._h, buf.ctypes.data_as(_dp)) == capi.E_UNSUPPORTED
+            assert L.splpak_debug_plan_pcg_tables(plan._h, 0, None, None, C.byref(n)) == (0 if has_pcg else capi.E_UNSUPPORTED)
+            assert L.splpak_debug_plan_pcg_tables(plan._h, 4, None, None, C.byref(n)) == capi.E_BADARG
+            assert L.splpak_debug_plan_rows_gradient(plan._h, None, 0, buf.ctypes.data_as(_dp), None, None) == capi.E_BADARG
+            assert L.splpak_debug_plan_rows_gradient(plan._h, c.ctypes.data_as(_dp), 3, buf.ctypes.data_as(_dp), None, None) == capi.E_BADARG
+            assert L.splpak_debug_plan_precondition(plan._h, 3, c.ctypes.data_as(_dp), buf.ctypes.data_as(_dp)) == capi.E_BADARG
+            assert L.splpak_debug_plan_precondition(plan._h, 0, None, buf.ctypes.data_as(_dp)) == capi.E_BADARG
+            assert L.splpak_debug_plan_pcg_diagonal(plan._h, None) == capi.E_BADARG
+            coefs = []
+            for trial in range(2):
+                coef = torch.zeros(ncol, dtype=torch.float64, device=x.device)
+                ierr, info = plan.fit(x, y, w, coef)
+                torch.cuda.synchronize()
+                assert ierr == 0
+                coefs.append((coef.cpu().numpy(), info[8], info[9], info[2]))
+                if trial == 0:
+                    for which in (0, 1, 2):
+                        plan.rows_gradient(c, which)
+                    if has_pcg:
+                        for part in (0, 1, 2):
+                            plan.precondition(c, part)
+                        plan.pcg_tables()
+            assert np.array_equal(coefs[0][0], coefs[1][0]) and coefs[0][1:] == coefs[1][1:]
+        finally:
+            plan.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU tier B
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["4d4", "4d5_cc", "4d6"])
+def test_histogram_from_the_rows_matches_golden(name, monkeypatch):
+    monkeypatch.setenv("SPLPAK_SOLVER", "pcg")
+    gold = load_golden(name)
+    inp = _inputs(name)
+    c, rc, hist, info = capi.fit(*_args(inp), want_hist=True)
+    assert rc == 0 and _iteration_answered(info)
+    err = relmax(hist, gold["hist"])
+    print(f"{name}: rows-only histogram against the golden {err:.2e} (1e-12); {int(np.count_nonzero(gold['hist'] == 0))} zeros")
+    assert err < 1e-12
+    assert np.all(hist[gold["hist"] == 0] == 0)
+
+
+@pytest.mark.gpu
+def test_histogram_far_outside_point_from_the_rows(port, monkeypatch):
+    """FAR_CASES' 4-D case (tests/test_gpu_parity.py, 4d6_mfma4) through an iteration-only plan: the far-outside atomic of
+    rowsop_histogram against the port's work(1:ncol)."""
+    from tests.test_gpu_parity import FAR_CASES, _far_outside_case
+    monkeypatch.setenv("SPLPAK_SOLVER", "pcg")
+    for name, nd, nodes, m, far, weighted in [f for f in FAR_CASES if f[1] == 4]:
+        x, y, w = _far_outside_case(nd, nodes, m, far, weighted)
+        lo, hi = [0.0] * nd, [1.0] * nd
+        ncol = int(np.prod(nodes))
+        c0, e0, work = port.fit(nd, x, y, w, lo, hi, nodes, 1.0)
+        c1, e1, hist, info = capi.fit(nd, x, y, w, lo, hi, nodes, 1.0, want_hist=True)
+        assert e0 == 0 and e1 == 0 and _iteration_answered(info)
+        base = capi.fit(nd, x[:-1], y[:-1], w[:-1], lo, hi, nodes, 1.0, want_hist=True)[2]
+        diff = hist - base
+        print(f"{name}: outlier counted at {int(np.argmax(np.abs(diff)))}, histogram against the port {relmax(hist, work[:ncol]):.1e} (1e-13)")
+        assert np.count_nonzero(diff) == 1 and abs(diff.max() - w[-1]) < 1e-12
+        assert relmax(hist, work[:ncol]) < 1e-13
+        assert int(np.argmax(diff)) == int(np.argmax(work[:ncol] - port.fit(nd, x[:-1], y[:-1], w[:-1], lo, hi, nodes, 1.0)[2][:ncol]))
+
+
+@pytest.mark.gpu
+def test_real32_fit_through_an_iteration_only_plan(monkeypatch):
+    """16^4 at config 5's density of points (10.8 per cell), inputs rounded to float first: the arithmetic is double and only the
+    storage single, so the REAL32 coefficients are the rounded real64 ones: |c32 - c64| <= 2^-24 |c64| + 1e-10 max |c64|."""
+    from splpak_amd.synth import synth_points
+    monkeypatch.setenv("SPLPAK_SOLVER", "pcg")
+    nd, nod = 4, 16
+    m = int(10.8 * (nod - 1) ** nd)
+    x, y, w = synth_points(nd, m)
+    x32, y32, w32 = x.astype(np.float32), y.astype(np.float32), w.astype(np.float32)
+    lo, hi, nodes = [0.0] * nd, [1.0] * nd, [nod] * nd
+    c64, e64, _, i64 = capi.fit(nd, x32.astype(np.float64), y32.astype(np.float64), w32.astype(np.float64), lo, hi, nodes, 1.0)
+    c32, e32, _, i32 = capi.fit(nd, x32, y32, w32, lo, hi, nodes, 1.0, real32=True)
+    assert e64 == 0 and e32 == 0 and _iteration_answered(i64) and _iteration_answered(i32)
+    assert c32.dtype == np.float32
+    err = np.abs(c32.astype(np.float64) - c64)
+    bound = 2.0 ** -24 * np.abs(c64) + 1e-10 * np.max(np.abs(c64))
+    print(f"16^4, {m} points: REAL32 against real64 of the same inputs, worst |c32 - c64| / bound {float(np.max(err / bound)):.3f}")
+    assert np.all(err <= bound)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU tier C
+PRECOND_GRIDS = [[300], [512], [64, 64], [63, 65], [17, 15], [300, 9], [512, 4], [16, 17, 15], [13, 8, 7], [6, 5, 7, 9], [13, 12, 14, 11], [7, 4, 6, 5]]
+BOX_EDGE = {1: 256, 2: 16, 3: 6, 4: 4}       # pcg.hip pcg_attach: aligned boxes of at most 256 nodes
+
+
+def _precond_inputs(nodes):
+    nd = len(nodes)
+    cells = int(np.prod([n - 1 for n in nodes]))
+    return _seeded(nd, nodes, int(min(200000, max(2000, 10.8 * cells))), 60 + nd + int(np.prod(nodes)) % 17)
+
+
+def _kron_apply(mats, X, transpose):
+    """Along every dimension d (axis nd - 1 - d of X): out_j = sum_i M[i, j] x_i (transpose) or sum_j M[i, j] x_j."""
+    nd = len(mats)
+    for d, M in enumerate(mats):
+        ax = nd - 1 - d
+        A = M.T if transpose else M
+        X = np.moveaxis(np.tensordot(A, X, axes=([1], [ax])), 0, ax)
+    return X
+
+
+def _separable_reference(Vs, dinv, r, nodes):
+    shape = tuple(int(n) for n in nodes[::-1])
+    ld = np.longdouble
+    Vl = [V.astype(ld) for V in Vs]
+    Va = [np.abs(V) for V in Vl]
+    D = dinv.astype(ld).reshape(shape)
+    z = _kron_apply(Vl, D * _kron_apply(Vl, r.astype(ld).reshape(shape), True), False)
+    e = _kron_apply(Va, np.abs(D) * _kron_apply(Va, np.abs(r).astype(ld).reshape(shape), True), False)
+    return z.reshape(-1), e.reshape(-1)
+
+
+def _test_vectors(ncol, seed):
+    first, last = np.zeros(ncol), np.zeros(ncol)
+    first[0], last[-1] = 1.0, 1.0
+    return [("random", np.random.default_rng(seed).uniform(-1.0, 1.0, ncol)), ("first", first), ("last", last), ("ones", np.ones(ncol))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nodes", PRECOND_GRIDS, ids=lambda n: "x".join(map(str, n)))
+def test_separable_part_matches_its_tables(nodes, monkeypatch):
+    """z = (kron V)(dinv * (kron V^T r)) in long double from the exported tables, against part = 1 of the entry, within the running
+    error bound (2 sum_k n_k + 2 d) 2^-53 (kron |V|)(|dinv| (kron |V|^T |r|)): the pairs on the matrix pipe (default; padding to 4 /
+    16, the VALU form where the LDS image does not fit, single modes above 64 nodes), the pairs on the vector unit, mode by mode."""
+    nd, ncol = len(nodes), int(np.prod(nodes))
+    inp = _precond_inputs(nodes)
+    solvers = [{"SPLPAK_SOLVER": "pcg+direct", "SPLPAK_PCG_ALWAYS": "1"}] + ([{"SPLPAK_SOLVER": "pcg"}] if nd == 4 else [])
+    factor = (2 * sum(nodes) + 2 * nd) * U53
+    worst = 0.0
+    for senv in solvers:
+        # (a 1-D grid has no pair of modes: the three forms are one launch)
+        for form in ({}, {"SPLPAK_PCG_PAIRS_VALU": "1"}, {"SPLPAK_PCG_NO_PAIRS": "1"})[:1 if nd == 1 else 3]:
+            plan, ierr, info, coef = _fit_plan(inp, dict(senv, **form), monkeypatch)
+            try:
+                assert ierr in (0, 107), ierr           # (an iteration-only plan may give up; the preconditioner was prepared all the same)
+                Vs, VTs, dinv = plan.pcg_tables()
+                for V, VT, n in zip(Vs, VTs, nodes):
+                    assert V.shape == (n, n) and np.array_equal(VT, V.T)
+                assert np.all(dinv > 0) and np.all(np.isfinite(dinv))
+                for rname, r in _test_vectors(ncol, 70 + nd):
+                    z = plan.precondition(r, 1)
+                    zr, e = _separable_reference(Vs, dinv, r, nodes)
+                    ratio = float(np.max(np.abs(np.asarray(z - zr, dtype=np.float64)) / np.asarray(factor * e, dtype=np.float64)))
+                    worst = max(worst, ratio)
+                    assert ratio <= 1.0, (nodes, senv["SPLPAK_SOLVER"], form, rname, ratio)
+                    z0, z2 = plan.precondition(r, 0), plan.precondition(r, 2)
+                    assert np.all(np.abs(z0 - (z + z2)) <= 2.0 * np.spacing(np.abs(z + z2))), (nodes, form, rname)
+            finally:
+                plan.close()
+    print(f"{nodes}: separable part, worst |z - z_ref| / bound {worst:.3f}")
+
+
+def _boxes(nodes):
+    """-> list of index arrays (caller's column numbering), one per aligned box, each in the plan's INTERNAL column order (the
+    order in which the library factors a box: a Cholesky factor, and what rounding its inverse to float32 does, depends on it)."""
+    nd = len(nodes)
+    e = BOX_EDGE[nd]
+    ncol = int(np.prod(nodes))
+    stride = np.cumprod([1] + list(nodes[:-1]))
+    multi = np.stack([(np.arange(ncol) // stride[d]) % nodes[d] for d in range(nd)], axis=1)
+    nbd = [(n + e - 1) // e for n in nodes]
+    key = np.ravel_multi_index((multi // e).T, nbd)
+    order = _internal_order(nodes)
+    internal = np.ravel_multi_index(multi[:, order[::-1]].T, [nodes[d] for d in order[::-1]])      # internal dimension 0 fastest
+    out = []
+    for b in range(int(np.prod(nbd))):
+        S = np.nonzero(key == b)[0]
+        out.append(S[np.argsort(internal[S])])
+    return out
+
+
+ASSEMBLED_BOX_GRIDS = [[300], [64, 64], [17, 15], [300, 9], [16, 17, 15], [13, 8, 7], [6, 5, 7, 9], [7, 4, 6, 5]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nodes", ASSEMBLED_BOX_GRIDS, ids=lambda n: "x".join(map(str, n)))
+def test_boxes_cut_out_of_the_assembled_equations_solve_them(port, nodes, monkeypatch):
+    """part = 2 where the boxes are principal submatrices of the assembled N (from the oracle), per box, two vectors, against the
+    same solve on the host with its inverse Cholesky factor rounded to float32 and applied in double; a partial box (identity
+    padding interleaved with its nodes) against the host solve over its real columns alone.  Every box must give a non-zero z.
+
+    Two measures, each no more than 4 times the host emulation's own:
+      * the energy-norm residual ||L^T z - L^-1 r||_2 / ||L^-1 r||_2 (L the Cholesky factor of the oracle's N_box; the relative
+        A-norm distance to the exact box solve): EVERY box.  Storing L^-1 in float32 keeps it between 1e-6 and 2e-2 for these boxes
+        whatever their conditioning, z = 0 gives 1, and two equally valid double factors rounded to float32 differ in it by up to
+        2.9 (host experiment: N_box perturbed by 2e-16, three samples per box);
+      * ||N_box z - r||_inf, the issue's measure: the boxes whose float32 factor is DETERMINED, n u cond(N_box) <= 2^-24, so that
+        the library and the host round the same factor and differ in the order of a 256-term sum.  The boxes of these fits reach
+        cond 1e14 (constraint rows carry 1 / dx^4); there two backward-stable double factors agree to 1e-2, their float32 roundings
+        are unrelated samples and this residual is not reproducible: the library's was up to 6.6 times the host's ([300, 9], box 13),
+        on the host alone equally valid factors differ by up to 9.6.  No box of [300], [64, 64] and [300, 9] is determined (asserted
+        below, so that the list stays true); every other grid has at least one.
+    4-D: also the boxes built from the rows (rows-only and lazy fits), which are approximate by design: kept, positive, and
+    symmetric to 4 times what the host emulation of the assembled boxes shows for the same vectors."""
+    import scipy.linalg as sl
+    nd, ncol = len(nodes), int(np.prod(nodes))
+    inp = _precond_inputs(nodes)
+    ne = _oracle_ne(port, inp)
+    N = stencil_to_sparse(ne["N"], nodes)
+    boxes = _boxes(nodes)
+    partial = sum(1 for S in boxes if S.size < 256)
+    env = {"SPLPAK_SOLVER": "pcg", "SPLPAK_PCG_ASSEMBLE": "1"} if nd == 4 else {"SPLPAK_SOLVER": "pcg+direct", "SPLPAK_PCG_ALWAYS": "1"}
+    u, v = (np.random.default_rng(s).uniform(-1.0, 1.0, ncol) for s in (81, 82))
+    plan, ierr, info, coef = _fit_plan(inp, env, monkeypatch)
+    try:
+        assert ierr in (0, 107) and (info[0], info[1]) == (ne["data_rows"], ne["constraint_rows"])
+        zg = {"u": plan.precondition(u, 2), "v": plan.precondition(v, 2)}
+    finally:
+        plan.close()
+    worst, worst_ill, worst_q, q_max, same = 0.0, 0.0, 0.0, 0.0, 0
+    zh = {"u": np.zeros(ncol), "v": np.zeros(ncol)}
+    for b, S in enumerate(boxes):
+        Nb = N[S][:, S].toarray()
+        Lc = np.linalg.cholesky(Nb)
+        Li = sl.solve_triangular(Lc, np.eye(S.size), lower=True)
+        Li32 = Li.astype(np.float32).astype(np.float64)
+        determined = S.size * U53 * np.linalg.cond(Nb) <= 2.0 ** -24        # the double factor fixes its float32 rounding
+        same += int(determined)
+        for rname, r in (("u", u), ("v", v)):
+            assert zg[rname][S].any(), f"{nodes} box {b} ({S.size} nodes), vector {rname}: z is zero -- the fit dropped its boxes"
+            zb = Li32.T @ (Li32 @ r[S])
+            zh[rname][S] = zb
+            y = Li @ r[S]
+            q_h = float(np.linalg.norm(Lc.T @ zb - y) / np.linalg.norm(y))
+            q_g = float(np.linalg.norm(Lc.T @ zg[rname][S] - y) / np.linalg.norm(y))
+            worst_q, q_max = max(worst_q, q_g / q_h), max(q_max, q_g)
+            assert q_g <= 4.0 * q_h, (nodes, rname, b, S.size, q_g, q_h)
+            res_h = float(np.max(np.abs(Nb @ zb - r[S])))
+            res_g = float(np.max(np.abs(Nb @ zg[rname][S] - r[S])))
+            if determined:
+                worst = max(worst, res_g / res_h)
+                assert res_g <= 4.0 * res_h, (nodes, rname, b, S.size, res_g, res_h)
+            else:
+                worst_ill = max(worst_ill, res_g / res_h)
+    print(f"{nodes}: {len(boxes)} boxes ({partial} partial): energy-norm residual against the host float32 emulation at worst {worst_q:.2f} (4), itself up to "
+          f"{q_max:.1e}; {same} boxes with a determined float32 factor: ||N z - r||_inf against the emulation {worst:.2f} (4); the others {worst_ill:.2f} (not held to it)")
+    assert (same == 0) == (nodes in ([300], [64, 64], [300, 9])), (nodes, same)
+    if nd != 4:
+        return
+
+    def asym(zu, zv):
+        return abs(u @ zv - v @ zu) / np.sqrt((u @ zu) * (v @ zv))
+
+    ref = asym(zh["u"], zh["v"])
+    for env in ({"SPLPAK_SOLVER": "pcg"}, {"SPLPAK_SOLVER": "pcg+direct", "SPLPAK_PCG_ALWAYS": "1"}):
+        plan, ierr, info, coef = _fit_plan(inp, env, monkeypatch)
+        try:
+            assert ierr in (0, 107)
+            zu, zv = plan.precondition(u, 2), plan.precondition(v, 2)
+            assert zu.any() and zv.any(), "the fit dropped its boxes"
+            assert u @ zu > 0 and v @ zv > 0
+            got = asym(zu, zv)
+            print(f"{nodes} {env['SPLPAK_SOLVER']}: boxes from the rows, asymmetry {got:.2e} against {ref:.2e} of the host emulation (x 4)")
+            assert got <= 4.0 * ref
+        finally:
+            plan.close()
+
+
+@pytest.mark.gpu
+def test_boxes_from_the_rows_are_kept_and_positive_at_13_12_14_11(monkeypatch):
+    """(no oracle N at this size: kept and positive only)"""
+    nodes = [13, 12, 14, 11]
+    inp = _precond_inputs(nodes)
+    plan, ierr, info, coef = _fit_plan(inp, {"SPLPAK_SOLVER": "pcg"}, monkeypatch)
+    try:
+        assert ierr in (0, 107)
+        for seed in (81, 82):
+            r = np.random.default_rng(seed).uniform(-1.0, 1.0, int(np.prod(nodes)))
+            z = plan.precondition(r, 2)
+            assert z.any() and r @ z > 0
+    finally:
+        plan.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# GPU tier D
+def _host_pcg(N, Minv, b, tol, maxit):
+    """Textbook preconditioned conjugate gradients from a zero start; stops when sqrt(r.z / r0.z0) <= tol (pcg_solve's rule)."""
+    x = np.zeros_like(b)
+    r = b.copy()
+    z = Minv @ r
+    p = z.copy()
+    rz0 = rz = r @ z
+    for it in range(1, maxit + 1):
+        q = N @ p
+        alpha = rz / (p @ q)
+        x += alpha * p
+        r -= alpha * q
+        z = Minv @ r
+        rz_new = r @ z
+        if np.sqrt(rz_new / rz0) <= tol:
+            return x, it
+        p = z + (rz_new / rz) * p
+        rz = rz_new
+    return x, maxit
+
+
+# regimes in which DESIGN section 4c says the iteration works: no constraint rows, or two or more per column
+CG_CASES = [("2d_30_30_xtrap0", lambda: _seeded(2, [30, 30], 9000, 95, xtrap=0.0)),
+            ("3d_10_11_12", lambda: _seeded(3, [10, 11, 12], 1500, 96)),
+            ("4d_6_5_7_6", lambda: _seeded(4, [6, 5, 7, 6], 4000, 97))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,make", CG_CASES, ids=[c[0] for c in CG_CASES])
+def test_conjugate_gradient_loop_against_a_textbook_one(port, name, make, monkeypatch):
+    """The library's loop (one solve, refinement off) against textbook PCG in double on the host with the SAME operator pieces taken
+    from outside the loop: the dense M^-1 (unit vectors through splpak_debug_plan_precondition) and the oracle's N and rhs.  The
+    library tests its stopping rule every 5 iterations, so its count is the host's rounded up to a multiple of 5 (+ rounding): within
+    5, the margin test_forms_of_the_preconditioner_agree_with_the_factorisation grants two roundings of the same transform.  The
+    backward error of its unrefined coefficients against the oracle's N: no more than 10 times the host loop's own.  M^-1 N has a
+    positive spectrum and a smaller condition number than N."""
+    import torch
+    inp = make()
+    nodes = [int(n) for n in inp["nodes"]]
+    ncol = int(np.prod(nodes))
+    ne = _oracle_ne(port, inp)
+    N = stencil_to_sparse(ne["N"], nodes).toarray()
+    rpc = ne["constraint_rows"] / ncol
+    assert rpc == 0 or rpc >= 2.0, rpc
+    x, y, w = _tensors(inp)
+    monkeypatch.setenv("SPLPAK_SOLVER", "pcg")
+    plan = capi.Plan(inp["ndim"], inp["nodes"], inp["xmin"], inp["xmax"], inp["xtrap"], x.shape[0])
+    monkeypatch.delenv("SPLPAK_SOLVER")
+    try:
+        plan.set_refine(0, 1e-11)
+        coef = torch.zeros(ncol, dtype=torch.float64, device=x.device)
+        ierr, info = plan.fit(x, y, w, coef)
+        torch.cuda.synchronize()
+        assert ierr == 0, capi.last_error()
+        assert (info[0], info[1]) == (ne["data_rows"], ne["constraint_rows"]) and info[2] == 0
+        its = plan.pcg_stats()
+        assert its["solves"] == 1
+        Minv = np.empty((ncol, ncol))
+        e = np.zeros(ncol)
+        for j in range(ncol):
+            e[j] = 1.0
+            Minv[:, j] = plan.precondition(e, 0)
+            e[j] = 0.0
+    finally:
+        plan.close()
+    c_gpu = coef.cpu().numpy()
+    asym = float(np.max(np.abs(Minv - Minv.T)) / np.max(np.abs(Minv)))
+    c_host, it_host = _host_pcg(N, Minv, ne["rhs"], 1e-11, 20000)
+
+    def bwd(c):
+        return float(np.max(np.abs(ne["rhs"] - N @ c)) / (np.max(np.sum(np.abs(N), axis=1)) * np.max(np.abs(c)) + np.max(np.abs(ne["rhs"]))))
+
+    ev = np.linalg.eigvals(Minv @ N).real
+    evn = np.linalg.eigvalsh(N)
+    print(f"{name}: {ncol} columns, {rpc:.2f} constraint rows per column; iterations library {its['iterations']} / host {it_host}; backward error of the "
+          f"unrefined coefficients library {bwd(c_gpu):.2e} / host {bwd(c_host):.2e} (ratio {bwd(c_gpu) / bwd(c_host):.2f}, bar 10); M^-1 asymmetry {asym:.1e}; "
+          f"eigenvalues of M^-1 N in [{ev.min():.3e}, {ev.max():.3e}]: cond {ev.max() / ev.min():.2e} against cond(N) {evn.max() / evn.min():.2e}")
+    assert abs(its["iterations"] - it_host) <= 5
+    assert bwd(c_gpu) <= 10.0 * bwd(c_host)
+    assert ev.min() > 0 and evn.min() > 0
+    assert ev.max() / ev.min() <= evn.max() / evn.min()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# solver choice
+def _has_iteration(plan):
+    n = C.c_int32(0)
+    rc = capi.lib().splpak_debug_plan_pcg_tables(plan._h, 0, None, None, C.byref(n))
+    assert rc in (0, capi.E_UNSUPPORTED)
+    return rc == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nodes,code", [([8, 8, 8], None), ([20] * 4, 4), ([32] * 4, 6)], ids=["8x8x8", "20^4", "32^4"])
+def test_solver_unset_auto_and_empty_are_the_same_plan(nodes, code, monkeypatch):
+    """SPLPAK_SOLVER=auto (the documented value) and an empty value used to lose the out-of-memory fallback to the iteration:
+    BASELINE config 5's grid failed plan creation.  Only the 3-D grid also goes through a fit and its pcg_stats: a fit of 1 000 points
+    at 20^4 or 32^4 would say little for seconds of iteration, so there the presence of the iteration is read from the plan
+    (splpak_debug_plan_pcg_tables answers SPLPAK_E_UNSUPPORTED without it), beside the factorisation code and the plan's bytes."""
+    import torch
+    capi.shutdown()
+    torch.cuda.empty_cache()
+    nd = len(nodes)
+    seen = []
+    for value in (None, "auto", ""):
+        if value is None:
+            monkeypatch.delenv("SPLPAK_SOLVER", raising=False)
+        else:
+            monkeypatch.setenv("SPLPAK_SOLVER", value)
+        plan = capi.Plan(nd, nodes, [0.0] * nd, [1.0] * nd, 1.0, 1000)
+        try:
+            its = None
+            if nd == 3:            # a small grid: the presence of the iteration also through a fit's statistics
+                inp = _seeded(3, nodes, 1000, 91)
+                x, y, w = _tensors(inp)
+                coef = torch.zeros(plan.ncol, dtype=torch.float64, device=x.device)
+                ierr, _ = plan.fit(x, y, w, coef)
+                assert ierr == 0
+                its = plan.pcg_stats()["iterations"]
+            seen.append((plan.factorisation()[0], _has_iteration(plan), plan.device_bytes(), its))
+        finally:
+            plan.close()
+    print(f"{nodes}: (factorisation code, iteration, bytes, iterations of a fit) unset / auto / empty: {seen}")
+    assert seen[0] == seen[1] == seen[2]
+    if code is not None:
+        assert seen[0][0] == code
+    assert seen[0][1] == (nd == 4)
+
+
+@pytest.mark.gpu
+def test_long_thin_4d_grid_keeps_its_factorisation(port, monkeypatch):
+    """[513, 7, 7, 7]: 175 959 columns, so the plan would put the iteration in front of its factorisation -- and the iteration takes
+    at most 512 nodes per dimension.  Left to itself the plan keeps the factorisation alone; asked for the iteration by name it
+    is refused as before."""
+    import torch
+    nodes = [513, 7, 7, 7]
+    monkeypatch.delenv("SPLPAK_SOLVER", raising=False)
+    inp = _seeded(4, nodes, 200000, 92)
+    plan, ierr, info, coef = _fit_plan(inp, {}, monkeypatch)
+    try:
+        code, what = plan.factorisation()
+        assert code == 4, (code, what)
+        assert not _has_iteration(plan) and plan.pcg_stats()["iterations"] == 0
+        assert ierr == 0, capi.last_error()
+    finally:
+        plan.close()
+    omega, reserr, nrow, ncons = port.rows_gradient(*_args(inp), coef)
+    print(f"{nodes}: {what}; host backward error {omega:.2e} (1e-12), GPU {info[9]:.1e}; rows {nrow} + {ncons}")
+    assert omega < 1e-12
+    assert (nrow, ncons) == (info[0], info[1]) and abs(reserr - info[8]) <= 1e-9 * reserr
+    monkeypatch.setenv("SPLPAK_SOLVER", "pcg")
+    with pytest.raises(capi.SplpakError) as e:
+        capi.Plan(4, nodes, [0.0] * 4, [1.0] * 4, 1.0, 1000)
+    assert "-4" in str(e.value) and "more than 512 nodes in one dimension" in str(e.value)
