@@ -329,6 +329,44 @@ int32_t splpak_eval_derivs_dev_f64(int32_t ndim, int64_t nq, const double *xq_de
                                    const double *coef_dev, const double *xmin, const double *xmax,
                                    const int32_t *nodes, double *out_dev, int32_t ldout, void *stream);
 
+/* Evaluation on a tensor-product grid of points: replaces the loop of splfe (:1258) / splde (:1089) calls over a
+ * regular sample that resamples a fit into an image, a volume or a table.
+ *   axes   the axis coordinates back to back: the npts[0] coordinates of dimension 1, then the npts[1] of
+ *          dimension 2, ...; sum_d npts[d] values.  Any values: unsorted, repeated, outside [xmin, xmax] (the
+ *          reference extrapolates through its window rule, :1201-1209, and so does this).
+ *   out    prod_d npts[d] values, dimension 1 fastest -- out[i0 + npts[0]*(i1 + npts[1]*(i2 + ...))], the ordering
+ *          `coef` uses (:227-228) -- each what splde (splfe when nderiv == NULL) returns at
+ *          (axes_1[i0], axes_2[i1], ...): the very values splpak_eval_* computes for that point.
+ * No query list is formed and nothing is sorted: 8 bytes of device memory traffic per output (4 for REAL32) and the
+ * coefficients; output counts beyond 2^31 are fine.
+ * Status as splpak_eval_f64: 101/102/103 return without computing, `out` set to 0 (101 -- no dimensions, so no
+ * shape: out[0] alone); 104 (nderiv outside 0..2) is reported but the values are computed with nderiv clamped to
+ * 0..2 (:1190-1194).  SPLPAK_E_BADARG: a null pointer, a negative npts[d], a product of npts beyond int64;
+ * SPLPAK_E_UNSUPPORTED: ndim > 4.  If any npts[d] is 0 the validation status is returned and nothing is written.
+ * All of these are decided on the host before any device work. */
+int32_t splpak_eval_grid_f64(int32_t ndim, const int64_t *npts, const double *axes, const int32_t *nderiv,
+                             const double *coef, const double *xmin, const double *xmax, const int32_t *nodes,
+                             double *out);
+int32_t splpak_eval_grid_f32(int32_t ndim, const int64_t *npts, const float *axes, const int32_t *nderiv,
+                             const float *coef, const float *xmin, const float *xmax, const int32_t *nodes,
+                             float *out);
+/* the same on resident data (asynchronous on `stream`); npts, nderiv, xmin, xmax and nodes are host arrays */
+int32_t splpak_eval_grid_dev_f64(int32_t ndim, const int64_t *npts /* host */, const double *axes_dev,
+                                 const int32_t *nderiv /* host, may be NULL */, const double *coef_dev,
+                                 const double *xmin, const double *xmax, const int32_t *nodes,
+                                 double *out_dev, void *stream);
+int32_t splpak_eval_grid_dev_f32(int32_t ndim, const int64_t *npts /* host */, const float *axes_dev,
+                                 const int32_t *nderiv /* host, may be NULL */, const float *coef_dev,
+                                 const float *xmin, const float *xmax, const int32_t *nodes,
+                                 float *out_dev, void *stream);
+/* Device memory (bytes) a grid call of this shape keeps, per calling thread, until splpak_shutdown: the per-axis
+ * factor tables, 40 bytes per axis coordinate.  0 when a count is 0; SPLPAK_E_BADARG for a shape the entries reject. */
+int64_t splpak_eval_grid_scratch_bytes(int32_t ndim, const int64_t *npts);
+/* Diagnostics: how many workgroup tiles of the calling thread's last grid call contracted a coefficient box staged in
+ * LDS (out2[0]) and how many gathered every window from global memory (out2[1]: boxes beyond the LDS budget -- coarse
+ * or unsorted axes -- and every 1-D call).  Waits for that call.  Both forms return the same values. */
+int32_t splpak_debug_eval_grid_stats(int64_t out2[2]);
+
 /* Device-side synthetic inputs of SURVEY 8d (Park-Miller stream, seed 42):
  * points first_point .. first_point+ndata-1; any of the outputs may be NULL.
  * xdata_dev is written with leading dimension ndim.  Queries continue the stream

@@ -30,6 +30,8 @@ SYMBOLS = [
     "splpak_rccl_comm_create_from_file", "splpak_rccl_comm_create_from_file_ex", "splpak_rccl_comm_destroy", "splpak_plan_set_refine", "splpak_plan_fit_dev",
     "splpak_plan_hist_dev", "splpak_plan_factorisation", "splpak_plan_enable_kernel_timing", "splpak_plan_kernel_timing", "splpak_plan_stage_timing",
     "splpak_eval_dev_f64", "splpak_eval_dev_f32", "splpak_eval_derivs_f64", "splpak_eval_derivs_f32", "splpak_eval_derivs_dev_f64",
+    "splpak_eval_grid_f64", "splpak_eval_grid_f32", "splpak_eval_grid_dev_f64", "splpak_eval_grid_dev_f32",
+    "splpak_eval_grid_scratch_bytes", "splpak_debug_eval_grid_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
     "splpak_mplan_create", "splpak_mplan_destroy", "splpak_mplan_device", "splpak_mplan_rank_bytes", "splpak_mplan_factorisation", "splpak_mplan_fit_dev", "splpak_fit_multi_f64",
     "splpak_plan_device_bytes", "splpak_plan_pcg_stats", "splpak_set_default_option", "splpak_plan_set_option", "splpak_plan_get_option",
@@ -123,6 +125,19 @@ def lib() -> C.CDLL:
     L.splpak_eval_derivs_f32.argtypes = [i32, i64, _fp, i32, i32, _fp, _fp, _fp, _ip, _fp, i32]
     L.splpak_eval_derivs_dev_f64.restype = i32
     L.splpak_eval_derivs_dev_f64.argtypes = [i32, i64, vp, i32, i32, vp, _dp, _dp, _ip, vp, i32, vp]
+    _lp = C.POINTER(C.c_int64)
+    L.splpak_eval_grid_f64.restype = i32
+    L.splpak_eval_grid_f64.argtypes = [i32, _lp, _dp, _ip, _dp, _dp, _dp, _ip, _dp]
+    L.splpak_eval_grid_f32.restype = i32
+    L.splpak_eval_grid_f32.argtypes = [i32, _lp, _fp, _ip, _fp, _fp, _fp, _ip, _fp]
+    L.splpak_eval_grid_dev_f64.restype = i32
+    L.splpak_eval_grid_dev_f64.argtypes = [i32, _lp, vp, _ip, vp, _dp, _dp, _ip, vp, vp]
+    L.splpak_eval_grid_dev_f32.restype = i32
+    L.splpak_eval_grid_dev_f32.argtypes = [i32, _lp, vp, _ip, vp, _fp, _fp, _ip, vp, vp]
+    L.splpak_eval_grid_scratch_bytes.restype = i64
+    L.splpak_eval_grid_scratch_bytes.argtypes = [i32, _lp]
+    L.splpak_debug_eval_grid_stats.restype = i32
+    L.splpak_debug_eval_grid_stats.argtypes = [_lp]
     L.splpak_synth_points_f64.restype = i32
     L.splpak_synth_points_f64.argtypes = [i32, i64, i64, vp, vp, vp, vp]
     L.splpak_synth_queries_f64.restype = i32
@@ -354,6 +369,38 @@ def evaluate(ndim, xq, nderiv, coef, xmin, xmax, nodes, real32=False):
     rc = _check(fn(ndim, nq, _p(xq, rp), ldx, _p(nd, _ip), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
                    _p(nodes, _ip), _p(out, rp)))
     return out, rc
+
+
+def evaluate_grid(ndim, axes, nderiv, coef, xmin, xmax, nodes, real32=False):
+    """splde (nderiv given) / splfe (nderiv None) at every point of the tensor-product grid axes[0] x axes[1] x ...
+    `axes` is a list of `ndim` 1-D arrays (any order, repeats and points outside the grid allowed).
+    -> (values of shape (len(axes[ndim-1]), ..., len(axes[0])), C-ordered: the LAST index runs along dimension 1; ierror)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
+    npts = np.array([a.size for a in axes], dtype=np.int64)
+    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    coef = np.ascontiguousarray(coef, dtype=dt)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    out = np.zeros(tuple(int(n) for n in npts[::-1]), dtype=dt)
+    fn = lib().splpak_eval_grid_f32 if real32 else lib().splpak_eval_grid_f64
+    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, rp), _p(nd, _ip), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), _p(out, rp)))
+    return out, rc
+
+
+def eval_grid_scratch_bytes(npts) -> int:
+    """Bytes of per-thread device scratch a grid call of this shape keeps until shutdown()."""
+    npts = np.ascontiguousarray(npts, dtype=np.int64)
+    return _check(lib().splpak_eval_grid_scratch_bytes(int(npts.size), _p(npts, C.POINTER(C.c_int64))))
+
+
+def debug_eval_grid_stats():
+    """(tiles that took the LDS form, tiles that took the general form) in this thread's last grid call; waits for it."""
+    v = np.zeros(2, dtype=np.int64)
+    _check(lib().splpak_debug_eval_grid_stats(_p(v, C.POINTER(C.c_int64))))
+    return int(v[0]), int(v[1])
 
 
 def derivs_nout(ndim, order):
@@ -601,6 +648,24 @@ def evaluate_dev(ndim, xq, nderiv, coef, xmin, xmax, nodes, out, stream=0):
     return _check(lib().splpak_eval_dev_f64(ndim, int(nq), xq.data_ptr(), int(ldx), _p(nd, _ip),
                                             coef.data_ptr(), _p(xmin, _dp), _p(xmax, _dp),
                                             _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
+
+
+def evaluate_grid_dev(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, stream=0):
+    """Grid evaluation on torch device tensors (asynchronous on `stream`): `axes` holds the npts[0] coordinates of dimension 1,
+    then the npts[1] of dimension 2, ...; `out` has prod(npts) entries, dimension 1 fastest (a C-ordered tensor of shape
+    npts[::-1]).  float32 tensors take the REAL32 entry."""
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    npts = np.ascontiguousarray(npts, dtype=np.int64)
+    lp = C.POINTER(C.c_int64)
+    if str(axes.dtype).endswith("float32"):
+        xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32)
+        return _check(lib().splpak_eval_grid_dev_f32(ndim, _p(npts, lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
+                                                     _p(xmin, _fp), _p(xmax, _fp), _p(nodes, _ip), out.data_ptr(),
+                                                     C.c_void_p(stream)))
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes)
+    return _check(lib().splpak_eval_grid_dev_f64(ndim, _p(npts, lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
+                                                 _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), out.data_ptr(),
+                                                 C.c_void_p(stream)))
 
 
 EVAL_AUTO, EVAL_DIRECT, EVAL_BINNED = 0, 1, 2

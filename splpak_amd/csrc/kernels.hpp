@@ -24,6 +24,19 @@ void eval_scratch_shutdown();
 hipError_t launch_eval_f32(const Grid &g, long long nq, const float *xq, int ldxq, const int *nderiv,
                            const float *coef, float *out, hipStream_t st);
 
+// ---- evalgrid.hip
+// out[i0 + npts[0] (i1 + npts[1] (...))] = the value (nderiv: that partial derivative) at (axes_1[i0], axes_2[i1], ...);
+// axes = the npts[0] coordinates of dimension 1, then those of dimension 2, ...  (device pointers; npts, nderiv on the host)
+hipError_t launch_eval_grid(const Grid &g, const long long *npts, const double *axes, const int *nderiv,
+                            const double *coef, double *out, hipStream_t st);
+hipError_t launch_eval_grid_f32(const Grid &g, const long long *npts, const float *axes, const int *nderiv,
+                                const float *coef, float *out, hipStream_t st);
+// bytes of per-thread scratch a call with ntab = sum of npts keeps (factor tables, window starts, tile counters)
+long long eval_grid_scratch_bytes(long long ntab);
+// tiles of the calling thread's last call that took the LDS form [0] and the general form [1]
+hipError_t eval_grid_stats(long long out2[2]);
+void eval_grid_scratch_shutdown();
+
 // ---- synth.hip
 hipError_t launch_synth_points(int ndim, long long first, long long n, double *x, double *y,
                                double *w, hipStream_t st);

@@ -65,6 +65,7 @@ module splpak_module
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
+        procedure,public :: evaluate_grid => splpak_eval_grid       !! every point of a tensor-product grid of points (additive)
         procedure,public :: destroy       => destroy_splpak
         procedure,public :: last_fit_info => splpak_last_fit_info   !! reserr, row counts, ... of the last fit (additive)
         procedure,public,nopass :: set_option => splpak_set_option    !! a named option of the HIP library for the following fits (additive)
@@ -77,6 +78,7 @@ module splpak_module
         procedure,private :: splfe_many
         procedure,private :: splde_many
         procedure,private :: splpak_derivs_many
+        procedure,private :: splpak_eval_grid
     end type splpak_type
 
 #ifndef REAL128
@@ -118,6 +120,17 @@ module splpak_module
             integer(c_int64_t),value :: nq
             type(c_ptr),value :: xq, coef, xmin, xmax, nodes, out
         end function c_eval_derivs
+#ifdef REAL32
+        integer(c_int32_t) function c_eval_grid(ndim,npts,axes,nderiv,coef,xmin,xmax,nodes,out) &
+                                                bind(C,name='splpak_eval_grid_f32')
+#else
+        integer(c_int32_t) function c_eval_grid(ndim,npts,axes,nderiv,coef,xmin,xmax,nodes,out) &
+                                                bind(C,name='splpak_eval_grid_f64')
+#endif
+            import :: c_int32_t, c_ptr
+            integer(c_int32_t),value :: ndim
+            type(c_ptr),value :: npts, axes, nderiv, coef, xmin, xmax, nodes, out
+        end function c_eval_grid
 #ifndef REAL32
         integer(c_int32_t) function c_fit_multi(ngpus,ndim,xdata,l1xdat,ydata,wdata,ndata,xmin,xmax,nodes,xtrap,&
                                                 coef,ncf,nwrk,hist,info) bind(C,name='splpak_fit_multi_f64')
@@ -667,6 +680,90 @@ module splpak_module
             if (ierror < 0) call report_library_failure(ierror,'evaluate_derivatives')
         end select
     end subroutine splpak_derivs_many
+
+    !> Resampling a fit onto a grid: f(i1 + npts(1)*((i2-1) + npts(2)*((i3-1) + ...))) is the spline -- with `nderiv`, that
+    !! partial derivative -- at (axes_1(i1), axes_2(i2), ...), what a loop of `evaluate` calls over a regular sample
+    !! returns (splfe :1258, splde :1089).  `axes` holds the npts(1) coordinates of dimension 1, then the npts(2) of
+    !! dimension 2, ... (any order, repeats and points outside the grid allowed); `f` has product(npts) entries, dimension 1
+    !! fastest, the ordering of `coef`.  One call of the HIP library (splpak_eval_grid_f64: no point list is formed);
+    !! under set_host(.true.), for ndim > 4 or with SPLPAK_HOST_IF_NO_GPU=1 a loop over the module's scalar evaluation,
+    !! as in evaluate_many.  ierror: 101..104 as splde (104: computed with nderiv clamped), -3 for a negative npts.
+    subroutine splpak_eval_grid(me,ndim,npts,axes,coef,xmin,xmax,nodes,f,ierror,nderiv)
+        class(splpak_type),intent(inout) :: me
+        integer,intent(in) :: ndim
+        integer,intent(in) :: npts(*)
+        real(wp),intent(in),target :: axes(*)
+        real(wp),intent(in),target :: coef(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(out),target :: f(*)
+        integer,intent(out) :: ierror
+        integer,intent(in),optional,target :: nderiv(*)
+        integer(c_int32_t) :: rc
+        integer(c_int64_t),target :: np64(max(ndim,1))
+        integer(c_int64_t) :: iq, nq
+        integer :: idim, ie, nder(max(ndim,1)), k(max(ndim,1)), off(max(ndim,1))
+        real(wp) :: x(max(ndim,1))
+        type(c_ptr) :: pd
+        me%mdim = ndim
+        rc = 0
+        np64 = 0
+        do idim = 1, ndim
+            np64(idim) = int(npts(idim),c_int64_t)
+        end do
+        pd = c_null_ptr
+        if (present(nderiv)) pd = c_loc(nderiv)
+#ifndef REAL128
+        if (.not. (host_takes(me,ndim) .and. ndim >= 1)) &
+            rc = c_eval_grid(int(ndim,c_int32_t), c_loc(np64), c_loc(axes), pd, c_loc(coef), c_loc(xmin), c_loc(xmax), &
+                             c_loc(nodes), c_loc(f))
+#endif
+        if ((host_takes(me,ndim) .or. host_if_no_gpu(int(rc))) .and. ndim >= 1) then   ! host solver: a loop over the scalar evaluation
+            ierror = 0
+            nq = 1
+            do idim = 1, ndim
+                if (npts(idim) < 0) then
+                    ierror = -3
+                    call report(ierror,' evaluate_grid - NPTS(IDIM) is negative for some IDIM')
+                    return
+                end if
+                off(idim) = int(sum(np64(1:idim-1)))
+                nq = nq*np64(idim)
+            end do
+            nder = 0
+            if (present(nderiv)) nder = nderiv(1:ndim)
+            k = 1
+            do iq = 1, nq
+                do idim = 1, ndim
+                    x(idim) = axes(off(idim) + k(idim))
+                end do
+                f(iq) = eval_point(me,ndim,x,nder,coef,xmin,xmax,nodes,ie)
+                if (ie /= 0) ierror = ie
+                if (ie /= 0 .and. ie /= 104) return
+                idim = 1                                    ! odometer, first dimension fastest
+                do while (idim <= ndim)
+                    k(idim) = k(idim) + 1
+                    if (k(idim) <= npts(idim)) exit
+                    k(idim) = 1
+                    idim = idim + 1
+                end do
+            end do
+            return
+        end if
+#ifdef REAL128
+        rc = -1
+#endif
+        ierror = int(rc)
+        select case (ierror)
+        case (0)
+        case (101); call report(ierror,' splfe or splde - NDIM is less than 1')
+        case (102); call report(ierror,' splfe or splde - NODES(IDIM) is less than  4for some IDIM')
+        case (103); call report(ierror,' splfe or splde - XMIN(IDIM) = XMAX(IDIM) for some IDIM')
+        case (104); call report(ierror,' splde - NDERIV(IDIM) IS less than 0 or greater than 2 for some IDIM')
+        case default
+            if (ierror < 0) call report_library_failure(ierror,'evaluate_grid')
+        end select
+    end subroutine splpak_eval_grid
 
     subroutine eval_common(me,ndim,nq,x,ldx,nderiv,coef,xmin,xmax,nodes,f,ierror)
         class(splpak_type),intent(inout) :: me
