@@ -1,0 +1,371 @@
+// The evaluation entries of the C ABI (include/splpak_hip.h): point, derivative and grid evaluation on host and device
+// pointers, the evaluation mode, and the host-only / synthetic-data helpers that need no plan.
+//
+// Every entry family has ONE ladder of argument checks (point_validate for the value and the derivative entries,
+// grid_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
+// Where two entries of a family have always answered differently, the difference is a named parameter of the ladder.
+#include "plan.hpp"
+#include "basis.hpp"
+
+#include <cstdio>
+#include <vector>
+
+using namespace splpak;
+
+// returns 0/101/102/103/104 exactly like splde's checks (:1166-1194)
+static int eval_validate(int32_t ndim, const int32_t *nderiv, const double *xmin, const double *xmax,
+                         const int32_t *nodes, Grid &g)
+{
+    int v = build_grid(ndim, nodes, xmin, xmax, g, nullptr);
+    if (v != 0) return v;
+    if (nderiv)
+        for (int d = 0; d < ndim; ++d)
+            if (nderiv[d] < 0 || nderiv[d] > 2) v = 104;
+    return v;
+}
+
+// device copies of a host entry's arrays: freed when the entry returns
+struct DevStage {
+    std::vector<void *> owned;
+    ~DevStage() { for (void *q : owned) (void)hipFree(q); }
+    template <typename T> bool alloc(T **ptr, size_t count)
+    {
+        void *q = nullptr;
+        if (count == 0) count = 1;
+        hipError_t e = hipMalloc(&q, count * sizeof(T));
+        if (e != hipSuccess && release_cached_plan_for_memory()) {      // the one-shot fit's cached plan (35 GB at 64^3) is in the way
+            (void)hipGetLastError();
+            e = hipMalloc(&q, count * sizeof(T));
+        }
+        if (e != hipSuccess) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "hipMalloc of %.3f GB failed: %s", (double)(count * sizeof(T)) / 1e9, hipGetErrorString(e));
+            set_error(buf);
+            (void)hipGetLastError();
+            return false;
+        }
+        owned.push_back(q);
+        *ptr = static_cast<T *>(q);
+        return true;
+    }
+};
+
+// A host entry after its checks: in (n_in) and coef (ncol) go to the device, launch(in, coef, out) runs on the null stream,
+// out (n_out; cleared first when `clear`) comes back.  rc = the status to return when all of that went well.
+template <typename T, typename F>
+static int32_t staged_call(const T *in, size_t n_in, const T *coef, size_t ncol, T *out, size_t n_out, bool clear, const char *what,
+                           int rc, F &&launch)
+{
+    DevStage stage;
+    T *din = nullptr, *dc = nullptr, *dout = nullptr;
+    if (!stage.alloc(&din, n_in) || !stage.alloc(&dc, ncol) || !stage.alloc(&dout, n_out)) return SPLPAK_E_NOMEM;
+    hipError_t e = hipMemcpy(din, in, sizeof(T) * n_in, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * ncol, hipMemcpyHostToDevice);
+    if (e == hipSuccess && clear) e = hipMemset(dout, 0, sizeof(T) * n_out);
+    if (e == hipSuccess) e = launch((const T *)din, (const T *)dc, dout);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(T) * n_out, hipMemcpyDeviceToHost);
+    return hip_ok(e, what) ? rc : SPLPAK_E_NODEVICE;
+}
+
+// the grid arguments every ladder starts with: the null checks, ndim in 1 .. MAXD, the limits widened to double.
+// zero_101: how many outputs to zero on ndim < 1.  Only splpak_eval_dev_f64 and splpak_eval_derivs_dev_f64 (all of them: they
+// took their 101 from the grid check, which zeroes) and the grid entries (the one output of the empty product) have ever done so.
+template <typename T>
+static bool grid_args(int32_t ndim, const T *xmin_t, const T *xmax_t, const int32_t *nodes, long long zero_101,
+                      double (&xmin)[MAXD], double (&xmax)[MAXD], int &rc, long long &zero_n)
+{
+    zero_n = 0;
+    if (!nodes || !xmin_t || !xmax_t) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (ndim < 1) { rc = 101; zero_n = zero_101; return false; }
+    if (ndim > MAXD) { rc = SPLPAK_E_UNSUPPORTED; return false; }
+    for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_t[d]; xmax[d] = (double)xmax_t[d]; }
+    return true;
+}
+
+// ---- evaluation at a list of points: one nderiv pattern (the value entries: ldout 1) or, `derivs`, value + gradient
+// (+ Hessian) of order 1 / 2 (the derivative entries: no nderiv) ----
+static int derivs_nout(int ndim, int order) { return 1 + ndim + (order == 2 ? ndim * (ndim + 1) / 2 : 0); }
+
+// The checks of a point entry before it touches a device.  True: the caller goes on to compute and returns rc (0 or 104)
+// afterwards; false: rc is the status to return and zero_n the outputs to zero first (102 / 103: all nq * ldout of them).
+// A bad nderiv (104) does not end the ladder: the call is evaluated with the orders clamped, as splde's callers get it.
+// The derivative entries check order, ldxq and ldout BEFORE they look at nq; the value entries look at ldxq only when
+// there are queries, after the null checks.
+template <typename T>
+static bool point_validate(bool derivs, int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, const int32_t *nderiv, int32_t order, const T *coef,
+                           const T *xmin_t, const T *xmax_t, const int32_t *nodes, const T *out, int32_t ldout, bool zero_101, Grid &g,
+                           int &rc, long long &zero_n)
+{
+    const long long nzero = ldout > 0 ? (long long)nq * ldout : 0;
+    double xmin[MAXD], xmax[MAXD];
+    if (!grid_args(ndim, xmin_t, xmax_t, nodes, zero_101 ? nzero : 0, xmin, xmax, rc, zero_n)) return false;
+    rc = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
+    if (rc != 0 && rc != 104) {
+        if (rc > 0) zero_n = nzero;
+        return false;
+    }
+    if (derivs) {
+        if (order < 1 || order > 2) { set_error("order must be 1 (gradient) or 2 (gradient and Hessian)"); rc = SPLPAK_E_BADARG; return false; }
+        if (ldxq < ndim || ldout < derivs_nout(ndim, order)) { set_error("ldxq or ldout too small"); rc = SPLPAK_E_BADARG; return false; }
+    }
+    if (nq <= 0) return false;
+    if (!xq || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (ldxq < ndim) { set_error("ldxq smaller than ndim"); rc = SPLPAK_E_BADARG; return false; }
+    if (int r = device_ready()) { rc = r; return false; }
+    return true;
+}
+
+template <typename T>
+static int32_t eval_dev(bool derivs, int32_t ndim, int64_t nq, const T *xq_dev, int32_t ldxq, const int32_t *nderiv, int32_t order, const T *coef_dev,
+                        const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, int32_t ldout, void *stream, bool zero_101)
+{
+    Grid g;
+    int rc = 0;
+    long long zero_n = 0;
+    if (!point_validate(derivs, ndim, nq, xq_dev, ldxq, nderiv, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, zero_101, g, rc, zero_n)) {
+        if (zero_n > 0 && out_dev) (void)hipMemsetAsync(out_dev, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
+        return rc;
+    }
+    SPLPAK_HIP_TRY(!derivs ? launch_eval<T>(g, nq, xq_dev, ldxq, nderiv, coef_dev, out_dev, (hipStream_t)stream)
+                              : launch_eval_derivs<T>(g, nq, xq_dev, ldxq, order, coef_dev, out_dev, ldout, (hipStream_t)stream),
+                   SPLPAK_E_NODEVICE);
+    return rc;
+}
+
+template <typename T>
+static int32_t eval_host(bool derivs, int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, const int32_t *nderiv, int32_t order, const T *coef,
+                         const T *xmin, const T *xmax, const int32_t *nodes, T *out, int32_t ldout)
+{
+    Grid g;
+    int rc = 0;
+    long long zero_n = 0;
+    if (!point_validate(derivs, ndim, nq, xq, ldxq, nderiv, order, coef, xmin, xmax, nodes, out, ldout, /*zero_101=*/false, g, rc, zero_n)) {
+        if (out) for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
+        return rc;
+    }
+    return staged_call<T>(xq, (size_t)nq * ldxq, coef, (size_t)g.ncol, out, (size_t)nq * ldout, derivs, "evaluation", rc,
+                          [&](const T *dq, const T *dc, T *dout) {
+                              return !derivs ? launch_eval<T>(g, nq, dq, ldxq, nderiv, dc, dout, nullptr)
+                                                : launch_eval_derivs<T>(g, nq, dq, ldxq, order, dc, dout, ldout, nullptr);
+                          });
+}
+
+extern "C" {
+
+int32_t splpak_eval_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq, const int32_t *nderiv, const double *coef,
+                        const double *xmin, const double *xmax, const int32_t *nodes, double *out)
+{
+    return eval_host<double>(false, ndim, nq, xq, ldxq, nderiv, 0, coef, xmin, xmax, nodes, out, 1);
+}
+
+int32_t splpak_eval_f32(int32_t ndim, int64_t nq, const float *xq, int32_t ldxq, const int32_t *nderiv, const float *coef,
+                        const float *xmin, const float *xmax, const int32_t *nodes, float *out)
+{
+    return eval_host<float>(false, ndim, nq, xq, ldxq, nderiv, 0, coef, xmin, xmax, nodes, out, 1);
+}
+
+int32_t splpak_eval_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq, const int32_t *nderiv, const double *coef_dev,
+                            const double *xmin, const double *xmax, const int32_t *nodes, double *out_dev, void *stream)
+{
+    return eval_dev<double>(false, ndim, nq, xq_dev, ldxq, nderiv, 0, coef_dev, xmin, xmax, nodes, out_dev, 1, stream, /*zero_101=*/true);
+}
+
+int32_t splpak_eval_dev_f32(int32_t ndim, int64_t nq, const float *xq_dev, int32_t ldxq, const int32_t *nderiv, const float *coef_dev,
+                            const float *xmin, const float *xmax, const int32_t *nodes, float *out_dev, void *stream)
+{
+    return eval_dev<float>(false, ndim, nq, xq_dev, ldxq, nderiv, 0, coef_dev, xmin, xmax, nodes, out_dev, 1, stream, /*zero_101=*/false);
+}
+
+int32_t splpak_eval_derivs_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq, int32_t order, const double *coef,
+                               const double *xmin, const double *xmax, const int32_t *nodes, double *out, int32_t ldout)
+{
+    return eval_host<double>(true, ndim, nq, xq, ldxq, nullptr, order, coef, xmin, xmax, nodes, out, ldout);
+}
+
+int32_t splpak_eval_derivs_f32(int32_t ndim, int64_t nq, const float *xq, int32_t ldxq, int32_t order, const float *coef,
+                               const float *xmin, const float *xmax, const int32_t *nodes, float *out, int32_t ldout)
+{
+    return eval_host<float>(true, ndim, nq, xq, ldxq, nullptr, order, coef, xmin, xmax, nodes, out, ldout);
+}
+
+int32_t splpak_eval_derivs_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq, int32_t order, const double *coef_dev,
+                                   const double *xmin, const double *xmax, const int32_t *nodes, double *out_dev, int32_t ldout,
+                                   void *stream)
+{
+    return eval_dev<double>(true, ndim, nq, xq_dev, ldxq, nullptr, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, stream, /*zero_101=*/true);
+}
+
+}  // extern "C"
+
+// ---- evaluation on a tensor-product grid of points (evalgrid.hip) ----
+// outputs and table entries of a grid call; false: a negative count or a product beyond int64
+static bool grid_counts(int32_t ndim, const int64_t *npts, long long &nout, long long &ntab)
+{
+    nout = 1;
+    ntab = 0;
+    bool zero = false;
+    for (int d = 0; d < ndim; ++d) {
+        if (npts[d] < 0) return false;
+        zero = zero || npts[d] == 0;
+        if (__builtin_add_overflow(ntab, (long long)npts[d], &ntab)) return false;
+    }
+    if (zero) { nout = 0; return true; }
+    for (int d = 0; d < ndim; ++d)
+        if (__builtin_mul_overflow(nout, (long long)npts[d], &nout)) return false;
+    return true;
+}
+
+// The checks every grid entry makes before it touches a device, in the order of eval_host / splpak_eval_dev_f64.
+// Returns true when the caller goes on to compute (rc = 0 or 104); otherwise rc is the status to return and
+// zero_n the outputs to zero first (101: the empty product, one output; 102 / 103: all of them).
+template <typename T>
+static bool grid_validate(int32_t ndim, const int64_t *npts, const T *axes, const int32_t *nderiv, const T *coef,
+                          const T *xmin_t, const T *xmax_t, const int32_t *nodes, const T *out, Grid &g, long long &nout,
+                          int &rc, long long &zero_n)
+{
+    nout = 0;
+    zero_n = 0;
+    if (!npts) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    double xmin[MAXD], xmax[MAXD];
+    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, xmin, xmax, rc, zero_n)) return false;
+    long long ntab = 0;
+    if (!grid_counts(ndim, npts, nout, ntab)) {
+        set_error("negative npts, or an output count beyond int64");
+        rc = SPLPAK_E_BADARG;
+        return false;
+    }
+    rc = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
+    if (rc != 0 && rc != 104) {
+        if (rc > 0 && out) zero_n = nout;
+        return false;
+    }
+    if (nout == 0) return false;
+    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (int r = device_ready()) { rc = r; return false; }
+    return true;
+}
+
+template <typename T>
+static int32_t eval_grid_dev(int32_t ndim, const int64_t *npts, const T *axes_dev, const int32_t *nderiv, const T *coef_dev,
+                             const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, void *stream)
+{
+    Grid g;
+    long long nout = 0, zero_n = 0;
+    int rc = 0;
+    if (!grid_validate(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, g, nout, rc, zero_n)) {
+        if (zero_n > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
+        return rc;
+    }
+    SPLPAK_HIP_TRY(launch_eval_grid<T>(g, npts, axes_dev, nderiv, coef_dev, out_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
+    return rc;
+}
+
+template <typename T>
+static int32_t eval_grid_host(int32_t ndim, const int64_t *npts, const T *axes, const int32_t *nderiv, const T *coef,
+                              const T *xmin, const T *xmax, const int32_t *nodes, T *out)
+{
+    Grid g;
+    long long nout = 0, zero_n = 0;
+    int rc = 0;
+    if (!grid_validate(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, g, nout, rc, zero_n)) {
+        for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
+        return rc;
+    }
+    long long ntab = 0;
+    for (int d = 0; d < ndim; ++d) ntab += npts[d];
+    return staged_call<T>(axes, (size_t)ntab, coef, (size_t)g.ncol, out, (size_t)nout, false, "grid evaluation", rc,
+                          [&](const T *da, const T *dc, T *dout) { return launch_eval_grid<T>(g, npts, da, nderiv, dc, dout, nullptr); });
+}
+
+extern "C" {
+
+int32_t splpak_eval_grid_f64(int32_t ndim, const int64_t *npts, const double *axes, const int32_t *nderiv,
+                             const double *coef, const double *xmin, const double *xmax, const int32_t *nodes, double *out)
+{
+    return eval_grid_host<double>(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out);
+}
+
+int32_t splpak_eval_grid_f32(int32_t ndim, const int64_t *npts, const float *axes, const int32_t *nderiv,
+                             const float *coef, const float *xmin, const float *xmax, const int32_t *nodes, float *out)
+{
+    return eval_grid_host<float>(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out);
+}
+
+int32_t splpak_eval_grid_dev_f64(int32_t ndim, const int64_t *npts, const double *axes_dev, const int32_t *nderiv,
+                                 const double *coef_dev, const double *xmin, const double *xmax, const int32_t *nodes,
+                                 double *out_dev, void *stream)
+{
+    return eval_grid_dev<double>(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, stream);
+}
+
+int32_t splpak_eval_grid_dev_f32(int32_t ndim, const int64_t *npts, const float *axes_dev, const int32_t *nderiv,
+                                 const float *coef_dev, const float *xmin, const float *xmax, const int32_t *nodes,
+                                 float *out_dev, void *stream)
+{
+    return eval_grid_dev<float>(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, stream);
+}
+
+int64_t splpak_eval_grid_scratch_bytes(int32_t ndim, const int64_t *npts)
+{
+    long long nout = 0, ntab = 0;
+    if (!npts || ndim < 1 || ndim > MAXD || !grid_counts(ndim, npts, nout, ntab)) { set_error("bad grid shape"); return SPLPAK_E_BADARG; }
+    return nout == 0 ? 0 : eval_grid_scratch_bytes(ntab);
+}
+
+int32_t splpak_debug_eval_grid_stats(int64_t out2[2])
+{
+    if (!out2) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    out2[0] = out2[1] = 0;
+    if (int r = device_ready()) return r;
+    long long v[2];
+    SPLPAK_HIP_TRY(eval_grid_stats(v), SPLPAK_E_NODEVICE);
+    out2[0] = v[0];
+    out2[1] = v[1];
+    return 0;
+}
+
+int32_t splpak_synth_points_f64(int32_t ndim, int64_t first_point, int64_t ndata, double *xdata_dev,
+                                double *ydata_dev, double *wdata_dev, void *stream)
+{
+    if (ndim < 1 || ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
+    if (int r = device_ready()) return r;
+    SPLPAK_HIP_TRY(launch_synth_points(ndim, first_point, ndata, xdata_dev, ydata_dev, wdata_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
+    return 0;
+}
+
+int32_t splpak_synth_queries_f64(int32_t ndim, int64_t ndata_before, int64_t first_query, int64_t nq,
+                                 double *xq_dev, void *stream)
+{
+    if (ndim < 1 || ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
+    if (int r = device_ready()) return r;
+    const long long skip = (long long)ndata_before * (ndim + 2) + (long long)first_query * ndim;
+    SPLPAK_HIP_TRY(launch_synth_queries(ndim, skip, nq, xq_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
+    return 0;
+}
+
+int32_t splpak_set_eval_mode(int32_t mode, int64_t chunk)
+{
+    if (mode < 0 || mode > 2 || chunk < 0) { set_error("bad evaluation mode"); return SPLPAK_E_BADARG; }
+    set_eval_mode(mode, chunk);
+    return 0;
+}
+
+// host only: the 4-entry value table of a 1-D grid at n points, as the evaluation kernels select it and in the general form
+int32_t splpak_debug_window_values(int32_t nodes, double xmin, double xmax, int64_t n, const double *x, int32_t *ws_out,
+                                   double *used4, double *general4, int32_t *form_out)
+{
+    if (!x || !ws_out || !used4 || !general4 || !form_out || n < 0) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    Grid g;
+    const int v = build_grid(1, &nodes, &xmin, &xmax, g, nullptr);
+    if (v != 0) return v;
+    for (int64_t i = 0; i < n; ++i) {
+        int form = 0;
+        ws_out[i] = window_table_selected(g, 0, x[i], used4 + 4 * i, form);
+        form_out[i] = form;
+        const int wg = window_table_value(g, 0, x[i], general4 + 4 * i);
+        if (wg != ws_out[i]) { set_error("window starts of the two forms differ"); return SPLPAK_E_BADARG; }
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,12 +1,29 @@
 // Device functions every evaluation kernel shares: the per-dimension factor table of a coordinate and the
 // factorised sum over the 4^D window.  One definition, so that the direct, the sorted and the grid kernels
-// (eval.hip, evalgrid.hip) return identical bits for the same point.
+// (eval.hip, evalsort.hip, evalruns.hip, evalregion.hip, evalgrid.hip) return identical bits for the same point.
 #pragma once
 #include "basis.hpp"
 
 namespace splpak {
 
 struct NDeriv { int v[MAXD]; };
+// the pattern a call evaluates: orders outside 0 .. 2 are clamped (the entries report them as 104), dimensions beyond ndim are 0
+inline NDeriv clamp_nderiv(const int *nderiv, int ndim)
+{
+    NDeriv nd;
+    for (int d = 0; d < MAXD; ++d) {
+        const int v = (nderiv && d < ndim) ? nderiv[d] : 0;
+        nd.v[d] = v < 0 ? 0 : (v > 2 ? 2 : v);
+    }
+    return nd;
+}
+// no derivative in any dimension: the kernels take the branch-free value form of the factor tables (eval_table<true>)
+inline bool value_only(const NDeriv &nd)
+{
+    bool v = true;
+    for (int d = 0; d < MAXD; ++d) v = v && nd.v[d] == 0;
+    return v;
+}
 
 // Sum of the 4^D window products, factorised: the innermost dimension is contracted with its four
 // factors first, then the partial sums with the factors of the next dimension, and so on -- 64 + 16 + 4
@@ -92,6 +109,89 @@ __device__ inline int eval_table(const Grid &g, int d, double x, int nder, doubl
         return ws;
     } else {
         return window_table(g, d, x, nder, b);
+    }
+}
+
+
+// ---- fused value + gradient (+ Hessian) ------------------------------------------------------------
+// all derivative patterns of total order <= ORDER from ONE pass over the window, instead
+// of one splde call (:1089-1240) per pattern.  Output per query, ldout apart:
+//   [ f, df/dx_1 .. df/dx_D, (ORDER 2:) d2f/dx_1dx_1, d2f/dx_1dx_2, .., d2f/dx_1dx_D, d2f/dx_2dx_2, .. ]
+// Each entry is the reference's sum  sum_window coef * prod_d bas1(nderiv_d; x_d)  for its nderiv
+// pattern; the 1-D factors come from the same window_table as everywhere else.
+// acc[*] for one query from its factor tables b[a][d][k] (a = derivative order) and a loader of window
+// rows: load4(k, c) delivers the 4 coefficients (k_0 = 0..3) of the row with window indices k[1..D-1].
+// Shared by the direct and the binned kernel: identical bits.
+template <int D, int ORDER, typename L4>
+__device__ inline void derivs_accumulate(const double (&b)[ORDER + 1][D][4], L4 &&load4,
+                                         double (&acc)[1 + D + (ORDER == 2 ? D * (D + 1) / 2 : 0)])
+{
+    constexpr int NOUT = 1 + D + (ORDER == 2 ? D * (D + 1) / 2 : 0);
+#pragma unroll
+    for (int j = 0; j < NOUT; ++j) acc[j] = 0.0;
+    // window rows (k_0 = 0..3 contiguous): contract dimension 1 with its value / first / second
+    // derivative factors first, then combine with the factors of the other dimensions
+    constexpr int NROW = D == 1 ? 1 : (D == 2 ? 4 : (D == 3 ? 16 : 64));
+    for (int e = 0; e < NROW; ++e) {
+        int k[D];
+        k[0] = 0;
+#pragma unroll
+        for (int d = 1; d < D; ++d) k[d] = (e >> (2 * (d - 1))) & 3;
+        double c[4];
+        load4(k, c);
+        double r[ORDER + 1];                  // r[a] = sum_k0 c[k0] * (a-th derivative factor of dim 1)
+#pragma unroll
+        for (int a = 0; a <= ORDER; ++a) {
+            double t = 0.0;
+#pragma unroll
+            for (int k0 = 0; k0 < 4; ++k0) t = fma(c[k0], b[a][0][k0], t);
+            r[a] = t;
+        }
+        double v0[D], v1[D], pex[D];          // dims >= 1: pex[d] = prod_{f >= 1, f != d} v0[f]
+        double full = 1.0;                    // prod_{f >= 1} v0[f]
+        v0[0] = v1[0] = pex[0] = 1.0;
+#pragma unroll
+        for (int d = 1; d < D; ++d) {
+            v0[d] = b[0][d][k[d]];
+            v1[d] = b[1][d][k[d]];
+            full *= v0[d];
+        }
+#pragma unroll
+        for (int d = 1; d < D; ++d) {
+            double pd = 1.0;
+#pragma unroll
+            for (int f = 1; f < D; ++f)
+                if (f != d) pd *= v0[f];
+            pex[d] = pd;
+        }
+        acc[0] = fma(r[0], full, acc[0]);
+        acc[1] = fma(r[1], full, acc[1]);
+#pragma unroll
+        for (int d = 1; d < D; ++d) acc[1 + d] = fma(r[0], v1[d] * pex[d], acc[1 + d]);
+        if constexpr (ORDER == 2) {
+            int j = 1 + D;
+#pragma unroll
+            for (int d = 0; d < D; ++d)
+#pragma unroll
+                for (int f = d; f < D; ++f) {
+                    double term;
+                    if (d == 0 && f == 0) {
+                        term = r[2] * full;
+                    } else if (d == 0) {
+                        term = r[1] * (v1[f] * pex[f]);
+                    } else if (f == d) {
+                        term = r[0] * (b[2][d][k[d]] * pex[d]);
+                    } else {
+                        double pdf = 1.0;
+#pragma unroll
+                        for (int h = 1; h < D; ++h)
+                            if (h != d && h != f) pdf *= v0[h];
+                        term = r[0] * (v1[d] * v1[f] * pdf);
+                    }
+                    acc[j] += term;
+                    ++j;
+                }
+        }
     }
 }
 

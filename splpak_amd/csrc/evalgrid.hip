@@ -2,7 +2,7 @@
 // derivative) at (axes_1[i0], axes_2[i1], ...), what a loop of splfe / splde calls over a regular sample
 // computes (src/splpak.F90:1089-1240, :1258-1275).
 //
-// The point route (eval.hip) takes the Cartesian product as a query list: 8 ndim bytes in per output, a sort
+// The point route (eval.hip and the sorted paths behind it) takes the Cartesian product as a query list: 8 ndim bytes in per output, a sort
 // by region although a grid is ordered, and the same ndim factor tables once per output.  Here:
 //
 //   grid_table_kernel   one thread per AXIS coordinate: window start + the four factors of that coordinate,
@@ -28,9 +28,8 @@
 // HBM traffic by construction: 8 bytes per output (4 for REAL32) + the coefficient boxes (each coefficient is
 // read by the tiles whose boxes hold it, from L2 after the first) + the tables.  Output counts are 64-bit;
 // coefficient indices stay int as in Grid.
-#include "basis.hpp"
 #include "evalcore.hpp"
-#include "kernels.hpp"
+#include "evalscratch.hpp"
 #include <climits>
 
 namespace splpak {
@@ -275,43 +274,28 @@ eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-namespace {
-// per-thread scratch: the tables and the two tile counters of the last call; kept until splpak_shutdown
-struct GScratch {
-    void *buf = nullptr;
-    long long cap = 0;             // table entries the buffer holds
-    hipEvent_t last = nullptr;     // end of the last call that used the buffer (another stream must wait for it)
-    bool used = false;
-};
-thread_local GScratch g_gscratch;
-}  // namespace
+// per-thread scratch (evalscratch.hpp): tile counters | factors [ntab][4] | window starts [ntab] of the last call
+static thread_local DevScratch<1> g_gscratch;
 
 long long eval_grid_scratch_bytes(long long ntab) { return 40 * ntab + 16; }      // 32 (factors) + 4 (start), rounded; counters
 
-void eval_grid_scratch_shutdown()
-{
-    GScratch &s = g_gscratch;
-    if (s.buf) (void)hipFree(s.buf);
-    if (s.last) (void)hipEventDestroy(s.last);
-    s = GScratch();
-}
+void eval_grid_scratch_shutdown() { g_gscratch.release(); }
 
 hipError_t eval_grid_stats(long long out2[2])
 {
-    GScratch &s = g_gscratch;
+    DevScratch<1> &s = g_gscratch;
     out2[0] = out2[1] = 0;
-    if (!s.buf || !s.used) return hipSuccess;
+    if (!s.buf[0] || !s.used) return hipSuccess;
     if (hipError_t e = hipEventSynchronize(s.last); e != hipSuccess) return e;
     unsigned long long v[2];
-    if (hipError_t e = hipMemcpy(v, s.buf, sizeof v, hipMemcpyDeviceToHost); e != hipSuccess) return e;
+    if (hipError_t e = hipMemcpy(v, s.buf[0], sizeof v, hipMemcpyDeviceToHost); e != hipSuccess) return e;
     out2[0] = (long long)v[0];
     out2[1] = (long long)v[1];
     return hipSuccess;
 }
 
 template <typename T>
-static hipError_t launch_eval_grid_t(const Grid &g, const long long *npts, const T *axes, const int *nderiv,
-                                     const T *coef, T *out, hipStream_t st)
+hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, const int *nderiv, const T *coef, T *out, hipStream_t st)
 {
     GridShape gs;
     long long ntab = 0, ntiles = 1;
@@ -324,43 +308,26 @@ static hipError_t launch_eval_grid_t(const Grid &g, const long long *npts, const
     }
     gs.off[MAXD] = ntab;
     for (int d = g.ndim; d < MAXD; ++d) gs.off[d] = ntab;
-    NDeriv nd;
-    bool value_only = true;
-    for (int d = 0; d < MAXD; ++d) {
-        const int v = (nderiv && d < g.ndim) ? nderiv[d] : 0;
-        nd.v[d] = v < 0 ? 0 : (v > 2 ? 2 : v);
-        value_only = value_only && nd.v[d] == 0;
-    }
+    const NDeriv nd = clamp_nderiv(nderiv, g.ndim);
     for (int d = 0; d < MAXD; ++d) {
         const int t = g.ndim == 1 ? GTile<1>::T[d] : g.ndim == 2 ? GTile<2>::T[d] : g.ndim == 3 ? GTile<3>::T[d] : GTile<4>::T[d];
         gs.ntile[d] = (gs.npts[d] + t - 1) / t;
         ntiles *= gs.ntile[d];
     }
     if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
-    GScratch &s = g_gscratch;
-    if (!s.last) if (hipError_t e = hipEventCreateWithFlags(&s.last, hipEventDisableTiming); e != hipSuccess) return e;
-    if (ntab > s.cap) {
-        if (s.buf) { (void)hipFree(s.buf); s.buf = nullptr; s.cap = 0; }      // (hipFree waits for the work that uses it)
-        hipError_t e = hipMalloc(&s.buf, (size_t)eval_grid_scratch_bytes(ntab));
-        if (e != hipSuccess && release_cached_plan_for_memory()) {
-            (void)hipGetLastError();
-            e = hipMalloc(&s.buf, (size_t)eval_grid_scratch_bytes(ntab));
-        }
-        if (e != hipSuccess) { s.buf = nullptr; return e; }
-        s.cap = ntab;
-        s.used = false;
-    }
-    if (s.used) if (hipError_t e = hipStreamWaitEvent(st, s.last, 0); e != hipSuccess) return e;
-    // counters | factors [ntab][4] | window starts [ntab]
-    unsigned long long *stats = static_cast<unsigned long long *>(s.buf);
+    DevScratch<1> &s = g_gscratch;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const size_t need[1] = {(size_t)eval_grid_scratch_bytes(ntab)};
+    if (hipError_t e = s.ensure(dev, need, /*may_release_plan=*/true); e != hipSuccess) return e;
+    if (hipError_t e = s.wait_on(st); e != hipSuccess) return e;
+    unsigned long long *stats = s.as<unsigned long long>(0);
     double *fac = reinterpret_cast<double *>(stats + 2);
-    int *wst = reinterpret_cast<int *>(fac + 4 * s.cap);
+    int *wst = reinterpret_cast<int *>(fac + 4 * ntab);
     if (hipError_t e = hipMemsetAsync(stats, 0, 16, st); e != hipSuccess) return e;
-    s.used = true;
     {
         dim3 gr((unsigned)((ntab + 255) / 256)), bl(256);
-        if (value_only) hipLaunchKernelGGL((grid_table_kernel<T, true>), gr, bl, 0, st, g, gs, nd, axes, fac, wst);
-        else hipLaunchKernelGGL((grid_table_kernel<T, false>), gr, bl, 0, st, g, gs, nd, axes, fac, wst);
+        hipLaunchKernelGGL((value_only(nd) ? grid_table_kernel<T, true> : grid_table_kernel<T, false>), gr, bl, 0, st, g, gs, nd, axes, fac, wst);
     }
     dim3 gr((unsigned)ntiles), bl(GRID_NT);
     switch (g.ndim) {
@@ -370,20 +337,10 @@ static hipError_t launch_eval_grid_t(const Grid &g, const long long *npts, const
     default: hipLaunchKernelGGL((eval_grid_kernel<4, T>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(s.last, st);
+    if (e == hipSuccess) e = s.mark_used(st);
     return e;
 }
-
-hipError_t launch_eval_grid(const Grid &g, const long long *npts, const double *axes, const int *nderiv,
-                            const double *coef, double *out, hipStream_t st)
-{
-    return launch_eval_grid_t<double>(g, npts, axes, nderiv, coef, out, st);
-}
-
-hipError_t launch_eval_grid_f32(const Grid &g, const long long *npts, const float *axes, const int *nderiv,
-                                const float *coef, float *out, hipStream_t st)
-{
-    return launch_eval_grid_t<float>(g, npts, axes, nderiv, coef, out, st);
-}
+template hipError_t launch_eval_grid<double>(const Grid &, const int64_t *, const double *, const int *, const double *, double *, hipStream_t);
+template hipError_t launch_eval_grid<float>(const Grid &, const int64_t *, const float *, const int *, const float *, float *, hipStream_t);
 
 }  // namespace splpak

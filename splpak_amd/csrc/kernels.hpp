@@ -1,4 +1,5 @@
-// Host-side launchers of the HIP kernels (implemented in the .hip files).
+// Host-side launchers of the HIP kernels (implemented in the .hip files).  The evaluation launchers are templates on the
+// storage type, explicitly instantiated for double and float in eval.hip and evalgrid.hip.
 #pragma once
 #include <cstdlib>
 #include "common.hpp"
@@ -9,28 +10,24 @@ namespace splpak {
 // after a failed allocation: release the plan / staging buffers the one-shot fit entry caches (plan.hip); true = retry
 bool release_cached_plan_for_memory();
 
-// ---- eval.hip
-hipError_t launch_eval(const Grid &g, long long nq, const double *xq, int ldxq, const int *nderiv,
-                       const double *coef, double *out, hipStream_t st);
+// ---- eval.hip (dispatchers; the sorted paths: evalpaths.hpp).  T = double or float: storage type of the coordinates,
+// the coefficients and the results (the arithmetic is double)
+template <typename T>
+hipError_t launch_eval(const Grid &g, long long nq, const T *xq, int ldxq, const int *nderiv, const T *coef, T *out, hipStream_t st);
 // value + gradient (order 1) (+ Hessian upper triangle, order 2) per query, ldout apart
-hipError_t launch_eval_derivs(const Grid &g, long long nq, const double *xq, int ldxq, int order,
-                              const double *coef, double *out, int ldout, hipStream_t st);
-hipError_t launch_eval_derivs_f32(const Grid &g, long long nq, const float *xq, int ldxq, int order,
-                                  const float *coef, float *out, int ldout, hipStream_t st);
+template <typename T>
+hipError_t launch_eval_derivs(const Grid &g, long long nq, const T *xq, int ldxq, int order, const T *coef, T *out, int ldout,
+                              hipStream_t st);
 // evaluation path of the calling thread: 0 auto, 1 direct (global gathers), 2 binned (LDS tiles);
 // chunk = queries sorted per pass of the binned path (0 = default)
 void set_eval_mode(int mode, long long chunk);
 void eval_scratch_shutdown();
-hipError_t launch_eval_f32(const Grid &g, long long nq, const float *xq, int ldxq, const int *nderiv,
-                           const float *coef, float *out, hipStream_t st);
 
 // ---- evalgrid.hip
 // out[i0 + npts[0] (i1 + npts[1] (...))] = the value (nderiv: that partial derivative) at (axes_1[i0], axes_2[i1], ...);
 // axes = the npts[0] coordinates of dimension 1, then those of dimension 2, ...  (device pointers; npts, nderiv on the host)
-hipError_t launch_eval_grid(const Grid &g, const long long *npts, const double *axes, const int *nderiv,
-                            const double *coef, double *out, hipStream_t st);
-hipError_t launch_eval_grid_f32(const Grid &g, const long long *npts, const float *axes, const int *nderiv,
-                                const float *coef, float *out, hipStream_t st);
+template <typename T>
+hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, const int *nderiv, const T *coef, T *out, hipStream_t st);
 // bytes of per-thread scratch a call with ntab = sum of npts keeps (factor tables, window starts, tile counters)
 long long eval_grid_scratch_bytes(long long ntab);
 // tiles of the calling thread's last call that took the LDS form [0] and the general form [1]

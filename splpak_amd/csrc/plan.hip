@@ -1,4 +1,5 @@
-// Fit driver and the C ABI (include/splpak_hip.h).
+// Fit driver and its part of the C ABI (include/splpak_hip.h): the plan, the fit, the one-shot fit entries, the debug-plan
+// entries, the options, shutdown, the error message and the device name.  The evaluation entries are in evalapi.hip.
 //
 // The fit that the reference performs as "one dense row at a time through a dense
 // Householder solver" (splcw :512-1060 -> suprls :1375-1695) is done here as
@@ -1123,389 +1124,6 @@ int32_t splpak_fit_f32(int32_t ndim, const float *xdata, int32_t l1xdat, const f
     return rc;
 }
 
-// returns 0/101/102/103/104 exactly like splde's checks (:1166-1194)
-static int eval_validate(int32_t ndim, const int32_t *nderiv, const double *xmin, const double *xmax,
-                         const int32_t *nodes, Grid &g)
-{
-    int v = build_grid(ndim, nodes, xmin, xmax, g, nullptr);
-    if (v != 0) return v;
-    if (nderiv)
-        for (int d = 0; d < ndim; ++d)
-            if (nderiv[d] < 0 || nderiv[d] > 2) v = 104;
-    return v;
-}
-
-// host only: the 4-entry value table of a 1-D grid at n points, as the evaluation kernels select it and in the general form
-int32_t splpak_debug_window_values(int32_t nodes, double xmin, double xmax, int64_t n, const double *x, int32_t *ws_out,
-                                   double *used4, double *general4, int32_t *form_out)
-{
-    if (!x || !ws_out || !used4 || !general4 || !form_out || n < 0) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    Grid g;
-    const int v = build_grid(1, &nodes, &xmin, &xmax, g, nullptr);
-    if (v != 0) return v;
-    for (int64_t i = 0; i < n; ++i) {
-        int form = 0;
-        ws_out[i] = window_table_selected(g, 0, x[i], used4 + 4 * i, form);
-        form_out[i] = form;
-        const int wg = window_table_value(g, 0, x[i], general4 + 4 * i);
-        if (wg != ws_out[i]) { set_error("window starts of the two forms differ"); return SPLPAK_E_BADARG; }
-    }
-    return 0;
-}
-
-int32_t splpak_eval_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq,
-                            const int32_t *nderiv, const double *coef_dev, const double *xmin,
-                            const double *xmax, const int32_t *nodes, double *out_dev, void *stream)
-{
-    if (!nodes || !xmin || !xmax) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    Grid g;
-    const int v = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
-    if (v != 0 && v != 104) {
-        if (v > 0 && out_dev && nq > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(double) * (size_t)nq, (hipStream_t)stream);
-        return v;
-    }
-    if (nq <= 0) return v;
-    if (!xq_dev || !coef_dev || !out_dev) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (ldxq < ndim) { set_error("ldxq smaller than ndim"); return SPLPAK_E_BADARG; }
-    if (int r = device_ready()) return r;
-    SPLPAK_HIP_TRY(launch_eval(g, nq, xq_dev, ldxq, nderiv, coef_dev, out_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return v;
-}
-
-int32_t splpak_eval_dev_f32(int32_t ndim, int64_t nq, const float *xq_dev, int32_t ldxq,
-                            const int32_t *nderiv, const float *coef_dev, const float *xmin_f,
-                            const float *xmax_f, const int32_t *nodes, float *out_dev, void *stream)
-{
-    if (!nodes || !xmin_f || !xmax_f) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (ndim < 1) return 101;
-    if (ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
-    double xmin[MAXD], xmax[MAXD];
-    for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_f[d]; xmax[d] = (double)xmax_f[d]; }
-    Grid g;
-    const int v = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
-    if (v != 0 && v != 104) {
-        if (v > 0 && out_dev && nq > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(float) * (size_t)nq, (hipStream_t)stream);
-        return v;
-    }
-    if (nq <= 0) return v;
-    if (!xq_dev || !coef_dev || !out_dev) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (ldxq < ndim) { set_error("ldxq smaller than ndim"); return SPLPAK_E_BADARG; }
-    if (int r = device_ready()) return r;
-    SPLPAK_HIP_TRY(launch_eval_f32(g, nq, xq_dev, ldxq, nderiv, coef_dev, out_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return v;
-}
-
-static int derivs_nout(int ndim, int order) { return 1 + ndim + (order == 2 ? ndim * (ndim + 1) / 2 : 0); }
-
-int32_t splpak_eval_derivs_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq, int32_t order,
-                                   const double *coef_dev, const double *xmin, const double *xmax,
-                                   const int32_t *nodes, double *out_dev, int32_t ldout, void *stream)
-{
-    if (!nodes || !xmin || !xmax) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    Grid g;
-    const int v = eval_validate(ndim, nullptr, xmin, xmax, nodes, g);
-    if (v != 0) {
-        if (v > 0 && out_dev && nq > 0 && ldout > 0)
-            (void)hipMemsetAsync(out_dev, 0, sizeof(double) * (size_t)nq * (size_t)ldout, (hipStream_t)stream);
-        return v;
-    }
-    if (order < 1 || order > 2) { set_error("order must be 1 (gradient) or 2 (gradient and Hessian)"); return SPLPAK_E_BADARG; }
-    if (ldxq < ndim || ldout < derivs_nout(ndim, order)) { set_error("ldxq or ldout too small"); return SPLPAK_E_BADARG; }
-    if (nq <= 0) return 0;
-    if (!xq_dev || !coef_dev || !out_dev) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (int r = device_ready()) return r;
-    SPLPAK_HIP_TRY(launch_eval_derivs(g, nq, xq_dev, ldxq, order, coef_dev, out_dev, ldout, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return 0;
-}
-
-}  // extern "C"
-
-template <typename T>
-static int32_t eval_host(int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, const int32_t *nderiv,
-                         const T *coef, const T *xmin_t, const T *xmax_t, const int32_t *nodes, T *out)
-{
-    if (!nodes || !xmin_t || !xmax_t) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (ndim < 1) return 101;
-    if (ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
-    double xmin[MAXD], xmax[MAXD];
-    for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_t[d]; xmax[d] = (double)xmax_t[d]; }
-    Grid g;
-    const int v = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
-    if (v != 0 && v != 104) {
-        if (v > 0 && out) for (int64_t i = 0; i < nq; ++i) out[i] = (T)0;
-        return v;
-    }
-    if (nq <= 0) return v;
-    if (!xq || !coef || !out) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (ldxq < ndim) { set_error("ldxq smaller than ndim"); return SPLPAK_E_BADARG; }
-    if (int r = device_ready()) return r;
-    T *dq = nullptr, *dc = nullptr, *dout = nullptr;
-    splpak_plan holder;   // only used as an allocation owner
-    bool ok = dev_alloc(&holder, &dq, (size_t)nq * ldxq) && dev_alloc(&holder, &dc, (size_t)g.ncol) &&
-              dev_alloc(&holder, &dout, (size_t)nq);
-    int rc = v;
-    if (!ok) rc = SPLPAK_E_NOMEM;
-    if (ok) {
-        hipError_t e = hipMemcpy(dq, xq, sizeof(T) * (size_t)nq * ldxq, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * (size_t)g.ncol, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            if constexpr (sizeof(T) == 8)
-                e = launch_eval(g, nq, (const double *)dq, ldxq, nderiv, (const double *)dc, (double *)dout, nullptr);
-            else
-                e = launch_eval_f32(g, nq, (const float *)dq, ldxq, nderiv, (const float *)dc, (float *)dout, nullptr);
-        }
-        if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost);
-        if (!hip_ok(e, "evaluation")) rc = SPLPAK_E_NODEVICE;
-    }
-    for (void *q : holder.owned) (void)hipFree(q);
-    return rc;
-}
-
-template <typename T>
-static int32_t eval_derivs_host(int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, int32_t order, const T *coef,
-                                const T *xmin_t, const T *xmax_t, const int32_t *nodes, T *out, int32_t ldout)
-{
-    if (!nodes || !xmin_t || !xmax_t) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (ndim < 1) return 101;
-    if (ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
-    double xmin[MAXD], xmax[MAXD];
-    for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_t[d]; xmax[d] = (double)xmax_t[d]; }
-    Grid g;
-    const int v = eval_validate(ndim, nullptr, xmin, xmax, nodes, g);
-    if (v != 0) {
-        if (v > 0 && out && ldout > 0) for (int64_t i = 0; i < nq * ldout; ++i) out[i] = (T)0;
-        return v;
-    }
-    if (order < 1 || order > 2) { set_error("order must be 1 (gradient) or 2 (gradient and Hessian)"); return SPLPAK_E_BADARG; }
-    if (ldxq < ndim || ldout < derivs_nout(ndim, order)) { set_error("ldxq or ldout too small"); return SPLPAK_E_BADARG; }
-    if (nq <= 0) return 0;
-    if (!xq || !coef || !out) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    if (int r = device_ready()) return r;
-    T *dq = nullptr, *dc = nullptr, *dout = nullptr;
-    splpak_plan holder;   // only used as an allocation owner
-    bool ok = dev_alloc(&holder, &dq, (size_t)nq * ldxq) && dev_alloc(&holder, &dc, (size_t)g.ncol) &&
-              dev_alloc(&holder, &dout, (size_t)nq * ldout);
-    int rc = 0;
-    if (!ok) rc = SPLPAK_E_NOMEM;
-    if (ok) {
-        hipError_t e = hipMemcpy(dq, xq, sizeof(T) * (size_t)nq * ldxq, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * (size_t)g.ncol, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemset(dout, 0, sizeof(T) * (size_t)nq * ldout);
-        if (e == hipSuccess) {
-            if constexpr (sizeof(T) == 8)
-                e = launch_eval_derivs(g, nq, (const double *)dq, ldxq, order, (const double *)dc, (double *)dout, ldout, nullptr);
-            else
-                e = launch_eval_derivs_f32(g, nq, (const float *)dq, ldxq, order, (const float *)dc, (float *)dout, ldout, nullptr);
-        }
-        if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(T) * (size_t)nq * ldout, hipMemcpyDeviceToHost);
-        if (!hip_ok(e, "evaluation")) rc = SPLPAK_E_NODEVICE;
-    }
-    for (void *q : holder.owned) (void)hipFree(q);
-    return rc;
-}
-
-extern "C" {
-
-int32_t splpak_eval_derivs_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq, int32_t order,
-                               const double *coef, const double *xmin, const double *xmax,
-                               const int32_t *nodes, double *out, int32_t ldout)
-{
-    return eval_derivs_host<double>(ndim, nq, xq, ldxq, order, coef, xmin, xmax, nodes, out, ldout);
-}
-
-int32_t splpak_eval_derivs_f32(int32_t ndim, int64_t nq, const float *xq, int32_t ldxq, int32_t order,
-                               const float *coef, const float *xmin, const float *xmax,
-                               const int32_t *nodes, float *out, int32_t ldout)
-{
-    return eval_derivs_host<float>(ndim, nq, xq, ldxq, order, coef, xmin, xmax, nodes, out, ldout);
-}
-
-int32_t splpak_eval_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq,
-                        const int32_t *nderiv, const double *coef, const double *xmin,
-                        const double *xmax, const int32_t *nodes, double *out)
-{
-    return eval_host<double>(ndim, nq, xq, ldxq, nderiv, coef, xmin, xmax, nodes, out);
-}
-
-int32_t splpak_eval_f32(int32_t ndim, int64_t nq, const float *xq, int32_t ldxq,
-                        const int32_t *nderiv, const float *coef, const float *xmin,
-                        const float *xmax, const int32_t *nodes, float *out)
-{
-    return eval_host<float>(ndim, nq, xq, ldxq, nderiv, coef, xmin, xmax, nodes, out);
-}
-
-}  // extern "C"
-
-// ---- evaluation on a tensor-product grid of points (evalgrid.hip) ----
-// outputs and table entries of a grid call; false: a negative count or a product beyond int64
-static bool grid_counts(int32_t ndim, const int64_t *npts, long long &nout, long long &ntab)
-{
-    nout = 1;
-    ntab = 0;
-    bool zero = false;
-    for (int d = 0; d < ndim; ++d) {
-        if (npts[d] < 0) return false;
-        zero = zero || npts[d] == 0;
-        if (__builtin_add_overflow(ntab, (long long)npts[d], &ntab)) return false;
-    }
-    if (zero) { nout = 0; return true; }
-    for (int d = 0; d < ndim; ++d)
-        if (__builtin_mul_overflow(nout, (long long)npts[d], &nout)) return false;
-    return true;
-}
-
-// The checks every grid entry makes before it touches a device, in the order of eval_host / splpak_eval_dev_f64.
-// Returns true when the caller goes on to compute (rc = 0 or 104); otherwise rc is the status to return and
-// zero_n the outputs to zero first (101: the empty product, one output; 102 / 103: all of them).
-template <typename T>
-static bool grid_validate(int32_t ndim, const int64_t *npts, const T *axes, const int32_t *nderiv, const T *coef,
-                          const T *xmin_t, const T *xmax_t, const int32_t *nodes, const T *out, Grid &g, long long &nout,
-                          int &rc, long long &zero_n)
-{
-    zero_n = 0;
-    nout = 0;
-    if (!nodes || !xmin_t || !xmax_t || !npts) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    if (ndim < 1) { rc = 101; zero_n = out ? 1 : 0; return false; }
-    if (ndim > MAXD) { rc = SPLPAK_E_UNSUPPORTED; return false; }
-    long long ntab = 0;
-    if (!grid_counts(ndim, npts, nout, ntab)) {
-        set_error("negative npts, or an output count beyond int64");
-        rc = SPLPAK_E_BADARG;
-        return false;
-    }
-    double xmin[MAXD], xmax[MAXD];
-    for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_t[d]; xmax[d] = (double)xmax_t[d]; }
-    rc = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
-    if (rc != 0 && rc != 104) {
-        if (rc > 0 && out) zero_n = nout;
-        return false;
-    }
-    if (nout == 0) return false;
-    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    if (int r = device_ready()) { rc = r; return false; }
-    return true;
-}
-
-template <typename T>
-static hipError_t launch_eval_grid_any(const Grid &g, const long long *npts, const T *axes, const int *nderiv, const T *coef,
-                                       T *out, hipStream_t st)
-{
-    if constexpr (sizeof(T) == 8) return launch_eval_grid(g, npts, (const double *)axes, nderiv, (const double *)coef, (double *)out, st);
-    else return launch_eval_grid_f32(g, npts, (const float *)axes, nderiv, (const float *)coef, (float *)out, st);
-}
-
-template <typename T>
-static int32_t eval_grid_dev(int32_t ndim, const int64_t *npts, const T *axes_dev, const int32_t *nderiv, const T *coef_dev,
-                             const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, void *stream)
-{
-    Grid g;
-    long long nout = 0, zero_n = 0;
-    int rc = 0;
-    if (!grid_validate(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, g, nout, rc, zero_n)) {
-        if (zero_n > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
-        return rc;
-    }
-    long long np[MAXD] = {1, 1, 1, 1};
-    for (int d = 0; d < ndim; ++d) np[d] = npts[d];
-    SPLPAK_HIP_TRY(launch_eval_grid_any<T>(g, np, axes_dev, nderiv, coef_dev, out_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return rc;
-}
-
-template <typename T>
-static int32_t eval_grid_host(int32_t ndim, const int64_t *npts, const T *axes, const int32_t *nderiv, const T *coef,
-                              const T *xmin, const T *xmax, const int32_t *nodes, T *out)
-{
-    Grid g;
-    long long nout = 0, zero_n = 0;
-    int rc = 0;
-    if (!grid_validate(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, g, nout, rc, zero_n)) {
-        for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
-        return rc;
-    }
-    long long np[MAXD] = {1, 1, 1, 1}, ntab = 0;
-    for (int d = 0; d < ndim; ++d) { np[d] = npts[d]; ntab += npts[d]; }
-    T *da = nullptr, *dc = nullptr, *dout = nullptr;
-    splpak_plan holder;   // only used as an allocation owner
-    const bool ok = dev_alloc(&holder, &da, (size_t)ntab) && dev_alloc(&holder, &dc, (size_t)g.ncol) &&
-                    dev_alloc(&holder, &dout, (size_t)nout);
-    if (!ok) rc = SPLPAK_E_NOMEM;
-    if (ok) {
-        hipError_t e = hipMemcpy(da, axes, sizeof(T) * (size_t)ntab, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * (size_t)g.ncol, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = launch_eval_grid_any<T>(g, np, da, nderiv, dc, dout, nullptr);
-        if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(T) * (size_t)nout, hipMemcpyDeviceToHost);
-        if (!hip_ok(e, "grid evaluation")) rc = SPLPAK_E_NODEVICE;
-    }
-    for (void *q : holder.owned) (void)hipFree(q);
-    return rc;
-}
-
-extern "C" {
-
-int32_t splpak_eval_grid_f64(int32_t ndim, const int64_t *npts, const double *axes, const int32_t *nderiv,
-                             const double *coef, const double *xmin, const double *xmax, const int32_t *nodes, double *out)
-{
-    return eval_grid_host<double>(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out);
-}
-
-int32_t splpak_eval_grid_f32(int32_t ndim, const int64_t *npts, const float *axes, const int32_t *nderiv,
-                             const float *coef, const float *xmin, const float *xmax, const int32_t *nodes, float *out)
-{
-    return eval_grid_host<float>(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out);
-}
-
-int32_t splpak_eval_grid_dev_f64(int32_t ndim, const int64_t *npts, const double *axes_dev, const int32_t *nderiv,
-                                 const double *coef_dev, const double *xmin, const double *xmax, const int32_t *nodes,
-                                 double *out_dev, void *stream)
-{
-    return eval_grid_dev<double>(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, stream);
-}
-
-int32_t splpak_eval_grid_dev_f32(int32_t ndim, const int64_t *npts, const float *axes_dev, const int32_t *nderiv,
-                                 const float *coef_dev, const float *xmin, const float *xmax, const int32_t *nodes,
-                                 float *out_dev, void *stream)
-{
-    return eval_grid_dev<float>(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, stream);
-}
-
-int64_t splpak_eval_grid_scratch_bytes(int32_t ndim, const int64_t *npts)
-{
-    long long nout = 0, ntab = 0;
-    if (!npts || ndim < 1 || ndim > MAXD || !grid_counts(ndim, npts, nout, ntab)) { set_error("bad grid shape"); return SPLPAK_E_BADARG; }
-    return nout == 0 ? 0 : eval_grid_scratch_bytes(ntab);
-}
-
-int32_t splpak_debug_eval_grid_stats(int64_t out2[2])
-{
-    if (!out2) { set_error("null argument"); return SPLPAK_E_BADARG; }
-    out2[0] = out2[1] = 0;
-    if (int r = device_ready()) return r;
-    long long v[2];
-    SPLPAK_HIP_TRY(eval_grid_stats(v), SPLPAK_E_NODEVICE);
-    out2[0] = v[0];
-    out2[1] = v[1];
-    return 0;
-}
-
-int32_t splpak_synth_points_f64(int32_t ndim, int64_t first_point, int64_t ndata, double *xdata_dev,
-                                double *ydata_dev, double *wdata_dev, void *stream)
-{
-    if (ndim < 1 || ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
-    if (int r = device_ready()) return r;
-    SPLPAK_HIP_TRY(launch_synth_points(ndim, first_point, ndata, xdata_dev, ydata_dev, wdata_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return 0;
-}
-
-int32_t splpak_synth_queries_f64(int32_t ndim, int64_t ndata_before, int64_t first_query, int64_t nq,
-                                 double *xq_dev, void *stream)
-{
-    if (ndim < 1 || ndim > MAXD) return SPLPAK_E_UNSUPPORTED;
-    if (int r = device_ready()) return r;
-    const long long skip = (long long)ndata_before * (ndim + 2) + (long long)first_query * ndim;
-    SPLPAK_HIP_TRY(launch_synth_queries(ndim, skip, nq, xq_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return 0;
-}
-
 int32_t splpak_debug_spd_band_solve_f64(int32_t n, int32_t halfbw, const double *a_lower,
                                         const double *bvec, double *x)
 {
@@ -1750,13 +1368,6 @@ void splpak_shutdown(void)
     }
     eval_scratch_shutdown();
     eval_grid_scratch_shutdown();
-}
-
-int32_t splpak_set_eval_mode(int32_t mode, int64_t chunk)
-{
-    if (mode < 0 || mode > 2 || chunk < 0) { set_error("bad evaluation mode"); return SPLPAK_E_BADARG; }
-    set_eval_mode(mode, chunk);
-    return 0;
 }
 
 int32_t splpak_last_error_message(char *buf, int32_t buflen)

@@ -259,6 +259,98 @@ def test_eval_binned_scratch_regrows_for_a_grid_with_more_regions():
         capi.set_eval_mode(capi.EVAL_AUTO)
 
 
+def test_eval_scratch_of_every_path_across_streams_regrowth_and_threads():
+    """Every evaluation path keeps per-thread device scratch of its own (csrc/evalscratch.hpp): a call on another stream
+    waits for the previous use, regrowing one path's scratch leaves the others' alone, and threads do not share it.
+    One host thread, EVAL_BINNED forced, the calls alternating between two streams with no synchronisation in between;
+    every call must return the bits of the direct kernel.  Which path takes a grid follows from the code:
+      1. 2-D (20, 20): the region sort (2-D has no other path; one region).
+      2. 3-D (7, 20, 20): make_pregions refuses nodes < 8; make_regions gives 1 x 2 x 2 = 4 <= 256 regions: the run path.
+      3. 3-D (19, 19, 19): 16 window starts per dimension are ONE region at 16 per region (< 8 regions: refused) and
+         2 x 2 x 2 = 8 at 8 per region: the persistent path.
+      4. 4-D (19, 19, 19, 11): 2 x 2 x 2 x 1 = 8 regions of 8 window starts: the persistent 4-D path.
+      5. the grid route on 9 x 10 x 11 points of (19, 19, 19), against the point route.
+      6. case 1 with 40 000 queries in chunks of 4 099 (ten chunks, a ragged last one: these still fit the buffers of call
+         1, which held 5 000 queries), then in ONE chunk, which regrows the sort scratch.
+      7. cases 2 and 3 again: their scratch was not touched by the regrowth.
+    At the end a second Python thread runs case 3 with scratch of its own."""
+    import threading
+    import torch
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2024)
+    streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
+
+    def make(nodes, nq):
+        nd = len(nodes)
+        coef = torch.randn(int(np.prod(nodes)), dtype=torch.float64, device=dev, generator=gen)
+        xq = torch.rand((nq, nd), dtype=torch.float64, device=dev, generator=gen) * 1.2 - 0.1      # ~30 % outside the grid
+        return nodes, coef, xq
+
+    c1, c2, c3, c4 = make((20, 20), 5000), make((7, 20, 20), 5000), make((19, 19, 19), 5000), make((19, 19, 19, 11), 5000)
+    c6 = (c1[0], c1[1], make(c1[0], 40_000)[2])
+    axes = [torch.rand(n, dtype=torch.float64, device=dev, generator=gen) * 1.2 - 0.1 for n in (9, 10, 11)]
+    g2, g1, g0 = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    grid_points = torch.stack([g0, g1, g2], dim=-1).reshape(-1, 3).contiguous()
+    torch.cuda.synchronize()
+    pending = []          # (what, binned / grid result, direct result)
+    turn = [0]
+
+    def point(case, mode, chunk=0, stream=None):
+        nodes, coef, xq = case
+        nd = len(nodes)
+        if stream is None:
+            stream = streams[turn[0] % 2]
+            turn[0] += 1
+        out = torch.empty(xq.shape[0], dtype=torch.float64, device=dev)
+        capi.set_eval_mode(mode, chunk)
+        assert capi.evaluate_dev(nd, xq, None, coef, [0.0] * nd, [1.0] * nd, nodes, out, stream.cuda_stream) == 0
+        return out
+
+    def both(what, case, chunk=0):
+        pending.append((what, point(case, capi.EVAL_BINNED, chunk), point(case, capi.EVAL_DIRECT)))
+
+    try:
+        both("1 sort", c1)
+        both("2 runs", c2)
+        both("3 persistent", c3)
+        both("4 persistent 4-D", c4)
+        gout = torch.empty(9 * 10 * 11, dtype=torch.float64, device=dev)
+        st = streams[turn[0] % 2]
+        turn[0] += 1
+        assert capi.evaluate_grid_dev(3, [9, 10, 11], torch.cat(axes), None, c3[1], [0.0] * 3, [1.0] * 3, c3[0], gout, st.cuda_stream) == 0
+        pending.append(("5 grid", gout, point((c3[0], c3[1], grid_points), capi.EVAL_DIRECT)))
+        both("6 sort, chunks of 4099", c6, 4099)
+        both("6 sort, regrown", c6)
+        both("7 runs again", c2)
+        both("7 persistent again", c3)
+        torch.cuda.synchronize()
+        for what, a, b in pending:
+            assert torch.equal(a, b), what
+        result = []
+
+        def other_thread():
+            try:
+                torch.cuda.set_device(0)
+                st2 = torch.cuda.Stream(device=dev)
+                a = point(c3, capi.EVAL_BINNED, stream=st2)
+                b = point(c3, capi.EVAL_DIRECT, stream=st2)
+                st2.synchronize()
+                result.append(bool(torch.equal(a, b)) and bool(torch.equal(a, pending[2][1])))
+            except Exception as exc:          # (reported by the assertion below)
+                result.append(exc)
+
+        t = threading.Thread(target=other_thread)
+        t.start()
+        t.join()
+        assert result == [True], result
+        both("3 persistent, first thread again", c3)
+        torch.cuda.synchronize()
+        assert torch.equal(pending[-1][1], pending[-1][2])
+    finally:
+        capi.set_eval_mode(capi.EVAL_AUTO)
+
+
 @pytest.mark.parametrize("nodes", [(64, 64, 64), (40, 33, 52), (20, 20, 20)])
 def test_eval_persistent_path_clusters_ends_and_small_batches(port, nodes):
     """The persistent 3-D path of round 4 (place pass that DEALS the queries of a bin by LDS slot class / evaluation waves
