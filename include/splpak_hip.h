@@ -85,6 +85,27 @@ int32_t splpak_fit_f32(int32_t ndim, const float *xdata, int32_t l1xdat,
                        float xtrap, float *coef, int64_t ncf, int64_t nwrk,
                        float *hist_out, double *info);
 
+/* New values on the points of the last one-shot fit: several fields sampled at the same points (the components of a
+ * velocity, a time series on a fixed sensor layout, bootstrap replicas) cost one fit and one refit each instead of a fit each.
+ * The reference has no counterpart: every splcw call starts from the points (:512-1060).
+ * splpak_fit_token: the token of the calling thread's last successful splpak_fit_f64 / _f32 (every successful fit of the
+ * process draws a fresh one); 0 if there was none, or after a multi-GPU fit. */
+int64_t splpak_fit_token(void);
+/* Field k is the `ndata` values at ydata + k*ldy, in the point order of that fit (ldy >= ndata); its coefficients go to
+ * coef + k*ldcoef (ldcoef >= ncol).  The fields are solved one after another with what the fit left on the device -- its
+ * factorisation, or its iteration -- as splpak_plan_refit_dev describes; info (10 doubles per field, may be NULL) likewise.
+ * Returns 0; 107 as the fit would (that field's coefficients as the fit would return them, the later fields zeroed);
+ * SPLPAK_E_BADARG for a null pointer, nfields < 1, ldy < ndata or ldcoef < ncol; SPLPAK_E_UNSUPPORTED, with the message "the
+ * fit is no longer resident: fit again", when `token` is not that of the fit the library still holds or `ndata` is not its
+ * number of points: after another fit, splpak_shutdown, a release of the cached plan under memory pressure, with
+ * SPLPAK_NO_PLAN_CACHE, or after a multi-GPU fit.  A refused call (either of those two statuses) and a 107 leave the fit resident
+ * and the token good; a device failure (SPLPAK_E_NODEVICE, SPLPAK_E_NOMEM) releases it. */
+int32_t splpak_refit_f64(int64_t token, int32_t nfields, const double *ydata, int64_t ldy, int64_t ndata,
+                         double *coef, int64_t ldcoef, double *info);
+/* the REAL32 twin: storage f32, arithmetic f64 (token of a splpak_fit_f32 or a splpak_fit_f64 alike) */
+int32_t splpak_refit_f32(int64_t token, int32_t nfields, const float *ydata, int64_t ldy, int64_t ndata,
+                         float *coef, int64_t ldcoef, double *info);
+
 /* Replaces a loop of splde (:1089) calls; nderiv == NULL gives splfe (:1258).
  * Query i is the `ndim` doubles at xq + i*ldxq (ldxq >= ndim, else SPLPAK_E_BADARG).  Error semantics per query are
  * the reference's: 101/102/103 return without computing (out is set to 0),
@@ -185,6 +206,28 @@ void    splpak_plan_set_refine(splpak_plan *plan, int32_t max_steps, double tol)
 int32_t splpak_plan_fit_dev(splpak_plan *plan, const double *xdata_dev, int32_t l1xdat,
                             const double *ydata_dev, const double *wdata_dev,
                             int64_t ndata, double *coef_dev, void *stream, double *info);
+/* New values on the points of the plan's last fit.  Only the solve depends on ydata: the binned points, the histogram, the
+ * data-sparse flags, the constraint rows, N = A^T W^2 A + C^T C, its factor and the iteration's preconditioner are functions of
+ * xdata, wdata and the grid, and a successful single-rank fit leaves them in the plan.  Field k is the `ndata` values (of that
+ * fit) at ydata_dev + k*ldy, in that fit's point order; its ncol coefficients go to coef_dev + k*ldcoef.  The fields are
+ * processed one after another: the values are gathered into the binned order, A^T W^2 y is one pass over the rows, and the
+ * solve, the refinement against the rows, the diagnostics and the decisions that end in 107 are the fit's own.  The solver
+ * follows what the fit left: a held factor is used as it is (no expansion, no factorisation); a fit the iteration answered is
+ * iterated again on the prepared preconditioner, and if that gives up and the plan has a factorisation the normal equations
+ * are assembled from the binned points and factored as the fit does -- the later fields then use the factor.
+ * info (10 doubles per field, may be NULL) as for the fit: [0] [1] the fit's row counts, [2] [3] [7] [8] [9] measured for the
+ * field, [4] the held factor's smallest pivot, [5] 0, [6] 0 unless the factorisation ran in this call.
+ * Returns 0; 107 as the fit (that field's coefficients zeroed or returned as the fit would, the later fields zeroed; the plan
+ * stays refit-able); SPLPAK_E_BADARG for a null pointer, nfields < 1, ldy < ndata or ldcoef < ncol; SPLPAK_E_UNSUPPORTED, with a
+ * message naming the reason, when there is nothing to refit: no successful fit yet, a failed fit, a splpak_debug_plan_solve
+ * since the fit, or a plan that is a rank of a sharded or multi-GPU fit (an all-reduce hook installed) -- decided on the host
+ * before any device work.  Synchronises `stream` before returning.
+ * After a successful refit splpak_debug_plan_rows_gradient and splpak_debug_plan_normal_equations describe the LAST FIELD: N is
+ * the fit's, rhs and the values of the rows are the field's; after a refit that returned 107 the former refuses, as after a
+ * failed fit.  splpak_plan_stage_timing after a refit: [1] is the values gather + right-hand side, [0] and [2] are 0, [3] is 0
+ * unless the factorisation ran, [4] [5] as for the fit. */
+int32_t splpak_plan_refit_dev(splpak_plan *plan, int32_t nfields, const double *ydata_dev, int64_t ldy,
+                              double *coef_dev, int64_t ldcoef, void *stream, double *info);
 /* device pointer to the (all-reduced) sparse-area histogram of the last fit */
 const double *splpak_plan_hist_dev(const splpak_plan *plan);
 /* device memory the plan holds (bytes) */

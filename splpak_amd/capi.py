@@ -25,6 +25,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_voi
 # every symbol include/splpak_hip.h declares
 SYMBOLS = [
     "splpak_fit_f64", "splpak_fit_f32", "splpak_eval_f64", "splpak_eval_f32",
+    "splpak_fit_token", "splpak_refit_f64", "splpak_refit_f32", "splpak_plan_refit_dev",
     "splpak_plan_comm_len", "splpak_plan_create", "splpak_plan_destroy",
     "splpak_plan_set_allreduce", "splpak_plan_set_allreduce_ex", "splpak_plan_set_rccl", "splpak_rccl_unique_id", "splpak_rccl_comm_create",
     "splpak_rccl_comm_create_from_file", "splpak_rccl_comm_create_from_file_ex", "splpak_rccl_comm_destroy", "splpak_plan_set_refine", "splpak_plan_fit_dev",
@@ -75,6 +76,14 @@ def lib() -> C.CDLL:
     L.splpak_fit_f64.argtypes = [i32, _dp, i32, _dp, _dp, i64, _dp, _dp, _ip, dbl, _dp, i64, i64, _dp, _dp]
     L.splpak_fit_f32.restype = i32
     L.splpak_fit_f32.argtypes = [i32, _fp, i32, _fp, _fp, i64, _fp, _fp, _ip, C.c_float, _fp, i64, i64, _fp, _dp]
+    L.splpak_fit_token.restype = i64
+    L.splpak_fit_token.argtypes = []
+    L.splpak_refit_f64.restype = i32
+    L.splpak_refit_f64.argtypes = [i64, i32, _dp, i64, i64, _dp, i64, _dp]
+    L.splpak_refit_f32.restype = i32
+    L.splpak_refit_f32.argtypes = [i64, i32, _fp, i64, i64, _fp, i64, _dp]
+    L.splpak_plan_refit_dev.restype = i32
+    L.splpak_plan_refit_dev.argtypes = [vp, i32, vp, i64, vp, i64, vp, _dp]
     L.splpak_eval_f64.restype = i32
     L.splpak_eval_f64.argtypes = [i32, i64, _dp, i32, _ip, _dp, _dp, _dp, _ip, _dp]
     L.splpak_eval_f32.restype = i32
@@ -277,6 +286,29 @@ def fit(ndim, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, ncf=None, nwrk=-1, 
                    _p(xmax, rp), _p(nodes, _ip), xt, _p(coef, rp), ncf, nwrk, _p(hist, rp),
                    _p(info, _dp)))
     return coef, rc, hist, info
+
+
+def fit_token() -> int:
+    """Token of this thread's last successful one-shot fit() (0: none) -- what refit() takes."""
+    return int(lib().splpak_fit_token())
+
+
+def refit(token, ydata, ncol, real32=False, ldcoef=None):
+    """New values on the points of the one-shot fit `token`: ydata is (nfields, ndata) or (ndata,), in that fit's point order;
+    `ncol` the fit's number of coefficients.  -> (coef of shape (nfields, ldcoef or ncol) -- (ncol,) for a 1-D ydata --, ierror,
+    info of shape (nfields, 10)).  Raises SplpakError when the fit is no longer resident (fit again)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    ydata = np.ascontiguousarray(ydata, dtype=dt)
+    single = ydata.ndim == 1
+    y2 = ydata.reshape(1, -1) if single else ydata
+    nfields, ndata = y2.shape
+    ldc = int(ncol if ldcoef is None else ldcoef)
+    coef = np.zeros((max(nfields, 1), max(ldc, 1)), dtype=dt)
+    info = np.zeros((max(nfields, 1), 10))
+    fn = lib().splpak_refit_f32 if real32 else lib().splpak_refit_f64
+    rc = _check(fn(int(token), int(nfields), _p(y2, rp), int(ndata), int(ndata), _p(coef, rp), ldc, _p(info, _dp)))
+    return (coef[0] if single else coef), rc, (info[0] if single else info)
 
 
 def fit_multi(ngpus, ndim, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, want_hist=False):
@@ -577,6 +609,24 @@ class Plan:
                                          None if wdata is None else wdata.data_ptr(), int(ndata),
                                          coef.data_ptr(), C.c_void_p(stream), _p(info, _dp))
         return _check(rc), info
+
+    def refit(self, ydata, coef, stream=0):
+        """New values on the points of this plan's last fit (splpak_plan_refit_dev).  ydata: (nfields, ndata) or (ndata,) torch
+        float64 device tensor, field k in row k (row stride >= ndata, unit stride inside a row), in that fit's point order;
+        coef: (nfields, >= ncol) or (ncol,) likewise.  Returns (ierror, info) with info of shape (nfields, 10) -- (10,) for a 1-D
+        ydata.  Raises SplpakError when there is nothing to refit."""
+        single = ydata.dim() == 1
+        nfields = 1 if single else int(ydata.shape[0])
+        ldy = int(ydata.shape[0]) if single else int(ydata.stride(0))
+        ldc = int(coef.shape[0]) if coef.dim() == 1 else int(coef.stride(0))
+        if any(t.shape[-1] > 1 and t.stride(-1) != 1 for t in (ydata, coef)):
+            raise SplpakError("refit: the values of a field, and its coefficients, must be contiguous")
+        if (coef.dim() == 1) != single or (not single and int(coef.shape[0]) != nfields):
+            raise SplpakError("refit: ydata and coef must name the same number of fields")
+        info = np.zeros((max(nfields, 1), 10))
+        rc = self._L.splpak_plan_refit_dev(self._h, nfields, ydata.data_ptr(), ldy, coef.data_ptr(), ldc,
+                                           C.c_void_p(stream), _p(info, _dp))
+        return _check(rc), (info[0] if single else info)
 
     def hist_ptr(self):
         return self._L.splpak_plan_hist_dev(self._h)

@@ -2215,6 +2215,44 @@ hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ld
     return hipGetLastError();
 }
 
+// New values on the points of the last binning (the refit): ys_out[pos] = y[idx[pos]].  The stores and the reads of idx are
+// consecutive per wave; the reads of y are the scattered side -- the points of a cell are ordered by original index, so a wave
+// mostly walks ascending addresses -- and four of them per thread are in flight together (the kernel does nothing but wait for
+// them).  The binning placed offset[ncell] points (a zero-weight point is counted, not placed): the positions behind them hold
+// no point, their idx is not read, and they are given 0; no weight ever reads them.
+__global__ void __launch_bounds__(256)
+regather_values_kernel(long long n, const int *__restrict__ placed, const int *__restrict__ idx, const double *__restrict__ y,
+                       double *__restrict__ ys)
+{
+    const long long np = min((long long)*placed, n);
+    const long long tile = 4LL * blockDim.x, stride = (long long)gridDim.x * tile;
+    for (long long p0 = (long long)blockIdx.x * tile + threadIdx.x; p0 < n; p0 += stride) {
+        long long src[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long pos = p0 + (long long)u * blockDim.x;
+            src[u] = pos < np ? (long long)idx[pos] : -1;
+        }
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = y[src[u] < 0 ? 0 : src[u]];      // (unconditional loads: four in flight)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long pos = p0 + (long long)u * blockDim.x;
+            if (pos < n) ys[pos] = src[u] < 0 ? 0.0 : v[u];
+        }
+    }
+}
+
+hipError_t launch_regather_values(const Grid &g, const SortScratch &s, long long n, const double *y, double *ys_out, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    if (n > s.cap) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(regather_values_kernel, dim3(grid_for(n, 1024, 2048)), dim3(256), 0, st, n, (const int *)s.offset + g.ncell,
+                       (const int *)s.idx, y, ys_out);
+    return hipGetLastError();
+}
+
 long long gram_scratch_min_doubles(const Grid &g)
 {   // one hyper-row of cells along the slowest dimension
     return (long long)g.cellstride[g.ndim - 1] * (gram_tri(g.nb) + 2LL * g.nb);

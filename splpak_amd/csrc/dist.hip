@@ -699,6 +699,7 @@ int32_t splpak_fit_multi_f64(int32_t ngpus, int32_t ndim, const double *xdata, i
     if (!xdata || !ydata || !coef) { set_error("null argument"); return SPLPAK_E_BADARG; }
     if (l1xdat < ndim) { set_error("l1xdat < ndim"); return SPLPAK_E_BADARG; }
     if (wdata && wdata[0] < 0.0) wdata = nullptr;
+    hostfit_forget_token();            // (the caller's last fit is this one from here on, and it leaves nothing to refit)
     const long long per = (ndata + ngpus - 1) / ngpus;
     splpak_mplan *mp = nullptr;
     const char *ck = splpak::opt_get("SPLPAK_DIST_CHUNK");

@@ -70,6 +70,10 @@ long long bin_record_doubles(const Grid &g, long long max_ndata);
 // cell ordered by original index
 hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ldx, const double *y,
                              const double *w, const SortScratch &s, double *scal, hipStream_t st);
+// new values on the binned points (the refit): ys_out[pos] = y[s.idx[pos]] for the s.offset[g.ncell] positions the last binning
+// of n points filled; the positions behind them, up to n, hold no point (zero weights are not placed) and receive 0.
+// y: the n values in the caller's point order
+hipError_t launch_regather_values(const Grid &g, const SortScratch &s, long long n, const double *y, double *ys_out, hipStream_t st);
 // doubles of scratch launch_gram uses when it can hold every cell's blocks at once (per-cell Gram blocks,
 // right-hand sides, histogram shares), and the least it can work with (one hyper-row of cells)
 long long gram_scratch_doubles(const Grid &g);

@@ -628,6 +628,24 @@ static int plan_diagnostics_pass(splpak_plan *p, bool rows_fit, hipStream_t st, 
     return 0;
 }
 
+// A 4-D plan with the iteration in front of a factorisation leaves the normal equations unassembled until the factorisation
+// is going to need them (see splpak_plan_fit_dev); read under the plan's options
+static bool plan_lazy_assembly(const splpak_plan *p)
+{
+    return !p->rows_only && p->pcg && p->solver_mode == 3 && p->rowsop && p->xtrap != 0.0 && p->world <= 1 && !p->ar &&
+           pcg_boxes_from_rows(p->pcg) && !splpak::opt_get("SPLPAK_PCG_EAGER");
+}
+
+// What the solve of a fit starts from: left by the assembly of splpak_plan_fit_dev, or taken from the plan by a refit
+struct SolveStart {
+    double rows_cons = 0, sumw2 = 0;
+    bool lazy = false;            // the normal equations are assembled only if the factorisation is going to run
+    bool rows_fit = false;        // they are not assembled (a rows-only plan, or a lazy one so far)
+    bool refit = false;           // new values on the last fit's points: the solver follows what that fit left in the plan
+    std::chrono::steady_clock::time_point t1;      // the end of the assembly (refit: the start of the field)
+};
+static int plan_solve_stage(splpak_plan *p, hipStream_t st, double *coef_dev, double *info, const SolveStart &a);
+
 extern "C" {
 
 int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, const double *y,
@@ -651,6 +669,8 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     p->ne_valid = false;
     p->fit_valid = false;
     p->pcg_prepared = false;
+    p->geom_valid = false;
+    p->factor_valid = false;
     hipStream_t st = (hipStream_t)stream;
     if (lerr == 0 && w && ndata > 0) {
         // a negative first weight means "no weights" (:796, :890), as in the host entry points: one value read back
@@ -676,8 +696,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     // going to need them (round 6): the iteration applies the rows, its boxes are built from the rows (bj_build_kernel), and whether
     // it is tried at all is known from the histogram -- so the fit starts as an iteration-only plan's does (3 ms) and falls back to
     // the assembly (62 ms at 24^4: 40 % of such a fit) where the iteration is not tried or gives up.  One rank, no reduction hook.
-    const bool lazy = !p->rows_only && p->pcg && p->solver_mode == 3 && p->rowsop && smooth && p->world <= 1 && !p->ar &&
-                      pcg_boxes_from_rows(p->pcg) && !splpak::opt_get("SPLPAK_PCG_EAGER");
+    const bool lazy = plan_lazy_assembly(p);
     {   // (lazy: the half stencil is cleared when -- if -- it is assembled)
         const long long skip = lazy ? (long long)(p->rhs - p->comm) : 0;
         SPLPAK_HIP_TRY(hipMemsetAsync(p->comm + skip, 0, sizeof(double) * (size_t)(p->lenG + p->lenH - skip), st), SPLPAK_E_NODEVICE);
@@ -689,17 +708,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     SPLPAK_HIP_TRY(launch_bin_points(g, ndata, x, l1xdat, y, w, p->s, p->scalH, st), SPLPAK_E_NODEVICE);
     if (p->pcg) SPLPAK_HIP_TRY(pcg_sum_w2(p, st), SPLPAK_E_NODEVICE);       // (rides the histogram's all-reduce)
     stamp(1);
-    bool rows_fit = p->rows_only || lazy;              // the normal equations are not assembled (yet)
-    auto assemble_now = [&]() -> int {                 // (lazy fits: everything the eager order would have written; same kernels, same bits)
-        SPLPAK_HIP_TRY(hipMemsetAsync(p->comm, 0, sizeof(double) * (size_t)(p->lenG + p->lenH), st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(launch_gram(g, p->s, p->gscratch, p->gscratch_doubles, smooth, p->nst, p->rhs, p->hist, p->scalH, st), SPLPAK_E_NODEVICE);
-        // (the weights of the constraint rows again, from THIS histogram: the rows' one differs from it in the last bits)
-        SPLPAK_HIP_TRY(launch_sparse_mark(g, p->hist, p->scalH, p->xtrap, p->dcw, p->spf, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(launch_constraint_rows(g, p->dcw, p->spf, p->ctab, p->nst, p->scalG, st), SPLPAK_E_NODEVICE);
-        rows_fit = false;
-        p->ne_valid = true;
-        return 0;
-    };
+    const bool rows_fit = p->rows_only || lazy;        // the normal equations are not assembled (yet)
     if (rows_fit) {
         // the histogram from the rows (tile by tile); the right-hand side follows below, when the reduced histogram has gone
         if (smooth) {
@@ -754,6 +763,53 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         set_error("fewer rows than coefficients (suprls 33)");
         return 107;
     }
+    SolveStart a;
+    a.rows_cons = rows_cons;
+    a.sumw2 = hs[SC_COUNT + SC_SUMW2];
+    a.lazy = lazy;
+    a.rows_fit = rows_fit;
+    a.t1 = t1;
+    const int rc = plan_solve_stage(p, st, coef_dev, info, a);
+    // what a refit continues from (splpak_plan_refit_dev)
+    p->geom_valid = rc == 0 && p->fit_valid;
+    p->fit_ndata = ndata;
+    p->fit_rows_data = rows_data;
+    p->fit_rows_cons = rows_cons;
+    p->fit_sumw2 = a.sumw2;
+    return rc;
+}
+
+}  // extern "C"
+
+// The part of a fit that depends on the values: the solve of N z = A^T W^2 y -- by the iteration where the plan has it, by the
+// factorisation otherwise or when the iteration gives up (a lazy plan assembles N first) --, the refinement against the rows, the
+// diagnostics pass and the decisions that end in 107.  p->rhs holds the right-hand side, p->s the binned points.  A refit
+// (a.refit) solves with what the last fit left: the held factor without factoring again, else the iteration on the prepared
+// preconditioner, and the factorisation -- from the binned points, as the fit runs it -- when that gives up.
+static int plan_solve_stage(splpak_plan *p, hipStream_t st, double *coef_dev, double *info, const SolveStart &a)
+{
+    const Grid &g = p->g;
+    const Band &b = p->band;
+    const bool smooth = p->xtrap != 0.0;                              // swght, :769
+    using clk = std::chrono::steady_clock;
+    const auto t1 = a.t1;
+    const bool stamps = p->stats.enabled;
+    auto stamp = [&](int i) { if (stamps) (void)hipEventRecord(p->evStage[i], st); };
+    const bool lazy = a.lazy;
+    const double rows_cons = a.rows_cons;
+    bool rows_fit = a.rows_fit;
+    auto assemble_now = [&]() -> int {                 // (lazy fits: everything the eager order would have written; same kernels, same bits)
+        SPLPAK_HIP_TRY(hipMemsetAsync(p->comm, 0, sizeof(double) * (size_t)(p->lenG + p->lenH), st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(launch_gram(g, p->s, p->gscratch, p->gscratch_doubles, smooth, p->nst, p->rhs, p->hist, p->scalH, st), SPLPAK_E_NODEVICE);
+        // (the weights of the constraint rows again, from THIS histogram: the rows' one differs from it in the last bits)
+        SPLPAK_HIP_TRY(launch_sparse_mark(g, p->hist, p->scalH, p->xtrap, p->dcw, p->spf, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(launch_constraint_rows(g, p->dcw, p->spf, p->ctab, p->nst, p->scalG, st), SPLPAK_E_NODEVICE);
+        rows_fit = false;
+        p->fit_rows = false;                           // (here, not only on success: a refit after a 107 must not assemble again)
+        p->ne_valid = true;
+        p->factor_valid = false;                       // (the Gram scratch may be the factor storage)
+        return 0;
+    };
 
     // ---- solve + refinement, around any solver of N z = v -----------------
     const double inf = std::numeric_limits<double>::infinity();
@@ -817,12 +873,15 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     };
 
     // ---- the iteration (pcg.hip), where the plan has it --------------------
-    bool solved = false;
+    bool solved = false, factored = false;
     auto t2 = t1;
     // Where a factorisation stands behind the iteration, the attempt is skipped in the regime in which it is known to stagnate or
     // crawl (between 0 and ~1.6 constraint rows per column; it works with none and from ~1.7 on)
     bool try_iteration = p->pcg != nullptr;
-    if (try_iteration && p->solver_mode == 3 && !splpak::opt_get("SPLPAK_PCG_ALWAYS")) {
+    // a refit: the held factor; else the iteration if it answered the fit (its preconditioner is prepared)
+    const bool held_factor = a.refit && p->factor_valid;
+    if (a.refit) try_iteration = try_iteration && !held_factor && p->pcg_prepared;
+    else if (try_iteration && p->solver_mode == 3 && !splpak::opt_get("SPLPAK_PCG_ALWAYS")) {
         const double rpc = rows_cons / (double)g.ncol;
         // (a factorisation of seconds -- 24^4: 4.5 s, 28^4: 18 s -- is worth a patient attempt where the iteration only crawls: 24^4 at
         //  1.5 / 1.4 / 1.33 rows per column 1.0 / 2.1 / 3.1 s; at 1.27 it gives up after 2.8 s.  45 TFLOP/s: what the factorisation sustains)
@@ -833,10 +892,11 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
             if (splpak::opt_get("SPLPAK_DEBUG")) fprintf(stderr, "[splpak] %.2f constraint rows per column: the factorisation without an attempt of the iteration\n", rpc);
         }
     }
-    if (lazy && !try_iteration)
+    if (lazy && rows_fit && !try_iteration && !held_factor)
         if (int r = assemble_now()) return r;
-    if (try_iteration) {
-        SPLPAK_HIP_TRY(pcg_prepare(p, p->pcg, hs[SC_COUNT + SC_SUMW2], smooth, rows_fit, st), SPLPAK_E_NODEVICE);
+    if (try_iteration && a.refit) pcg_restart_counts(p->pcg);
+    if (try_iteration && !a.refit) {
+        SPLPAK_HIP_TRY(pcg_prepare(p, p->pcg, a.sumw2, smooth, rows_fit, st), SPLPAK_E_NODEVICE);
         p->pcg_prepared = true;
         if (pcg_singular(p->pcg)) {
             // A box taken out of the ASSEMBLED normal equations -- a principal submatrix of N -- is not positive definite by the pivot
@@ -877,17 +937,25 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     }
 
     // ---- factorisation --------------------------------------------------
-    if (!solved && rows_fit && lazy)
+    if (!solved && rows_fit && lazy && !held_factor)
         if (int r = assemble_now()) return r;
-    if (!solved) {
+    if (held_factor) {
+        if (info) info[4] = p->fit_minpiv;
+        const int r = solve_and_refine([&](double *v, bool) -> int { return plan_factor_solve(p, v, st); });
+        if (r != 0) return r;
+    } else if (!solved) {
         int hinfo = 0;
         double minpiv = 0.0;
+        p->factor_valid = false;
+        factored = true;
         if (int r = plan_factor(p, st, &hinfo, &minpiv, stamps ? p->evStage[4] : nullptr, stamps ? p->evStage[5] : nullptr)) return r;
         t2 = clk::now();
         if (info) {
             info[4] = minpiv;
             info[6] = std::chrono::duration<double>(t2 - t1).count();
         }
+        p->factor_valid = hinfo == 0 && p->world <= 1 && !p->ar && p->dm.R == 1;
+        p->fit_minpiv = minpiv;
         if (hinfo != 0) {
             // not positive definite: the reference's "system is singular" (suprls 34 -> 107)
             SPLPAK_HIP_TRY(hipMemsetAsync(coef_dev, 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
@@ -934,7 +1002,9 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         const int slot[5] = {0, 1, 2, 3, 5};
         for (int i = 0; i < 5; ++i) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, p->evStage[pairs[i][0]], p->evStage[pairs[i][1]]) == hipSuccess) p->stage_ms[slot[i]] = ms;
+            // (a refit records the values gather + right-hand side as stage 1 and bins nothing; it expands only when it factors)
+            if (a.refit && (slot[i] == 0 || slot[i] == 2 || (slot[i] == 3 && !factored))) p->stage_ms[slot[i]] = 0.0;
+            else if (hipEventElapsedTime(&ms, p->evStage[pairs[i][0]], p->evStage[pairs[i][1]]) == hipSuccess) p->stage_ms[slot[i]] = ms;
             else (void)hipGetLastError();
         }
     }
@@ -970,6 +1040,65 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
 #undef SPLPAK_HOOK_TRY
 }
 
+extern "C" {
+
+int32_t splpak_plan_refit_dev(splpak_plan *p, int32_t nfields, const double *ydata_dev, int64_t ldy, double *coef_dev, int64_t ldcoef,
+                              void *stream, double *info)
+{
+    if (!p || !ydata_dev || !coef_dev) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (nfields < 1) { set_error("nfields < 1"); return SPLPAK_E_BADARG; }
+    // nothing to refit: decided here, on the host, before any device work
+    if (p->world > 1 || p->dm.R > 1 || p->ar) { set_error("nothing to refit: the plan is a rank of a sharded or multi-GPU fit"); return SPLPAK_E_UNSUPPORTED; }
+    if (!p->geom_valid) {
+        set_error("nothing to refit: the plan holds no successful fit (none yet, a failed one, or a splpak_debug_plan_solve since): fit first");
+        return SPLPAK_E_UNSUPPORTED;
+    }
+    const Grid &g = p->g;
+    const long long ndata = p->fit_ndata;
+    if (ldy < ndata) { set_error("ldy < ndata of the last fit"); return SPLPAK_E_BADARG; }
+    if (ldcoef < g.ncol) { set_error("ldcoef < number of coefficients"); return SPLPAK_E_BADARG; }
+    OptionsScope opt_scope(&p->opt);
+    hipStream_t st = (hipStream_t)stream;
+    p->comm_failed = false;
+    const bool stamps = p->stats.enabled;
+    if (stamps)
+        for (hipEvent_t &e : p->evStage)
+            if (!e) SPLPAK_HIP_TRY(hipEventCreate(&e), SPLPAK_E_NODEVICE);
+    for (int k = 0; k < nfields; ++k) {
+        double *inf = info ? info + 10 * (size_t)k : nullptr;
+        double *coef_k = coef_dev + (size_t)k * (size_t)ldcoef;
+        if (inf) for (int i = 0; i < 10; ++i) inf[i] = 0.0;
+        // the values and the right-hand side are being replaced: until the field is through, the plan describes no fit
+        p->fit_valid = false;
+        p->geom_valid = false;
+        SolveStart a;
+        a.rows_cons = p->fit_rows_cons;
+        a.sumw2 = p->fit_sumw2;
+        a.lazy = plan_lazy_assembly(p);
+        a.rows_fit = p->fit_rows;
+        a.refit = true;
+        a.t1 = std::chrono::steady_clock::now();
+        if (stamps) (void)hipEventRecord(p->evStage[1], st);
+        SPLPAK_HIP_TRY(launch_regather_values(g, p->s, ndata, ydata_dev + (size_t)k * (size_t)ldy, p->s.ys, st), SPLPAK_E_NODEVICE);
+        // A^T W^2 y: the refinement's pass over the rows at x = 0, without the constraint rows
+        SPLPAK_HIP_TRY(hipMemsetAsync(p->xvec, 0, sizeof(double) * (size_t)p->band.npad, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemsetAsync(p->rhs, 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(plan_rows_residual(p, p->s, p->xvec, false, p->rhs, st), SPLPAK_E_NODEVICE);
+        if (stamps) (void)hipEventRecord(p->evStage[2], st);
+        if (inf) { inf[0] = p->fit_rows_data; inf[1] = p->fit_rows_cons; }
+        const int rc = plan_solve_stage(p, st, coef_k, inf, a);
+        if (rc < 0) return rc;
+        p->geom_valid = true;                  // (107 too: the points, N and the factor or preconditioner are those of the fit still)
+        if (rc != 0) {
+            for (int j = k + 1; j < nfields; ++j)
+                SPLPAK_HIP_TRY(hipMemsetAsync(coef_dev + (size_t)j * (size_t)ldcoef, 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
+            SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+            return rc;
+        }
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // one-shot host entry points
 // ---------------------------------------------------------------------------
@@ -986,8 +1115,11 @@ struct HostFitCache {
     double xmin[MAXD] = {0, 0, 0, 0}, xmax[MAXD] = {0, 0, 0, 0}, xtrap = 0.0;
     double *dx = nullptr, *dy = nullptr, *dw = nullptr, *dc = nullptr;
     long long cap_x = 0, cap_y = 0, cap_w = 0, cap_c = 0;
+    int64_t token = 0;            // of the successful fit the plan holds (splpak_fit_token / splpak_refit_*); 0: none
+    long long ndata = 0;          // its points
     void release()
     {
+        token = 0;
         for (double **q : {&dx, &dy, &dw, &dc}) { if (*q) (void)hipFree(*q); *q = nullptr; }
         cap_x = cap_y = cap_w = cap_c = 0;
         if (plan) splpak_plan_destroy(plan);
@@ -995,6 +1127,8 @@ struct HostFitCache {
     }
 };
 HostFitCache g_hostfit;
+std::atomic<int64_t> g_fit_tokens{0};              // every successful one-shot fit of the process draws a fresh token
+thread_local int64_t t_fit_token = 0;              // of the calling thread's last successful one-shot fit
 }  // namespace
 
 }  // extern "C"
@@ -1010,6 +1144,14 @@ bool splpak::release_cached_plan_for_memory()
     if (!lock.owns_lock() || !g_hostfit.plan) return false;
     g_hostfit.release();
     return true;
+}
+
+void splpak::hostfit_forget_token()
+{
+    t_fit_token = 0;
+    if (t_in_fit_host) return;
+    std::lock_guard<std::mutex> lock(g_hostfit.mu);
+    g_hostfit.token = 0;
 }
 
 extern "C" {
@@ -1042,6 +1184,7 @@ static int32_t fit_host(int32_t ndim, const double *xdata, int32_t l1xdat, const
     (void)hipGetDevice(&dev);
     // the switches are part of the cache key as a whole (a plan keeps the snapshot it was created with)
     const Options cur = options_snapshot();
+    hc.token = 0;                      // (whatever fit the plan held is being replaced)
     bool same = hc.plan && hc.dev == dev && hc.ndim == ndim && hc.xtrap == xtrap && hc.plan->max_ndata >= ndata && hc.plan->opt == cur;
     for (int d = 0; same && d < ndim; ++d)
         same = hc.nodes[d] == nodes[d] && hc.xmin[d] == xmin[d] && hc.xmax[d] == xmax[d];
@@ -1079,7 +1222,80 @@ static int32_t fit_host(int32_t ndim, const double *xdata, int32_t l1xdat, const
         if (!hip_ok(e, "hipMemcpy D2H")) rc = SPLPAK_E_NODEVICE;
     }
     if (rc < 0 || splpak::opt_get("SPLPAK_NO_PLAN_CACHE")) hc.release();
+    if (rc == 0) {                     // (the token is drawn even when nothing stays resident: a refit then says so)
+        t_fit_token = ++g_fit_tokens;
+        if (hc.plan) { hc.token = t_fit_token; hc.ndata = ndata; }
+    }
     return rc;
+}
+
+// New values on the points of the one-shot fit `token`: every field through the cache's staging buffers and the cached plan's
+// refit.  real32: the caller's arrays are floats, widened and narrowed on the host as splpak_fit_f32 does.
+static int32_t refit_host(int64_t token, int32_t nfields, const void *ydata, int64_t ldy, int64_t ndata, void *coef, int64_t ldcoef,
+                          double *info, bool real32)
+{
+    if (!ydata || !coef) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (nfields < 1) { set_error("nfields < 1"); return SPLPAK_E_BADARG; }
+    if (ndata < 1 || ldy < ndata) { set_error("ldy < ndata, or ndata < 1"); return SPLPAK_E_BADARG; }
+    if (int r = device_ready()) return r;
+    HostFitCache &hc = g_hostfit;
+    std::lock_guard<std::mutex> lock(hc.mu);
+    struct InFit { InFit() { t_in_fit_host = true; } ~InFit() { t_in_fit_host = false; } } in_fit;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (token == 0 || !hc.plan || hc.token != token || hc.ndata != ndata || hc.dev != dev || !hc.dy || !hc.dc || hc.cap_y < ndata) {
+        set_error("the fit is no longer resident: fit again (another fit, splpak_shutdown, a release under memory pressure, "
+                  "SPLPAK_NO_PLAN_CACHE or a multi-GPU fit since, or another ndata)");
+        return SPLPAK_E_UNSUPPORTED;
+    }
+    splpak_plan *p = hc.plan;
+    const long long ncol = p->g.ncol;
+    if (ldcoef < ncol) { set_error("ldcoef < number of coefficients"); return SPLPAK_E_BADARG; }
+    std::vector<double> wide;
+    if (real32) wide.resize((size_t)(ndata > ncol ? ndata : ncol));
+    for (int k = 0; k < nfields; ++k) {
+        const double *src = nullptr;
+        if (real32) {
+            const float *yf = static_cast<const float *>(ydata) + (size_t)k * (size_t)ldy;
+            for (long long i = 0; i < ndata; ++i) wide[(size_t)i] = yf[i];
+            src = wide.data();
+        } else
+            src = static_cast<const double *>(ydata) + (size_t)k * (size_t)ldy;
+        if (!hip_ok(hipMemcpy(hc.dy, src, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice), "hipMemcpy H2D")) { hc.release(); return SPLPAK_E_NODEVICE; }
+        int rc = splpak_plan_refit_dev(p, 1, hc.dy, ndata, hc.dc, ncol, nullptr, info ? info + 10 * (size_t)k : nullptr);
+        // (a refusal -- the plan's state or an argument -- leaves the resident fit as it was; a device failure does not)
+        if (rc == SPLPAK_E_UNSUPPORTED || rc == SPLPAK_E_BADARG) return rc;
+        if (rc < 0) { hc.release(); return rc; }
+        double *dst = real32 ? wide.data() : static_cast<double *>(coef) + (size_t)k * (size_t)ldcoef;
+        if (!hip_ok(hipMemcpy(dst, hc.dc, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost), "hipMemcpy D2H")) { hc.release(); return SPLPAK_E_NODEVICE; }
+        if (real32) {
+            float *cf = static_cast<float *>(coef) + (size_t)k * (size_t)ldcoef;
+            for (long long i = 0; i < ncol; ++i) cf[i] = (float)wide[(size_t)i];
+        }
+        if (rc != 0) {                 // 107: the later fields are zeroed, as splpak_plan_refit_dev leaves them
+            for (int j = k + 1; j < nfields; ++j) {
+                if (real32) std::memset(static_cast<float *>(coef) + (size_t)j * (size_t)ldcoef, 0, sizeof(float) * (size_t)ncol);
+                else std::memset(static_cast<double *>(coef) + (size_t)j * (size_t)ldcoef, 0, sizeof(double) * (size_t)ncol);
+                if (info) for (int i = 0; i < 10; ++i) info[10 * (size_t)j + i] = 0.0;
+            }
+            return rc;
+        }
+    }
+    return 0;
+}
+
+int64_t splpak_fit_token(void) { return t_fit_token; }
+
+int32_t splpak_refit_f64(int64_t token, int32_t nfields, const double *ydata, int64_t ldy, int64_t ndata, double *coef, int64_t ldcoef,
+                         double *info)
+{
+    return refit_host(token, nfields, ydata, ldy, ndata, coef, ldcoef, info, false);
+}
+
+int32_t splpak_refit_f32(int64_t token, int32_t nfields, const float *ydata, int64_t ldy, int64_t ndata, float *coef, int64_t ldcoef,
+                         double *info)
+{
+    return refit_host(token, nfields, ydata, ldy, ndata, coef, ldcoef, info, true);
 }
 
 int32_t splpak_fit_f64(int32_t ndim, const double *xdata, int32_t l1xdat, const double *ydata,
@@ -1262,6 +1478,8 @@ int32_t splpak_debug_plan_solve(splpak_plan *p, const double *nst_ref, const dou
     p->comm_failed = false;
     p->ne_valid = false;                  // (the half stencil now holds the caller's matrix)
     p->fit_valid = false;
+    p->geom_valid = false;                // (and the factor storage its factor: nothing to refit)
+    p->factor_valid = false;
     SPLPAK_HIP_TRY(hipMemcpy(p->nst, h.data(), sizeof(double) * nst_n, hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
     SPLPAK_HIP_TRY(hipMemcpy(p->xvec, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);
     if (p->prefit_fn) SPLPAK_HIP_TRY(p->prefit_fn(p, st, p->fn_user), SPLPAK_E_NODEVICE);

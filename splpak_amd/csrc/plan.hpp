@@ -113,6 +113,12 @@ struct splpak_plan {
     bool fit_valid = false;       // the binned points, dcw, spf and rhs are those of a completed single-rank fit (splpak_debug_plan_rows_gradient)
     bool fit_rows = false;        // ... which never assembled the normal equations (a rows-only plan, or a lazy fit the iteration answered)
     bool pcg_prepared = false;    // the last fit prepared the preconditioner (splpak_debug_plan_precondition)
+    // what a refit (splpak_plan_refit_dev) continues from
+    bool geom_valid = false;      // the binned points (xs, ws, idx, offsets), dcw, spf and whatever of N / the preconditioner the last fit built are
+                                  // those of a successful single-rank fit: stays set when a REFIT returns 107 (fit_valid does not)
+    bool factor_valid = false;    // the factor storage holds the factor of these points' N (cleared by whatever rewrites the storage)
+    long long fit_ndata = 0;      // of that fit: its points, row counts, sum of w^2 and the factor's smallest pivot
+    double fit_rows_data = 0, fit_rows_cons = 0, fit_sumw2 = 0, fit_minpiv = 0;
     const char *fn_name = nullptr;                 // what the hooks are (splpak_plan_factorisation); fn_code: 2 two-ended band, 4 nested dissection, 3 distributed band
     int fn_code = 0;
 };
@@ -123,6 +129,8 @@ namespace splpak {
 int build_grid(int ndim, const int *nodes, const double *xmin, const double *xmax, Grid &g, long long *ncol_out,
                bool reorder = false);
 int device_ready();
+// the one-shot entry's refit token (splpak_fit_token): a fit that keeps nothing resident -- a multi-GPU one -- withdraws it
+void hostfit_forget_token();
 // rccl.hip: RCCL for the one-process multi-GPU plan (SPLPAK_MPLAN_RCCL=1)
 int rccl_comms_for_devices(int n, const int *devices, void **comms);      // ncclCommInitAll; 0 or an SPLPAK_E_* code
 int rccl_allreduce_sum(void *comm, double *buf, long long count, hipStream_t st);
@@ -186,6 +194,7 @@ hipError_t pcg_sum_w2(splpak_plan *p, hipStream_t st);
 hipError_t pcg_prepare(splpak_plan *p, PcgState *s, double sumw2, bool smooth, bool from_rows, hipStream_t st);
 bool pcg_boxes_from_rows(const PcgState *s);      // the state can build its boxes from the rows (4-D: the fit may leave the normal equations unassembled)
 int pcg_solve(splpak_plan *p, PcgState *s, double *v, double tol, bool smooth, hipStream_t st);
+void pcg_restart_counts(PcgState *s);             // a refit solves again on the prepared preconditioner: the counters pcg_stats reports start over
 // diagnostics (splpak_debug_plan_precondition / _pcg_tables / _pcg_diagonal): host vectors in the plan's INTERNAL column order.
 // part: 0 the whole preconditioner, 1 its separable part, 2 its boxes (zero when the fit dropped them)
 int pcg_debug_precondition(PcgState *s, int part, const double *r_host, double *z_host);

@@ -21,6 +21,7 @@
 !!    sparse-area histogram exactly as the reference leaves it (:879-907).
 !!  * additive: `evaluate_many` evaluates a batch of points in one kernel launch,
 !!    `evaluate_derivatives` value + gradient (+ Hessian) of a batch in one pass,
+!!    `refit` fits new values on the points of the last `initialize` with the factorisation that fit left on the GPU,
 !!    `last_fit_info` returns the diagnostics of the last fit (the residual norm `reserr` that the
 !!    reference computes, suprls :1693, and drops, splcw :690; row counts; refinement steps).
 !!
@@ -54,6 +55,10 @@ module splpak_module
         integer :: mdim = 0    !! dimension of the last call (the reference keeps scratch here, :95-111)
         real(real64) :: info(10) = 0.0_real64   !! diagnostics of the last fit (include/splpak_hip.h, `info`)
         integer :: ngpus = 1   !! GPUs of this node the fit is spread over (set_gpus)
+        integer(c_int64_t) :: token = 0       !! of the last successful single-GPU `initialize` (splpak_fit_token; 0: nothing to refit)
+        integer(c_int64_t) :: fit_ndata = 0   !! its points
+        integer(c_int64_t) :: fit_ncol = 0    !! its coefficients
+        logical :: fit_fell_to_host = .false. !! the last `initialize` ran on the host for want of a GPU (SPLPAK_HOST_IF_NO_GPU)
 #ifdef REAL128
         logical :: host = .true.    !! quad precision: the host solver is the only path
 #else
@@ -66,6 +71,7 @@ module splpak_module
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
         procedure,public :: evaluate_grid => splpak_eval_grid       !! every point of a tensor-product grid of points (additive)
+        procedure,public :: refit         => splpak_refit           !! new values on the points of the last `initialize` (additive)
         procedure,public :: destroy       => destroy_splpak
         procedure,public :: last_fit_info => splpak_last_fit_info   !! reserr, row counts, ... of the last fit (additive)
         procedure,public,nopass :: set_option => splpak_set_option    !! a named option of the HIP library for the following fits (additive)
@@ -141,6 +147,19 @@ module splpak_module
             real(wp),value :: xtrap
         end function c_fit_multi
 #endif
+        integer(c_int64_t) function c_fit_token() bind(C,name='splpak_fit_token')
+            import :: c_int64_t
+        end function c_fit_token
+#ifdef REAL32
+        integer(c_int32_t) function c_refit(token,nfields,ydata,ldy,ndata,coef,ldcoef,info) bind(C,name='splpak_refit_f32')
+#else
+        integer(c_int32_t) function c_refit(token,nfields,ydata,ldy,ndata,coef,ldcoef,info) bind(C,name='splpak_refit_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr
+            integer(c_int64_t),value :: token, ldy, ndata, ldcoef
+            integer(c_int32_t),value :: nfields
+            type(c_ptr),value :: ydata, coef, info
+        end function c_refit
         subroutine c_shutdown() bind(C,name='splpak_shutdown')
         end subroutine c_shutdown
         integer(c_int32_t) function c_set_default_option(name,val) bind(C,name='splpak_set_default_option')
@@ -165,6 +184,8 @@ module splpak_module
         integer,intent(in),optional :: ndim
         me%mdim = 0
         me%info = 0.0_real64
+        me%token = 0
+        me%fit_fell_to_host = .false.
         if (present(ndim)) then
             me%mdim = ndim
 #ifndef REAL128
@@ -365,6 +386,8 @@ module splpak_module
         integer :: idim
         type(c_ptr) :: hist
         me%mdim = ndim
+        me%token = 0                          ! (whatever this object could refit is being replaced)
+        me%fit_fell_to_host = .false.
         ! the histogram comes back in work(1:ncol) when the caller's array can hold it
         hist = c_null_ptr
         ncol = 1
@@ -392,8 +415,14 @@ module splpak_module
 #endif
         ierror = int(rc)
         if (host_if_no_gpu(ierror)) then
+            me%fit_fell_to_host = .true.
             call fit_on_host(me,ndim,xdata,l1xdat,ydata,wdata,ndata,xmin,xmax,nodes,xtrap,coef,ncf,work,nwrk,ierror)
             return
+        end if
+        if (rc == 0 .and. me%ngpus <= 1) then     ! what `refit` continues from
+            me%token = c_fit_token()
+            me%fit_ndata = int(ndata,c_int64_t)
+            me%fit_ncol = ncol
         end if
         if (rc > 0) then
             call report_fit(ierror)
@@ -402,6 +431,71 @@ module splpak_module
         end if
 #endif
     end subroutine fit_common
+
+    !> New values on the points of this object's last `initialize`: several fields sampled at the same points (the
+    !! components of a velocity, a time series on a fixed sensor layout, bootstrap replicas) cost one `initialize` and one
+    !! `refit` each -- the binning, the normal equations and their factorisation are functions of the points, the weights and
+    !! the grid, and the HIP library keeps them on the device (include/splpak_hip.h, splpak_refit_f64).  The reference has no
+    !! counterpart.  `ydata(ndata,nfields)`: the values, in the point order of that `initialize`; `coef(ncol,nfields)`: one
+    !! set of coefficients per field (`nfields` defaults to 1).  ierror: 0; 107 with the reference's message, as `initialize`;
+    !! -3 for nfields < 1; -4, with a message, when there is nothing to refit on the device: no successful `initialize` of
+    !! this object, another fit of the process since (the library holds one), `destroy`, or an object under set_host,
+    !! set_gpus(n > 1) or with ndim > 4 -- `refit` never falls back to another path silently: call `initialize` per field there.
+    subroutine splpak_refit(me,ydata,coef,ierror,nfields)
+        class(splpak_type),intent(inout),target :: me
+        real(wp),intent(in),target :: ydata(*)
+        real(wp),intent(out),target :: coef(*)
+        integer,intent(out) :: ierror
+        integer,intent(in),optional :: nfields
+        integer :: nf, k
+        integer(c_int32_t) :: rc
+        real(real64),allocatable,target :: info(:,:)
+        nf = 1
+        if (present(nfields)) nf = nfields
+        if (host_takes(me,me%mdim) .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' refit - not available under set_host, set_gpus(n > 1) or for ndim > 4: '// &
+                               'call initialize for every field')
+            return
+        end if
+        rc = -4
+#ifndef REAL128
+        if (nf < 1) then
+            ierror = -3
+            call report(ierror,' refit - NFIELDS is less than 1')
+            return
+        end if
+        if (me%token == 0) then
+            ierror = -4
+            if (me%fit_fell_to_host) then
+                call report(ierror,' refit - the last initialize of this object ran on the host for want of a GPU: '// &
+                                   'call initialize for every field')
+            else
+                call report(ierror,' refit - no successful initialize of this object to refit')
+            end if
+            return
+        end if
+        allocate(info(10,nf))
+        info = 0.0_real64
+        rc = c_refit(me%token, int(nf,c_int32_t), c_loc(ydata), me%fit_ndata, me%fit_ndata, c_loc(coef), me%fit_ncol, c_loc(info))
+        ! last_fit_info: of the last field that was solved -- the last one, or the one that ended in 107 (the fields behind
+        ! it are not run and their diagnostics are zero, row counts included)
+        if (rc == 0 .or. rc == 107) then
+            do k = nf, 1, -1
+                if (info(1,k) > 0.0_real64 .or. k == 1) then
+                    me%info = info(:,k)
+                    exit
+                end if
+            end do
+        end if
+#endif
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'refit')
+        end if
+    end subroutine splpak_refit
 
     !> The fit on the host solver (set_host / REAL128): the reference's argument checks in its order (:716-781), then
     !! splpak_host_solver's banded normal equations.  Same `ierror` codes and messages as the GPU path.
