@@ -136,7 +136,7 @@ typedef struct splpak_plan splpak_plan;
  * equations and the refinement residuals.  A hook installed with
  * splpak_plan_set_allreduce_ex(.., SPLPAK_AR_ANY_POINTER) is also handed front panels,
  * Schur buffers and solve vectors that live in the library's own device allocations
- * (the nested-dissection factorisation distributed by subtrees, csrc/ndchol.hip). */
+ * (the nested-dissection factorisation distributed by subtrees, csrc/ndattach.hip, csrc/ndchol.hip). */
 typedef int32_t (*splpak_allreduce_fn)(void *dev_buf, int64_t count, void *stream, void *user);
 
 /* Validates exactly like splcw (:716-781; 105/106 are checked at fit time) and
@@ -164,7 +164,7 @@ void    splpak_plan_set_allreduce(splpak_plan *plan, splpak_allreduce_fn fn, voi
  * the factorisation is replicated on every rank, as in rounds 1-2.  SPLPAK_AR_ANY_POINTER: the hook accepts ANY device
  * pointer of the calling process (ncclAllReduce does; splpak_plan_set_rccl installs such a hook; the Python shim wraps
  * foreign pointers through the CUDA array interface) -- the nested-dissection factorisation of a sharded fit is then
- * distributed by subtrees (csrc/ndchol.hip; SPLPAK_ND_DIST=0 turns that off) and sums front panels, Schur buffers and
+ * distributed by subtrees (csrc/ndattach.hip, csrc/ndchol.hip; SPLPAK_ND_DIST=0 turns that off) and sums front panels, Schur buffers and
  * solve vectors that live in the library's own allocations.  Returns 0 or a negative status (a failure while the
  * per-rank job tables are rebuilt; the plan's next fit returns it on every rank). */
 #define SPLPAK_AR_ANY_POINTER 1
@@ -297,7 +297,7 @@ void    splpak_plan_stage_timing(const splpak_plan *plan, double *out6);
  *     fronts above them are cut into 256-column blocks dealt to the GPUs in chunks of `chunk` blocks; a solved
  *     panel is copied GPU-to-GPU (hipMemcpyPeerAsync over xGMI) by the owners of the columns it updates, a
  *     child's Schur complement is pulled by the owners of the parent's columns through the peer mapping
- *     (csrc/ndtop.inc).  64^3: 4.4-4.6 GB of factorisation per GPU on eight instead of 30 GB; the 4-D 32^4 grid
+ *     (csrc/ndtop.hip).  64^3: 4.4-4.6 GB of factorisation per GPU on eight instead of 30 GB; the 4-D 32^4 grid
  *     of BASELINE config 5: 159-190 GB per GPU on eight (476 GB of panels do not fit one GPU).  This form needs
  *     peer access between every pair of distinct devices (kernels read the other GPUs' memory): without it the
  *     plan falls back to the distributed band below, or returns SPLPAK_E_UNSUPPORTED when that cannot hold the grid;

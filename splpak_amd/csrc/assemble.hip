@@ -2121,14 +2121,6 @@ inline unsigned grid_for(long long n, int threads, long long maxblocks = 256LL *
 
 }  // namespace
 
-#define DISPATCH_D(ndim, CALL)        \
-    switch (ndim) {                   \
-    case 1: { constexpr int D = 1; CALL; } break; \
-    case 2: { constexpr int D = 2; CALL; } break; \
-    case 3: { constexpr int D = 3; CALL; } break; \
-    default: { constexpr int D = 4; CALL; } break; \
-    }
-
 __global__ void __launch_bounds__(256)
 to_reference_order_kernel(Grid g, const double *__restrict__ xvec, double *__restrict__ coef)
 {

@@ -1,5 +1,5 @@
 // Device pieces of the blocked Cholesky shared by the band factorisation (bandchol.hip) and the nested-dissection
-// multifrontal factorisation (ndchol.hip): the 256x256 diagonal-block factorisation in strip form, the panel solve
+// multifrontal factorisation (ndkernels.hip): the 256x256 diagonal-block factorisation in strip form, the panel solve
 // on the f64 matrix cores, small helpers.  Everything lives in an anonymous namespace: each translation unit gets
 // its own copy, the kernels that wrap these bodies are defined where they are launched.
 #pragma once
@@ -118,7 +118,7 @@ __device__ unsigned long long g_strip_cycles[8];
 #endif
 // A = the diagonal block (A(r,c) = A[r + c*lda], r >= c); k0 only labels the pivot index reported through info.
 // The minimum pivot is tracked with an integer atomic on the bit pattern (positive doubles order like their
-// bits), so that several blocks may be factored by concurrent workgroups (the batched launches of ndchol.hip).
+// bits), so that several blocks may be factored by concurrent workgroups (the batched launches of ndkernels.hip).
 // ncols (1 .. 256): the columns from ncols on are identity padding (a front of the nested-dissection factorisation whose
 // own variables do not fill its last block): strips that hold nothing else are skipped -- their part of L is the identity
 // the assembly left there, and the leaf inverses at the end read it.

@@ -54,4 +54,13 @@ bool hip_ok(hipError_t e, const char *what);
         if (!::splpak::hip_ok((expr), #expr)) return (ret); \
     } while (0)
 
+// CALL with `D` = the grid's number of dimensions as a compile-time constant (the kernels templated on it)
+#define DISPATCH_D(ndim, CALL)        \
+    switch (ndim) {                   \
+    case 1: { constexpr int D = 1; CALL; } break; \
+    case 2: { constexpr int D = 2; CALL; } break; \
+    case 3: { constexpr int D = 3; CALL; } break; \
+    default: { constexpr int D = 4; CALL; } break; \
+    }
+
 }  // namespace splpak

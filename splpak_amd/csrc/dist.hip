@@ -81,7 +81,7 @@ struct MRank {
 
 struct splpak_mplan {
     int R = 1, chunk = 1;
-    splpak::NdGroup *ndgrp = nullptr;       // the grid takes the nested-dissection factorisation (ndchol.hip), distributed over the ranks
+    splpak::NdGroup *ndgrp = nullptr;       // the grid takes the nested-dissection factorisation (ndchol.hip, ndtop.hip), distributed over the ranks
     std::vector<MRank *> ranks;
     Barrier bar;
     std::atomic<int> ready_prog{-1};        // last panel whose "posted" event has been recorded

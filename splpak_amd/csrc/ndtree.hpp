@@ -115,7 +115,7 @@ inline long long nd_schur_ld(const NdFront &f, bool packed) { return packed ? -(
 // halves > 0 (cut = 0 only): the depths 1 .. halves as two half-stages each, by the root's subtrees, interleaved (see nd_schedule)
 void nd_schedule(const NdTree &t, int cut, bool packed, const std::vector<char> *mine, const std::vector<char> *needs, int dlow, NdSchedule &sc, int halves = 0);
 
-// Distribution of the tree over the R GPUs of a one-process multi-GPU fit (round 4; ndchol.hip "top phase"):
+// Distribution of the tree over the R GPUs of a one-process multi-GPU fit (round 4; ndtop.hip, the "top phase"):
 //   * the subtrees below tree depth dcut = ceil(log2 R) are dealt to the ranks (subtree i of the depth-dcut fronts -> rank
 //     i mod R): a rank stores and eliminates ITS subtrees only (panels, Schur buffers, block inverses);
 //   * the fronts above (depth < dcut: "top fronts") are DISTRIBUTED BY BLOCK COLUMNS: a top front is one square lower

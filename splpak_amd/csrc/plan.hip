@@ -256,7 +256,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     // Large 3-D / 4-D grids on one GPU: the nested-dissection multifrontal factorisation (ndchol.hip) instead of the
     // band.  It owns its storage; the factor arena stands in for the band as the home of the Gram scratch.
     // Several GPUs driven by one process (ndgrp): the same factorisation, distributed -- every rank keeps its own subtrees and
-    // its block columns of the fronts above them (round 4; ndchol.hip, ndtop.inc).
+    // its block columns of the fronts above them (round 4; ndchol.hip, ndtop.hip).
     // How the least-squares problem is solved (round 6): a factorisation (band / nested dissection) whenever one fits the device;
     // the iteration of pcg.hip for the grids none fits (4-D from about 29^4 on one GPU) or by request -- SPLPAK_SOLVER =
     // direct | pcg | pcg+direct (the iteration first, the factorisation when it stagnates) | auto.
@@ -268,7 +268,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     if (mode == 0 && g.ndim == 4 && g.ncol >= 160000) mode = 3;
     const bool auto_mode = !named && p->dm.R == 1;      // the plan chose: what does not fit or is not supported is replaced, not reported
     bool direct = mode != 2;
-    const bool use_nd = direct && allow_nd && (p->dm.R == 1 || ndgrp != nullptr) && nd_wanted(g, p->band);
+    const bool use_nd = direct && allow_nd && (p->dm.R == 1 || ndgrp != nullptr) && nd_wanted(g);
     if (use_nd && ok) {
         double *arena = nullptr;
         long long arena_doubles = 0;

@@ -9,7 +9,7 @@
 #include <vector>
 
 namespace splpak {
-// Barrier of the host threads of a one-process multi-GPU fit (one thread per GPU: dist.hip, ndchol.hip).
+// Barrier of the host threads of a one-process multi-GPU fit (one thread per GPU: dist.hip, ndtop.hip).
 struct HostBarrier {
     std::mutex mu;
     std::condition_variable cv;
@@ -40,7 +40,7 @@ struct HostBarrier {
 };
 struct RowsOp;         // the rows of a 4-D fit applied to a vector, tile by tile (rowsop.hip)
 struct PcgState;       // iterative solve of the least-squares problem (pcg.hip)
-struct NdGroup;        // the ranks of a one-process multi-GPU nested-dissection factorisation (ndchol.hip)
+struct NdGroup;        // the ranks of a one-process multi-GPU nested-dissection factorisation (ndstate.hpp, ndtop.hip)
 }  // namespace splpak
 
 struct splpak_plan {
@@ -137,12 +137,12 @@ int rccl_allreduce_sum(void *comm, double *buf, long long count, hipStream_t st)
 void rccl_comm_free(void *comm);
 // plan for rank r of R (chunks of c block columns); R = 1 is the ordinary single-GPU plan
 // ndgrp != NULL (R > 1): the plan is rank r of a one-process multi-GPU fit whose grid takes the nested-dissection
-// factorisation -- distributed over the group's ranks by subtrees and, above them, by block columns (ndchol.hip)
+// factorisation -- distributed over the group's ranks by subtrees and, above them, by block columns (ndchol.hip, ndtop.hip)
 int plan_create_dist(int ndim, const int *nodes, const double *xmin, const double *xmax, double xtrap,
                      long long max_ndata, void *comm_buf_dev, long long comm_len, int R, int r, int c,
                      splpak_plan **plan, bool allow_nd = false, NdGroup *ndgrp = nullptr);
-// large 3-D / 4-D grids on one GPU: nested-dissection multifrontal factorisation (ndchol.hip) instead of the band
-bool nd_wanted(const Grid &g, const Band &band);
+// large 3-D / 4-D grids on one GPU: nested-dissection multifrontal factorisation (ndattach.hip installs it; ndchol.hip) instead of the band
+bool nd_wanted(const Grid &g);
 int nd_attach(splpak_plan *p, double **factor_arena, long long *factor_doubles, NdGroup *grp = nullptr, int rank = 0);
 // One-process multi-GPU fit: the group its ranks' plans share (abort: the fit's abort flag, set when a rank fails).
 // nd_group_finalize: after every rank's plan has been created -- the tables that hold the peers' addresses.
@@ -153,7 +153,7 @@ void nd_group_destroy(NdGroup *g);
 void nd_group_reset(NdGroup *g);
 // the whole-grid test of nd_wanted for a grid given by its nodes (no plan yet)
 bool nd_wanted_for(int ndim, const int *nodes, const double *xmin, const double *xmax);
-// the sharded fit's ranks are known: distribute the nested-dissection factorisation by subtrees (SPLPAK_ND_DIST=1; ndchol.hip)
+// the sharded fit's ranks are known: distribute the nested-dissection factorisation by subtrees (SPLPAK_ND_DIST=1; ndattach.hip)
 int nd_set_ranks(splpak_plan *p, int rank, int world);
 // sum over the ranks of the sharded fit through the caller's hook (plan.hip); 0 = fine (also with one rank)
 int plan_allreduce(splpak_plan *p, double *buf, long long count, hipStream_t st);
@@ -179,7 +179,7 @@ inline hipError_t plan_rows_residual(splpak_plan *p, const SortScratch &rows, co
     if (p->rowsop) return rowsop_apply(p->g, p->rowsop, rows, xvec, p->dcw, p->spf, p->ctab, constraints, rho, st);
     return launch_residual(p->g, rows, xvec, p->rcell, p->dcw, p->spf, p->ctab, constraints, p->tbuf, rho, nullptr, nullptr, st);
 }
-// ndchol.hip: batched Cholesky + triangular inverses of independent dense 256 x 256 blocks
+// ndkernels.hip: batched Cholesky + triangular inverses of independent dense 256 x 256 blocks
 size_t block_chol_job_bytes(int nb);
 hipError_t block_chol_prepare(void *jobs_dev, int nb, double *blocks, double *inv16, double *dinv, double *dinvt, const int *ncols_host);
 hipError_t block_chol_run(const void *jobs_dev, int nb, int *info_dev, double *minpiv_dev, hipStream_t st);

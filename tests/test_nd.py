@@ -1,4 +1,4 @@
-"""Nested-dissection multifrontal factorisation (csrc/ndtree.hip, csrc/ndchol.hip).
+"""Nested-dissection multifrontal factorisation (csrc/ndtree.hip, csrc/ndchol.hip and the csrc/nd*.hip beside it).
 
 CPU tier: the elimination tree is host code -- its invariants (every node owned once, every entry of the
 7^d-stencil normal equations has a row in its column's front, monotone child -> parent maps) are checked

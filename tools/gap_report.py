@@ -6,7 +6,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 nshow = int(sys.argv[2]) if len(sys.argv) > 2 else 25
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 def short(nm):
-    nm = nm.replace("splpak::", "").replace("(anonymous namespace)::", "").replace("void ", "")
+    nm = nm.replace("splpak::nd::", "").replace("splpak::", "").replace("(anonymous namespace)::", "").replace("void ", "")
     return nm.split("(")[0][:44]
 ia = max(i for i, r in enumerate(rows) if "nd_assemble" in r["Kernel_Name"])
 it = min(i for i, r in enumerate(rows) if i > ia and "nd_trinv" in r["Kernel_Name"])

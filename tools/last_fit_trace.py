@@ -11,7 +11,7 @@ end = t0
 busy = 0
 for r in sel:
     s, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
-    nm = r["Kernel_Name"].replace("splpak::", "").replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
+    nm = r["Kernel_Name"].replace("splpak::nd::", "").replace("splpak::", "").replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
     wg = int(r["Grid_Size_X"]) // max(1, int(r["Workgroup_Size_X"]))
     print(f"{(s - t0) / 1e3:9.1f} us  dur {(e - s) / 1e3:8.1f}  gap {(s - end) / 1e3:7.1f}  q={r['Queue_Id']:>2} wg={wg:>6}  {nm[:50]}")
     busy += max(0, e - max(s, end))
