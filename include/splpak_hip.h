@@ -410,6 +410,54 @@ int64_t splpak_eval_grid_scratch_bytes(int32_t ndim, const int64_t *npts);
  * or unsorted axes -- and every 1-D call).  Waits for that call.  Both forms return the same values. */
 int32_t splpak_debug_eval_grid_stats(int64_t out2[2]);
 
+/* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
+ * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one
+ * splpak_eval_* call per field -- each reading the coordinates, building the factor tables and, for a large batch on a
+ * 3-D / 4-D grid, sorting the queries by grid region again.  Here all of that is done once.
+ *   coef   field k has its ncol coefficients at coef + k*ldcoef, ldcoef >= ncol: the layout refit writes;
+ *   out    its nq results go to out + k*ldout, ldout >= nq;
+ *   nderiv one pattern for all fields (NULL: values).
+ * out[k*ldout + i] is the very value splpak_eval_* returns for query i with field k's coefficients (identical bits: the
+ * same factor table and the same sum over the window, field by field; no partial sum is shared between fields).  The
+ * words of `coef` and `out` between the fields are neither read nor written.
+ * Status, decided on the host before any device work, the first failing check wins:
+ *   SPLPAK_E_BADARG       nodes, xmin or xmax null; then nfields < 1, nq < 0 or ldout < nq;
+ *   101, then SPLPAK_E_UNSUPPORTED (ndim > 4), then 102 / 103 as splpak_eval_f64 -- on 101 / 102 / 103 the nq results of
+ *                         every field are set to 0 (if `out` is not null), on the others nothing is written;
+ *   SPLPAK_E_BADARG       ldxq < ndim or ldcoef < ncol;
+ *   nq == 0               0, or 104 for an nderiv outside 0..2; nothing is written;
+ *   SPLPAK_E_BADARG       xq, coef or out null.
+ * 104 is reported but the values are computed with nderiv clamped to 0..2 (:1190-1194).
+ * The host forms stage through the device: (nfields-1)*ldcoef + ncol coefficients go up, the results come back field by field. */
+int32_t splpak_eval_fields_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq, const int32_t *nderiv,
+                               int32_t nfields, const double *coef, int64_t ldcoef,
+                               const double *xmin, const double *xmax, const int32_t *nodes,
+                               double *out, int64_t ldout);
+/* REAL32 storage, arithmetic in double, as splpak_eval_f32 */
+int32_t splpak_eval_fields_f32(int32_t ndim, int64_t nq, const float *xq, int32_t ldxq, const int32_t *nderiv,
+                               int32_t nfields, const float *coef, int64_t ldcoef,
+                               const float *xmin, const float *xmax, const int32_t *nodes,
+                               float *out, int64_t ldout);
+/* the same on resident data (asynchronous on `stream`); nderiv, xmin, xmax and nodes are host arrays */
+int32_t splpak_eval_fields_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq,
+                                   const int32_t *nderiv /* host, may be NULL */,
+                                   int32_t nfields, const double *coef_dev, int64_t ldcoef,
+                                   const double *xmin, const double *xmax, const int32_t *nodes,
+                                   double *out_dev, int64_t ldout, void *stream);
+int32_t splpak_eval_fields_dev_f32(int32_t ndim, int64_t nq, const float *xq_dev, int32_t ldxq,
+                                   const int32_t *nderiv /* host, may be NULL */,
+                                   int32_t nfields, const float *coef_dev, int64_t ldcoef,
+                                   const float *xmin, const float *xmax, const int32_t *nodes,
+                                   float *out_dev, int64_t ldout, void *stream);
+/* Diagnostics: host-side counters of the calling thread's last fields call (no device is asked, nothing is waited for).
+ * out3[0] the route: 0 no call yet, 1 the direct fields kernel (one thread per query, every field's window summed from one
+ *         factor table), 2 the shared sort (queries sorted by grid region once, every field evaluated from LDS tiles),
+ *         3 one single-field evaluation per field (nfields == 1, and large batches on grids the shared sort does not
+ *         take: 2-D, more than 64 (4-D: 256) regions, no room for its scratch);
+ * out3[1] the sorting (place) passes it launched itself: 1 on route 2, else 0;
+ * out3[2] the evaluation kernels it launched: 1 on route 1, nfields on route 2; on route 3 the single-field evaluations. */
+int32_t splpak_debug_eval_fields_stats(int64_t out3[3]);
+
 /* Device-side synthetic inputs of SURVEY 8d (Park-Miller stream, seed 42):
  * points first_point .. first_point+ndata-1; any of the outputs may be NULL.
  * xdata_dev is written with leading dimension ndim.  Queries continue the stream

@@ -33,6 +33,8 @@ SYMBOLS = [
     "splpak_eval_dev_f64", "splpak_eval_dev_f32", "splpak_eval_derivs_f64", "splpak_eval_derivs_f32", "splpak_eval_derivs_dev_f64",
     "splpak_eval_grid_f64", "splpak_eval_grid_f32", "splpak_eval_grid_dev_f64", "splpak_eval_grid_dev_f32",
     "splpak_eval_grid_scratch_bytes", "splpak_debug_eval_grid_stats",
+    "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
+    "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
     "splpak_mplan_create", "splpak_mplan_destroy", "splpak_mplan_device", "splpak_mplan_rank_bytes", "splpak_mplan_factorisation", "splpak_mplan_fit_dev", "splpak_fit_multi_f64",
     "splpak_plan_device_bytes", "splpak_plan_pcg_stats", "splpak_set_default_option", "splpak_plan_set_option", "splpak_plan_get_option",
@@ -147,6 +149,16 @@ def lib() -> C.CDLL:
     L.splpak_eval_grid_scratch_bytes.argtypes = [i32, _lp]
     L.splpak_debug_eval_grid_stats.restype = i32
     L.splpak_debug_eval_grid_stats.argtypes = [_lp]
+    L.splpak_eval_fields_f64.restype = i32
+    L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
+    L.splpak_eval_fields_f32.restype = i32
+    L.splpak_eval_fields_f32.argtypes = [i32, i64, _fp, i32, _ip, i32, _fp, i64, _fp, _fp, _ip, _fp, i64]
+    L.splpak_eval_fields_dev_f64.restype = i32
+    L.splpak_eval_fields_dev_f64.argtypes = [i32, i64, vp, i32, _ip, i32, vp, i64, _dp, _dp, _ip, vp, i64, vp]
+    L.splpak_eval_fields_dev_f32.restype = i32
+    L.splpak_eval_fields_dev_f32.argtypes = [i32, i64, vp, i32, _ip, i32, vp, i64, _fp, _fp, _ip, vp, i64, vp]
+    L.splpak_debug_eval_fields_stats.restype = i32
+    L.splpak_debug_eval_fields_stats.argtypes = [_lp]
     L.splpak_synth_points_f64.restype = i32
     L.splpak_synth_points_f64.argtypes = [i32, i64, i64, vp, vp, vp, vp]
     L.splpak_synth_queries_f64.restype = i32
@@ -435,6 +447,39 @@ def debug_eval_grid_stats():
     return int(v[0]), int(v[1])
 
 
+def evaluate_fields(ndim, xq, nderiv, coefs, xmin, xmax, nodes, real32=False, ldcoef=None, ldout=None):
+    """Several coefficient sets at the same points under one nderiv pattern (splpak_eval_fields_*): `coefs` is (nfields, ncol)
+    or (ncol,), field k in row k.  ldcoef / ldout (>= ncol / nq) are the distances the library is given between the fields'
+    coefficients / results (default: packed); the rows are staged with that padding.  -> (values (nfields, nq), ierror)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    xq = np.ascontiguousarray(xq, dtype=dt)
+    if xq.ndim == 1:
+        xq = xq.reshape(-1, 1)
+    nq, ldx = xq.shape
+    coefs = np.atleast_2d(np.asarray(coefs, dtype=dt))
+    nfields, ncol = coefs.shape
+    ldc = int(ncol if ldcoef is None else ldcoef)
+    ldo = int(nq if ldout is None else ldout)
+    cpad = np.zeros((max(nfields, 1), max(ldc, ncol, 1)), dtype=dt)
+    cpad[:nfields, :ncol] = coefs
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    out = np.zeros((max(nfields, 1), max(ldo, nq, 1)), dtype=dt)
+    fn = lib().splpak_eval_fields_f32 if real32 else lib().splpak_eval_fields_f64
+    rc = _check(fn(ndim, nq, _p(xq, rp), ldx, _p(nd, _ip), int(nfields), _p(cpad, rp), ldc, _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), _p(out, rp), ldo))
+    return out[:nfields, :nq], rc
+
+
+def debug_eval_fields_stats():
+    """(route, place passes, evaluation kernels) of this thread's last fields call -- route: 0 none yet, 1 the direct fields
+    kernel, 2 the shared sort, 3 one single-field evaluation per field.  Host-side counters: nothing is waited for."""
+    v = np.zeros(3, dtype=np.int64)
+    _check(lib().splpak_debug_eval_fields_stats(_p(v, C.POINTER(C.c_int64))))
+    return int(v[0]), int(v[1]), int(v[2])
+
+
 def derivs_nout(ndim, order):
     return 1 + ndim + (ndim * (ndim + 1) // 2 if order == 2 else 0)
 
@@ -698,6 +743,29 @@ def evaluate_dev(ndim, xq, nderiv, coef, xmin, xmax, nodes, out, stream=0):
     return _check(lib().splpak_eval_dev_f64(ndim, int(nq), xq.data_ptr(), int(ldx), _p(nd, _ip),
                                             coef.data_ptr(), _p(xmin, _dp), _p(xmax, _dp),
                                             _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
+
+
+def evaluate_fields_dev(ndim, xq, nderiv, coef, xmin, xmax, nodes, out, stream=0):
+    """Several coefficient sets at the same points on torch device tensors (asynchronous on `stream`): fields are rows --
+    coef (nfields, >= ncol) or (ncol,), out (nfields, >= nq) or (nq,), unit stride inside a row; the row strides are passed as
+    ldcoef / ldout, so the tensor Plan.refit filled can be given as it is.  float32 tensors take the REAL32 entry."""
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    nq, ldx = xq.shape
+    nfields = 1 if coef.dim() == 1 else int(coef.shape[0])
+    ldc = int(coef.shape[0]) if coef.dim() == 1 else int(coef.stride(0))
+    ldo = int(out.shape[0]) if out.dim() == 1 else int(out.stride(0))
+    if any(t.shape[-1] > 1 and t.stride(-1) != 1 for t in (coef, out)):
+        raise SplpakError("evaluate_fields_dev: the coefficients of a field, and its results, must be contiguous")
+    if (out.dim() == 1) != (coef.dim() == 1) or (out.dim() > 1 and int(out.shape[0]) != nfields):
+        raise SplpakError("evaluate_fields_dev: coef and out must name the same number of fields")
+    if int(out.shape[-1]) < int(nq):
+        raise SplpakError("evaluate_fields_dev: out has fewer entries per field than there are queries")
+    real32 = str(xq.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    fn = lib().splpak_eval_fields_dev_f32 if real32 else lib().splpak_eval_fields_dev_f64
+    rp = _fp if real32 else _dp
+    return _check(fn(ndim, int(nq), xq.data_ptr(), int(ldx), _p(nd, _ip), nfields, coef.data_ptr(), ldc, _p(xmin, rp), _p(xmax, rp),
+                     _p(nodes, _ip), out.data_ptr(), ldo, C.c_void_p(stream)))
 
 
 def evaluate_grid_dev(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, stream=0):

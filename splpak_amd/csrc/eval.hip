@@ -53,6 +53,54 @@ eval_kernel(Grid g, long long nq, const T *__restrict__ xq, int ldxq, NDeriv nd,
     }
 }
 
+// Several coefficient sets at the same queries (splpak_eval_fields_*): field k's coefficients at coef + k*ldcoef, its results at
+// out + k*ldout.  A thread reads its coordinates and builds its factor table once, then sums the window once per field with
+// eval_kernel's row loads and window_sum's arithmetic -- nothing is shared between the fields, so every field has the bits of
+// its own eval_kernel call.  Up to 3-D two fields at a time: their sums are independent, so the gathers of one are in flight
+// while the other is multiplied.  4-D one at a time: beside the 32 registers of its table a pair of 256-coefficient windows
+// takes the whole register file (256 VGPRs, one wave per SIMD, against the 70 of eval_kernel).
+template <int D, typename T, bool VAL>
+__global__ void __launch_bounds__(256)
+eval_fields_kernel(Grid g, long long nq, const T *__restrict__ xq, int ldxq, NDeriv nd, int nfields, const T *__restrict__ coef,
+                   long long ldcoef, T *__restrict__ out, long long ldout)
+{
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += stride) {
+        double b[D][4];
+        int base = 0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const double x = (double)xq[i * ldxq + d];
+            const int ws = eval_table<VAL>(g, d, x, nd.v[d], b[d]);
+            base += ws * g.colstride[d];
+        }
+        const int s1 = D > 1 ? g.colstride[1] : 0, s2 = D > 2 ? g.colstride[2] : 0, s3 = D > 3 ? g.colstride[3] : 0;
+        auto field = [&](const T *__restrict__ cf) {
+            return window_sum<D>(b, [&](int k1, int k2, int k3, double (&c)[4]) {
+                const long long idx = base + k1 * s1 + k2 * s2 + k3 * s3;
+                if constexpr (sizeof(T) == 8) {
+                    typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
+                    const d2v lo = *reinterpret_cast<const d2v *>(cf + idx);
+                    const d2v hi = *reinterpret_cast<const d2v *>(cf + idx + 2);
+                    c[0] = lo[0]; c[1] = lo[1]; c[2] = hi[0]; c[3] = hi[1];
+                } else {
+                    typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
+                    const f4v v = *reinterpret_cast<const f4v *>(cf + idx);
+                    c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
+                }
+            });
+        };
+        int k = 0;
+        for (; D < 4 && k + 1 < nfields; k += 2) {
+            const T *c0 = coef + (long long)k * ldcoef;
+            const double sum0 = field(c0), sum1 = field(c0 + ldcoef);
+            out[(long long)k * ldout + i] = (T)sum0;
+            out[(long long)(k + 1) * ldout + i] = (T)sum1;
+        }
+        for (; k < nfields; ++k) out[(long long)k * ldout + i] = (T)field(coef + (long long)k * ldcoef);      // (up to 3-D: the odd one)
+    }
+}
+
 template <int D, int ORDER, typename T>
 __global__ void __launch_bounds__(256)
 eval_derivs_kernel(Grid g, long long nq, const T *__restrict__ xq, int ldxq, const T *__restrict__ coef,
@@ -99,6 +147,15 @@ void set_eval_mode(int mode, long long chunk)
 {
     g_eval_mode = mode;
     g_eval_chunk = chunk;
+}
+
+// the calling thread's last fields call: route (0 none yet, 1 direct fields kernel, 2 shared sort, 3 one launch_eval per field),
+// place passes launched, evaluation-kernel launches
+static thread_local long long g_fields_stats[3] = {0, 0, 0};
+
+void eval_fields_stats(long long out3[3])
+{
+    for (int j = 0; j < 3; ++j) out3[j] = g_fields_stats[j];
 }
 
 void eval_scratch_shutdown()
@@ -196,5 +253,65 @@ hipError_t launch_eval(const Grid &g, long long nq, const T *xq, int ldxq, const
 }
 template hipError_t launch_eval<double>(const Grid &, long long, const double *, int, const int *, const double *, double *, hipStream_t);
 template hipError_t launch_eval<float>(const Grid &, long long, const float *, int, const int *, const float *, float *, hipStream_t);
+
+// Several fields at the same queries.  One field: launch_eval itself.  A batch launch_eval would sort: the persistent region
+// path sorts it once for all fields; where that path does not apply (2-D, too many regions, no room for its scratch -- it says so
+// before it launches anything) every field takes launch_eval on its own, so that the run path and the region sort serve those
+// grids as they do for one field.  Everything else: the direct fields kernel.
+template <typename T>
+hipError_t launch_eval_fields(const Grid &g, long long nq, const T *xq, int ldxq, const int *nderiv, int nfields, const T *coef,
+                              long long ldcoef, T *out, long long ldout, hipStream_t st)
+{
+    long long (&stats)[3] = g_fields_stats;
+    stats[0] = stats[1] = stats[2] = 0;
+    if (nq <= 0 || nfields < 1) return hipSuccess;
+    // (route 3 counts the launch_eval calls; what these sort and launch is theirs)
+    auto per_field = [&]() {
+        stats[0] = 3;
+        for (int k = 0; k < nfields; ++k) {
+            const hipError_t e = launch_eval<T>(g, nq, xq, ldxq, nderiv, coef + (long long)k * ldcoef, out + (long long)k * ldout, st);
+            if (e != hipSuccess) return e;
+            ++stats[2];
+        }
+        return hipSuccess;
+    };
+    if (nfields == 1) return per_field();
+    const NDeriv nd = clamp_nderiv(nderiv, g.ndim);
+    if (want_binned(g, nq)) {
+        Regions rg;
+        if (make_regions(g, rg)) {
+            const hipError_t e = eval_persistent<T>(g, nq, xq, ldxq, nd, coef, out, st, nfields, ldcoef, ldout);
+            if (e != hipErrorNotSupported) {
+                stats[0] = 2;
+                stats[1] = 1;
+                stats[2] = nfields;
+                return e;
+            }
+        }
+        return per_field();
+    }
+    const int threads = 256;
+    long long blocks = (nq + threads - 1) / threads;
+    if (blocks > 256LL * 32) blocks = 256LL * 32;   // grid-stride the rest
+    dim3 gr((unsigned)blocks), bl(threads);
+    const bool plain = value_only(nd);
+#define SPLPAK_EVAL_FIELDS(DD) \
+    hipLaunchKernelGGL((plain ? eval_fields_kernel<DD, T, true> : eval_fields_kernel<DD, T, false>), gr, bl, 0, st, g, nq, xq, ldxq, nd, nfields, \
+                       coef, ldcoef, out, ldout);
+    switch (g.ndim) {
+    case 1: SPLPAK_EVAL_FIELDS(1) break;
+    case 2: SPLPAK_EVAL_FIELDS(2) break;
+    case 3: SPLPAK_EVAL_FIELDS(3) break;
+    default: SPLPAK_EVAL_FIELDS(4) break;
+    }
+#undef SPLPAK_EVAL_FIELDS
+    stats[0] = 1;
+    stats[2] = 1;
+    return hipGetLastError();
+}
+template hipError_t launch_eval_fields<double>(const Grid &, long long, const double *, int, const int *, int, const double *, long long, double *,
+                                               long long, hipStream_t);
+template hipError_t launch_eval_fields<float>(const Grid &, long long, const float *, int, const int *, int, const float *, long long, float *,
+                                              long long, hipStream_t);
 
 }  // namespace splpak

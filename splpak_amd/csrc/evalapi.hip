@@ -2,7 +2,7 @@
 // pointers, the evaluation mode, and the host-only / synthetic-data helpers that need no plan.
 //
 // Every entry family has ONE ladder of argument checks (point_validate for the value and the derivative entries,
-// grid_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
+// fields_validate, grid_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
 // Where two entries of a family have always answered differently, the difference is a named parameter of the ladder.
 #include "plan.hpp"
 #include "basis.hpp"
@@ -193,6 +193,120 @@ int32_t splpak_eval_derivs_dev_f64(int32_t ndim, int64_t nq, const double *xq_de
                                    void *stream)
 {
     return eval_dev<double>(true, ndim, nq, xq_dev, ldxq, nullptr, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, stream, /*zero_101=*/true);
+}
+
+}  // extern "C"
+
+// ---- several coefficient sets at the same points (eval.hip launch_eval_fields): field k's coefficients at coef + k*ldcoef,
+// its nq results at out + k*ldout, one nderiv pattern for all ----
+// The checks of a fields entry before it touches a device, in the order the header gives.  True: the caller goes on to compute and
+// returns rc (0 or 104) afterwards; false: rc is the status to return and `zero` says whether the nq results of every field are
+// zeroed first (101 / 102 / 103; the words between the fields stay as they are).
+template <typename T>
+static bool fields_validate(int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, const int32_t *nderiv, int32_t nfields, const T *coef,
+                            int64_t ldcoef, const T *xmin_t, const T *xmax_t, const int32_t *nodes, const T *out, int64_t ldout, Grid &g,
+                            int &rc, bool &zero)
+{
+    zero = false;
+    if (!nodes || !xmin_t || !xmax_t) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (nfields < 1 || nq < 0 || ldout < nq) { set_error("nfields < 1, nq < 0 or ldout smaller than nq"); rc = SPLPAK_E_BADARG; return false; }
+    double xmin[MAXD], xmax[MAXD];
+    long long zero_n = 0;
+    if (!grid_args(ndim, xmin_t, xmax_t, nodes, 1, xmin, xmax, rc, zero_n)) { zero = zero_n > 0; return false; }
+    rc = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
+    if (rc != 0 && rc != 104) {
+        zero = rc > 0;
+        return false;
+    }
+    if (ldxq < ndim || ldcoef < g.ncol) { set_error("ldxq smaller than ndim or ldcoef smaller than the number of coefficients"); rc = SPLPAK_E_BADARG; return false; }
+    if (nq == 0) return false;
+    if (!xq || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (int r = device_ready()) { rc = r; return false; }
+    return true;
+}
+
+template <typename T>
+static int32_t eval_fields_dev(int32_t ndim, int64_t nq, const T *xq_dev, int32_t ldxq, const int32_t *nderiv, int32_t nfields, const T *coef_dev,
+                               int64_t ldcoef, const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, int64_t ldout, void *stream)
+{
+    Grid g;
+    int rc = 0;
+    bool zero = false;
+    if (!fields_validate(ndim, nq, xq_dev, ldxq, nderiv, nfields, coef_dev, ldcoef, xmin, xmax, nodes, out_dev, ldout, g, rc, zero)) {
+        if (zero && out_dev && nq > 0)
+            for (int32_t k = 0; k < nfields; ++k) (void)hipMemsetAsync(out_dev + (long long)k * ldout, 0, sizeof(T) * (size_t)nq, (hipStream_t)stream);
+        return rc;
+    }
+    SPLPAK_HIP_TRY(launch_eval_fields<T>(g, nq, xq_dev, ldxq, nderiv, nfields, coef_dev, ldcoef, out_dev, ldout, (hipStream_t)stream),
+                   SPLPAK_E_NODEVICE);
+    return rc;
+}
+
+// the host form stages through the device as staged_call does: the coefficients of all fields with the caller's ldcoef in one
+// copy, the results packed (nq apart) and copied back field by field, so that the caller's words between the fields keep their contents
+template <typename T>
+static int32_t eval_fields_host(int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, const int32_t *nderiv, int32_t nfields, const T *coef,
+                                int64_t ldcoef, const T *xmin, const T *xmax, const int32_t *nodes, T *out, int64_t ldout)
+{
+    Grid g;
+    int rc = 0;
+    bool zero = false;
+    if (!fields_validate(ndim, nq, xq, ldxq, nderiv, nfields, coef, ldcoef, xmin, xmax, nodes, out, ldout, g, rc, zero)) {
+        if (zero && out)
+            for (int32_t k = 0; k < nfields; ++k)
+                for (int64_t i = 0; i < nq; ++i) out[(long long)k * ldout + i] = (T)0;
+        return rc;
+    }
+    const size_t n_in = (size_t)nq * ldxq, n_coef = (size_t)(nfields - 1) * (size_t)ldcoef + (size_t)g.ncol, n_out = (size_t)nfields * (size_t)nq;
+    DevStage stage;
+    T *din = nullptr, *dc = nullptr, *dout = nullptr;
+    if (!stage.alloc(&din, n_in) || !stage.alloc(&dc, n_coef) || !stage.alloc(&dout, n_out)) return SPLPAK_E_NOMEM;
+    hipError_t e = hipMemcpy(din, xq, sizeof(T) * n_in, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * n_coef, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_eval_fields<T>(g, nq, din, ldxq, nderiv, nfields, dc, ldcoef, dout, nq, nullptr);
+    for (int32_t k = 0; k < nfields && e == hipSuccess; ++k)
+        e = hipMemcpy(out + (long long)k * ldout, dout + (long long)k * nq, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost);
+    return hip_ok(e, "evaluation of several fields") ? rc : SPLPAK_E_NODEVICE;
+}
+
+extern "C" {
+
+int32_t splpak_eval_fields_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq, const int32_t *nderiv, int32_t nfields,
+                               const double *coef, int64_t ldcoef, const double *xmin, const double *xmax, const int32_t *nodes,
+                               double *out, int64_t ldout)
+{
+    return eval_fields_host<double>(ndim, nq, xq, ldxq, nderiv, nfields, coef, ldcoef, xmin, xmax, nodes, out, ldout);
+}
+
+int32_t splpak_eval_fields_f32(int32_t ndim, int64_t nq, const float *xq, int32_t ldxq, const int32_t *nderiv, int32_t nfields,
+                               const float *coef, int64_t ldcoef, const float *xmin, const float *xmax, const int32_t *nodes,
+                               float *out, int64_t ldout)
+{
+    return eval_fields_host<float>(ndim, nq, xq, ldxq, nderiv, nfields, coef, ldcoef, xmin, xmax, nodes, out, ldout);
+}
+
+int32_t splpak_eval_fields_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq, const int32_t *nderiv, int32_t nfields,
+                                   const double *coef_dev, int64_t ldcoef, const double *xmin, const double *xmax, const int32_t *nodes,
+                                   double *out_dev, int64_t ldout, void *stream)
+{
+    return eval_fields_dev<double>(ndim, nq, xq_dev, ldxq, nderiv, nfields, coef_dev, ldcoef, xmin, xmax, nodes, out_dev, ldout, stream);
+}
+
+int32_t splpak_eval_fields_dev_f32(int32_t ndim, int64_t nq, const float *xq_dev, int32_t ldxq, const int32_t *nderiv, int32_t nfields,
+                                   const float *coef_dev, int64_t ldcoef, const float *xmin, const float *xmax, const int32_t *nodes,
+                                   float *out_dev, int64_t ldout, void *stream)
+{
+    return eval_fields_dev<float>(ndim, nq, xq_dev, ldxq, nderiv, nfields, coef_dev, ldcoef, xmin, xmax, nodes, out_dev, ldout, stream);
+}
+
+// host-side counters of the calling thread's last fields call (no device is asked)
+int32_t splpak_debug_eval_fields_stats(int64_t out3[3])
+{
+    if (!out3) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    long long v[3];
+    eval_fields_stats(v);
+    for (int j = 0; j < 3; ++j) out3[j] = v[j];
+    return 0;
 }
 
 }  // extern "C"

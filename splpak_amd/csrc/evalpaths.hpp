@@ -23,9 +23,12 @@ hipError_t eval_runs(const Grid &g, const Regions &rg, long long nq, const T *xq
                      long long chunk, hipStream_t st);
 void eval_runs_shutdown();
 
-// evalregion.hip -- hipErrorNotSupported = not for this grid, or no room for its scratch: take the run path
+// evalregion.hip -- hipErrorNotSupported = not for this grid, or no room for its scratch: take the run path (decided before
+// anything is launched).  nfields > 1: field k's coefficients at coef + k*ldcoef, its results to out + k*ldout, ONE sort of the
+// queries for all of them
 template <typename T>
-hipError_t eval_persistent(const Grid &g, long long nq, const T *xq, int ldxq, const NDeriv &nd, const T *coef, T *out, hipStream_t st);
+hipError_t eval_persistent(const Grid &g, long long nq, const T *xq, int ldxq, const NDeriv &nd, const T *coef, T *out, hipStream_t st,
+                           int nfields = 1, long long ldcoef = 0, long long ldout = 0);
 void eval_persistent_shutdown();
 
 }  // namespace splpak

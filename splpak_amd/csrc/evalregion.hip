@@ -903,8 +903,11 @@ static thread_local int g_pscratch_ncu = 0;         // compute units of the devi
 
 void eval_persistent_shutdown() { g_pscratch.release(); }
 
+// nfields coefficient sets (ldcoef apart) at the same queries, results ldout apart: the place pass runs ONCE, then every field
+// takes the evaluation and the unsort pass in stream order (an evaluation pass consumes the chunk counters: cleared per field)
 template <int D, typename T>
-static hipError_t eval_persistent_d(const Grid &g, long long nq, const T *xq, int ldxq, const NDeriv &nd, const T *coef, T *out, hipStream_t st)
+static hipError_t eval_persistent_d(const Grid &g, long long nq, const T *xq, int ldxq, const NDeriv &nd, const T *coef, T *out, hipStream_t st,
+                                    int nfields, long long ldcoef, long long ldout)
 {
     // regions of 16 window starts per dimension (tiles of 19^3 = 55 KB: 64^3 nodes give 4 x 4 x 4 regions), of 8 for smaller grids
     PRegions rg;
@@ -945,34 +948,44 @@ static hipError_t eval_persistent_d(const Grid &g, long long nq, const T *xq, in
         int v = 0;
         g_pscratch_ncu = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
     }
-    // (chunks of 4 place-pass workgroups of interior runs, 16 of boundary runs: ~400 queries; the waves of a workgroup take
-    //  them from a counter in LDS, so small chunks cost nothing and keep the tails short)
     const dim3 grid((unsigned)g_pscratch_ncu);
-    if constexpr (D == 4) {
-        // chunks of 32 place-pass workgroups of one bin: ~500 queries (a chunk's runs sit one per lane: at most 64)
-        const int c0 = 32;
-        hipLaunchKernelGGL((plain ? pr_eval4_kernel<8, true, T> : pr_eval4_kernel<8, false, T>), grid, dim3(PR4_EW), 0, st, g, rg, nd, coef,
-                           (const T *)xs, (const unsigned char *)scls, (const int *)starts, nwg, c0, claim, outs);
-    } else {
-        const int c0 = 4;
-        hipLaunchKernelGGL((sper == 16 ? (plain ? pr_eval_kernel<D, 16, true, T> : pr_eval_kernel<D, 16, false, T>)
-                                       : (plain ? pr_eval_kernel<D, 8, true, T> : pr_eval_kernel<D, 8, false, T>)),
-                           grid, dim3(PR_EW), 0, st, g, rg, nd, coef, (const T *)xs, (const int *)starts, nwg, c0, claim, outs);
+    for (int k = 0; k < nfields; ++k) {
+        const T *coefk = coef + (long long)k * ldcoef;
+        if (k > 0) {
+            e = hipMemsetAsync(claim, 0, sizeof(int) * 2 * PR_MAXBINS, st);
+            if (e != hipSuccess) break;
+        }
+        if constexpr (D == 4) {
+            // chunks of 32 place-pass workgroups of one bin: ~500 queries (a chunk's runs sit one per lane: at most 64)
+            const int c0 = 32;
+            hipLaunchKernelGGL((plain ? pr_eval4_kernel<8, true, T> : pr_eval4_kernel<8, false, T>), grid, dim3(PR4_EW), 0, st, g, rg, nd, coefk,
+                               (const T *)xs, (const unsigned char *)scls, (const int *)starts, nwg, c0, claim, outs);
+        } else {
+            // (chunks of 4 place-pass workgroups of interior runs, 16 of boundary runs: ~400 queries; the waves of a workgroup
+            //  take them from a counter in LDS, so small chunks cost nothing and keep the tails short)
+            const int c0 = 4;
+            hipLaunchKernelGGL((sper == 16 ? (plain ? pr_eval_kernel<D, 16, true, T> : pr_eval_kernel<D, 16, false, T>)
+                                           : (plain ? pr_eval_kernel<D, 8, true, T> : pr_eval_kernel<D, 8, false, T>)),
+                               grid, dim3(PR_EW), 0, st, g, rg, nd, coefk, (const T *)xs, (const int *)starts, nwg, c0, claim, outs);
+        }
+        hipLaunchKernelGGL((pr_unsort_kernel<T>), dim3((unsigned)nwg), dim3(PR_NT), 0, st, nq, (const unsigned short *)sidx, (const int *)starts,
+                           2 * rg.nbins + 1, (const T *)outs, out + (long long)k * ldout);
     }
-    hipLaunchKernelGGL((pr_unsort_kernel<T>), dim3((unsigned)nwg), dim3(PR_NT), 0, st, nq, (const unsigned short *)sidx, (const int *)starts,
-                       2 * rg.nbins + 1, (const T *)outs, out);
     (void)s.mark_used(st);
-    return hipGetLastError();
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 template <typename T>
-hipError_t eval_persistent(const Grid &g, long long nq, const T *xq, int ldxq, const NDeriv &nd, const T *coef, T *out, hipStream_t st)
+hipError_t eval_persistent(const Grid &g, long long nq, const T *xq, int ldxq, const NDeriv &nd, const T *coef, T *out, hipStream_t st,
+                           int nfields, long long ldcoef, long long ldout)
 {
-    if (g.ndim == 3) return eval_persistent_d<3, T>(g, nq, xq, ldxq, nd, coef, out, st);
-    if (g.ndim == 4) return eval_persistent_d<4, T>(g, nq, xq, ldxq, nd, coef, out, st);
+    if (g.ndim == 3) return eval_persistent_d<3, T>(g, nq, xq, ldxq, nd, coef, out, st, nfields, ldcoef, ldout);
+    if (g.ndim == 4) return eval_persistent_d<4, T>(g, nq, xq, ldxq, nd, coef, out, st, nfields, ldcoef, ldout);
     return hipErrorNotSupported;
 }
-template hipError_t eval_persistent<double>(const Grid &, long long, const double *, int, const NDeriv &, const double *, double *, hipStream_t);
-template hipError_t eval_persistent<float>(const Grid &, long long, const float *, int, const NDeriv &, const float *, float *, hipStream_t);
+template hipError_t eval_persistent<double>(const Grid &, long long, const double *, int, const NDeriv &, const double *, double *, hipStream_t, int,
+                                            long long, long long);
+template hipError_t eval_persistent<float>(const Grid &, long long, const float *, int, const NDeriv &, const float *, float *, hipStream_t, int,
+                                           long long, long long);
 
 }  // namespace splpak

@@ -14,6 +14,14 @@ bool release_cached_plan_for_memory();
 // the coefficients and the results (the arithmetic is double)
 template <typename T>
 hipError_t launch_eval(const Grid &g, long long nq, const T *xq, int ldxq, const int *nderiv, const T *coef, T *out, hipStream_t st);
+// nfields coefficient sets at the same queries under one nderiv pattern: field k's coefficients at coef + k*ldcoef, its nq
+// results to out + k*ldout, each the bits of launch_eval on that field
+template <typename T>
+hipError_t launch_eval_fields(const Grid &g, long long nq, const T *xq, int ldxq, const int *nderiv, int nfields, const T *coef,
+                              long long ldcoef, T *out, long long ldout, hipStream_t st);
+// the calling thread's last launch_eval_fields: route (0 none yet, 1 direct fields kernel, 2 shared sort, 3 launch_eval per
+// field) [0], place passes [1] and evaluation kernels [2] it launched (route 3: the launch_eval calls)
+void eval_fields_stats(long long out3[3]);
 // value + gradient (order 1) (+ Hessian upper triangle, order 2) per query, ldout apart
 template <typename T>
 hipError_t launch_eval_derivs(const Grid &g, long long nq, const T *xq, int ldxq, int order, const T *coef, T *out, int ldout,

@@ -22,6 +22,7 @@
 !!  * additive: `evaluate_many` evaluates a batch of points in one kernel launch,
 !!    `evaluate_derivatives` value + gradient (+ Hessian) of a batch in one pass,
 !!    `refit` fits new values on the points of the last `initialize` with the factorisation that fit left on the GPU,
+!!    `evaluate_fields` evaluates several coefficient sets (what `refit` returns) at the same batch of points in one call,
 !!    `last_fit_info` returns the diagnostics of the last fit (the residual norm `reserr` that the
 !!    reference computes, suprls :1693, and drops, splcw :690; row counts; refinement steps).
 !!
@@ -71,6 +72,7 @@ module splpak_module
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
         procedure,public :: evaluate_grid => splpak_eval_grid       !! every point of a tensor-product grid of points (additive)
+        procedure,public :: evaluate_fields => splpak_eval_fields   !! several coefficient sets at the same batch of points (additive)
         procedure,public :: refit         => splpak_refit           !! new values on the points of the last `initialize` (additive)
         procedure,public :: destroy       => destroy_splpak
         procedure,public :: last_fit_info => splpak_last_fit_info   !! reserr, row counts, ... of the last fit (additive)
@@ -85,6 +87,7 @@ module splpak_module
         procedure,private :: splde_many
         procedure,private :: splpak_derivs_many
         procedure,private :: splpak_eval_grid
+        procedure,private :: splpak_eval_fields
     end type splpak_type
 
 #ifndef REAL128
@@ -137,6 +140,18 @@ module splpak_module
             integer(c_int32_t),value :: ndim
             type(c_ptr),value :: npts, axes, nderiv, coef, xmin, xmax, nodes, out
         end function c_eval_grid
+#ifdef REAL32
+        integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
+                                                  bind(C,name='splpak_eval_fields_f32')
+#else
+        integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
+                                                  bind(C,name='splpak_eval_fields_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr
+            integer(c_int32_t),value :: ndim, ldxq, nfields
+            integer(c_int64_t),value :: nq, ldcoef, ldout
+            type(c_ptr),value :: xq, nderiv, coef, xmin, xmax, nodes, out
+        end function c_eval_fields
 #ifndef REAL32
         integer(c_int32_t) function c_fit_multi(ngpus,ndim,xdata,l1xdat,ydata,wdata,ndata,xmin,xmax,nodes,xtrap,&
                                                 coef,ncf,nwrk,hist,info) bind(C,name='splpak_fit_multi_f64')
@@ -858,6 +873,69 @@ module splpak_module
             if (ierror < 0) call report_library_failure(ierror,'evaluate_grid')
         end select
     end subroutine splpak_eval_grid
+
+    !> Several coefficient sets at the same batch of points -- the evaluation half of `refit`: f(i,k) is the spline of
+    !! coef(:,k) (with `nderiv`, that partial derivative) at x(:,i), the very value `evaluate_many` returns for that field.
+    !! coef is coef(ldcoef,nfields) as `refit` fills it, f is f(ldf,nfields) with ldf >= nq; rows of f beyond nq are not
+    !! touched.  One call of the HIP library (splpak_eval_fields_f64: coordinates read, factor tables built and, for large
+    !! batches, queries sorted once for all fields); under set_host(.true.), in the -DREAL128 build, for ndim > 4 or with
+    !! SPLPAK_HOST_IF_NO_GPU=1 the module's host evaluation field by field, as in evaluate_many.
+    !! ierror: 101..104 as splde (104: computed with nderiv clamped), -3 for nfields < 1, nq < 0 or a leading dimension too small.
+    subroutine splpak_eval_fields(me,ndim,nq,x,ldx,nfields,coef,ldcoef,xmin,xmax,nodes,f,ldf,ierror,nderiv)
+        class(splpak_type),intent(inout) :: me
+        integer,intent(in) :: ndim, nq, ldx, nfields, ldcoef, ldf
+        real(wp),intent(in),target :: x(ldx,*)
+        real(wp),intent(in),target :: coef(ldcoef,*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(inout),target :: f(ldf,*)
+        integer,intent(out) :: ierror
+        integer,intent(in),optional,target :: nderiv(*)
+        integer(c_int32_t) :: rc
+        integer :: k, ie, idim, ncol
+        type(c_ptr) :: pd
+        me%mdim = ndim
+        rc = 0
+        pd = c_null_ptr
+        if (present(nderiv)) pd = c_loc(nderiv)
+#ifndef REAL128
+        if (.not. (host_takes(me,ndim) .and. ndim >= 1)) &
+            rc = c_eval_fields(int(ndim,c_int32_t), int(nq,c_int64_t), c_loc(x), int(ldx,c_int32_t), pd, int(nfields,c_int32_t), &
+                               c_loc(coef), int(ldcoef,c_int64_t), c_loc(xmin), c_loc(xmax), c_loc(nodes), c_loc(f), int(ldf,c_int64_t))
+#endif
+        if ((host_takes(me,ndim) .or. host_if_no_gpu(int(rc))) .and. ndim >= 1) then   ! host solver: evaluate_many's host loop per field
+            ierror = 0
+            ncol = 1
+            do idim = 1, ndim
+                ncol = ncol*max(nodes(idim),1)
+            end do
+            if (nfields < 1 .or. nq < 0 .or. ldf < nq .or. ldx < ndim .or. ldcoef < ncol) then
+                ierror = -3
+                call report(ierror,' evaluate_fields - NFIELDS < 1, NQ < 0 or a leading dimension is too small')
+                return
+            end if
+            do k = 1, nfields
+                call eval_common(me,ndim,int(nq,c_int64_t),c_loc(x),ldx,pd,c_loc(coef(1,k)),c_loc(xmin),c_loc(xmax), &
+                                 c_loc(nodes),c_loc(f(1,k)),ie)
+                if (ie /= 0) ierror = ie
+                if (ie /= 0 .and. ie /= 104) return
+            end do
+            return
+        end if
+#ifdef REAL128
+        rc = -1
+#endif
+        ierror = int(rc)
+        select case (ierror)
+        case (0)
+        case (101); call report(ierror,' splfe or splde - NDIM is less than 1')
+        case (102); call report(ierror,' splfe or splde - NODES(IDIM) is less than  4for some IDIM')
+        case (103); call report(ierror,' splfe or splde - XMIN(IDIM) = XMAX(IDIM) for some IDIM')
+        case (104); call report(ierror,' splde - NDERIV(IDIM) IS less than 0 or greater than 2 for some IDIM')
+        case default
+            if (ierror < 0) call report_library_failure(ierror,'evaluate_fields')
+        end select
+    end subroutine splpak_eval_fields
 
     subroutine eval_common(me,ndim,nq,x,ldx,nderiv,coef,xmin,xmax,nodes,f,ierror)
         class(splpak_type),intent(inout) :: me
