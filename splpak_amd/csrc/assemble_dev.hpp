@@ -1,0 +1,107 @@
+// What more than one stage of the assembly uses on the device, and grid_for of their launchers (binpoints.hip, gram.hip, constraints.hip, residual.hip,
+// sums.hip, expand.hip).  Everything lives in an anonymous namespace: each translation unit gets its own copy.
+#pragma once
+#include "basis.hpp"
+#include "kernels.hpp"
+
+namespace splpak {
+namespace {
+
+
+// Cells whose window contains node `in`: window starts ws_d in [max(in_d - 3, 0), min(in_d, cells_d - 1)],
+// enumerated with dimension 0 fastest -- THE fixed summation order of every gather (stencil_gather_kernel, rho_gather_kernel).
+template <int D>
+struct CellRange {
+    int lo[D], cnt[D], total;
+    __device__ CellRange(const Grid &g, const int *in)
+    {
+        total = 1;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            lo[d] = in[d] - 3 > 0 ? in[d] - 3 : 0;
+            const int hi = in[d] < g.cells[d] - 1 ? in[d] : g.cells[d] - 1;
+            cnt[d] = hi - lo[d] + 1;
+            total *= cnt[d];
+        }
+    }
+    // e-th cell: its linear index, and the node's local basis index r inside that cell's window
+    __device__ void get(const Grid &g, const int *in, int e, int &cell, int &r) const
+    {
+        cell = 0;
+        r = 0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int wsd = lo[d] + e % cnt[d];
+            e /= cnt[d];
+            cell += wsd * g.cellstride[d];
+            r += (in[d] - wsd) << (2 * d);
+        }
+    }
+};
+
+// a node's "data sparse" flag and constraint weight (sparse_node: constraints.hip)
+struct SparseNode {
+    bool sparse;
+    double dcwght;
+};
+
+// The derivative-constraint rows (what they are: the head of constraints.hip), as constraints.hip adds them to the normal
+// equations and residual.hip applies them to a vector.
+// derivative orders and weight of constraint row `pair` (idm <= jdm enumerated row by row) of node `in`
+template <int D>
+__device__ inline double constraint_pattern(const Grid &g, const int *in, int idm, int jdm, double dcwght, int *nder)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int d = 0; d < D; ++d) nder[d] = 0;
+    bool boundary = true;
+    double rowwt = 2.0 * dcwght;                                  // :983
+    if (jdm == idm) {
+        rowwt = dcwght;
+        nder[jdm] = 2;
+        if (in[idm] != 0 && in[idm] != g.nodes[idm] - 1) boundary = false;
+    }
+    if (boundary) { nder[idm] = 1; nder[jdm] = 1; }                // :998-999
+    return rowwt;
+}
+
+// one dimension's factor of a constraint-row entry: derivative `nder` of the basis function of node n + o at node n
+__device__ inline double constraint_factor(const Grid &g, int d, int n, int o, int nder)
+{
+#pragma clang fp contract(off)
+    const int ib = n + o;
+    if (ib < 0 || ib > g.nodes[d] - 1) return 0.0;
+    const double xnode = g.xmin[d] + (double)n * g.dx[d];         // :943
+    const double xb = g.xmin[d] + (double)ib * g.dx[d];
+    return basis_1d(basis_kind(ib, g.nodes[d]), nder, xnode, xb, g.dxin[d]);
+}
+
+// entry of the constraint row of node n (coordinates nn) at node j = nn + off (off_d in [-1,1]); 0 outside the grid
+template <int D>
+__device__ inline double constraint_entry(const Grid &g, const double *__restrict__ ctab, const int *nn, const int *off,
+                                          const int *nder, double rowwt)
+{
+#pragma clang fp contract(off)
+    double basm = 1.0;
+    int base = 0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        const int ib = nn[d] + off[d];
+        if (ib < 0 || ib > g.nodes[d] - 1) return 0.0;
+        basm *= ctab ? ctab[base + (nn[d] * 3 + off[d] + 1) * 3 + nder[d]] : constraint_factor(g, d, nn[d], off[d], nder[d]);
+        base += 9 * g.nodes[d];
+    }
+    return rowwt * basm;                                          // :1011
+}
+
+// workgroups of `threads` for a grid-stride loop over n items
+inline unsigned grid_for(long long n, int threads, long long maxblocks = 256LL * 16)
+{
+    long long b = (n + threads - 1) / threads;
+    if (b < 1) b = 1;
+    if (b > maxblocks) b = maxblocks;
+    return (unsigned)b;
+}
+
+}  // namespace
+}  // namespace splpak

@@ -8,10 +8,6 @@
 namespace splpak {
 namespace {
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
-
-
 constexpr int IB = 16;                 // inner panel width
 constexpr int PTB = 4;                 // 16x16 tiles of the in-block update per wave and round
 constexpr int XLD = NBLK + 16;         // LDS row of the panel image (bank-half alternation, as in syrk)
@@ -400,14 +396,6 @@ __device__ __forceinline__ void trsm_rows(const double *__restrict__ L, double *
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-}
-
-// ---------------------------------------------------------------------------
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 }  // namespace

@@ -46,6 +46,18 @@ __host__ __device__ inline int stencil_code(const int *o, int ndim)
     return e;
 }
 
+// two / four doubles as one register group: 16-byte memory words, operands and results of the f64 matrix instructions
+typedef double d2_t __attribute__((ext_vector_type(2)));
+typedef double d4_t __attribute__((ext_vector_type(4)));
+
+// sum of v over the 64 lanes of a wave, in every lane
+__device__ inline double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 void set_error(const std::string &msg);
 bool hip_ok(hipError_t e, const char *what);
 

@@ -1,7 +1,7 @@
 // The fit on several GPUs of one node, driven from ONE process.
 //
 // What is distributed
-//   points        every GPU bins and assembles its own shard (assemble.hip); the histogram, the
+//   points        every GPU bins and assembles its own shard (binpoints.hip, gram.hip); the histogram, the
 //                 normal equations and every refinement residual are summed over the GPUs
 //   band factor   the block columns of the band are dealt to the GPUs in chunks (DistMap): a GPU stores
 //                 and updates only its own block columns -- 1/R of the 26.9 GB at 64^3, and the only way

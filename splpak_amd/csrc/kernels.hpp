@@ -48,7 +48,7 @@ hipError_t launch_synth_points(int ndim, long long first, long long n, double *x
 hipError_t launch_synth_queries(int ndim, long long skip_draws, long long nq, double *xq,
                                 hipStream_t st);
 
-// ---- assemble.hip
+// ---- binpoints.hip
 // scalars (device doubles) written by the assembly kernels
 enum { SC_TOTLWT = 0, SC_NROWS_DATA = 1, SC_NROWS_CONS = 2, SC_ERRFLAG = 3, SC_SUMW2 = 4 /* pcg.hip: sum of w^2 */, SC_COUNT = 8 };
 
@@ -63,7 +63,7 @@ struct SortScratch {
     double *ws;      // [cap]
     int *idx;        // [cap] original index of the sorted points (orders the points inside a cell)
     long long cap;   // max_ndata
-    // stable partition (round 5; sp_* kernels of assemble.hip): per-block bin counts / bases, bin bases, intermediate records
+    // stable partition (round 5; sp_* kernels of binpoints.hip): per-block bin counts / bases, bin bases, intermediate records
     int *cntm;       // [ceil(cap / SP_Q)][SP_NB]
     int *binbase;    // [SP_NB + 1]
     int *sppart;     // [chunks of 16 blocks][SP_NB]
@@ -82,6 +82,8 @@ hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ld
 // of n points filled; the positions behind them, up to n, hold no point (zero weights are not placed) and receive 0.
 // y: the n values in the caller's point order
 hipError_t launch_regather_values(const Grid &g, const SortScratch &s, long long n, const double *y, double *ys_out, hipStream_t st);
+
+// ---- gram.hip
 // doubles of scratch launch_gram uses when it can hold every cell's blocks at once (per-cell Gram blocks,
 // right-hand sides, histogram shares), and the least it can work with (one hyper-row of cells)
 long long gram_scratch_doubles(const Grid &g);
@@ -90,6 +92,11 @@ long long gram_scratch_min_doubles(const Grid &g);
 // when smooth, the nearest-node histogram hist[ncol] (caller's order; must be zero on entry) + its total
 hipError_t launch_gram(const Grid &g, const SortScratch &s, double *scratch, long long scratch_doubles, bool smooth,
                        double *nst, double *rhs, double *hist, double *scalH, hipStream_t st);
+// the table of the constraint rows' factors (constraints.hip), once per plan: built beside the Gram kernels, see gram.hip
+long long constraint_table_doubles(const Grid &g);
+hipError_t launch_constraint_table(const Grid &g, double *ctab, hipStream_t st);
+
+// ---- constraints.hip
 // derivative-constraint rows of the data-sparse nodes (:921-1046): nst += C^T C, rows counted into
 // scal_out[SC_NROWS_CONS]
 // dcw[node] / spf[node]: constraint weight xtrap (expect - have) and "data sparse" flag of every node (:923-960)
@@ -99,16 +106,14 @@ hipError_t launch_sparse_mark(const Grid &g, const double *hist, const double *s
 // constraint_table_doubles entries); NULL = evaluate them in place
 hipError_t launch_constraint_rows(const Grid &g, const double *dcw, const unsigned char *spf, const double *ctab, double *nst,
                                   double *scal_out, hipStream_t st);
-// the two single-workgroup reductions of the assembly on their own (the rows-only assembly of pcg-only plans, rowsop.hip):
-// scal[SC_TOTLWT] = sum of the histogram; scal_out[SC_NROWS_CONS] += rows of the data-sparse nodes
-hipError_t launch_hist_total(const Grid &g, const double *hist, double *scal, hipStream_t st);
+// the single-workgroup reduction at the end of launch_constraint_rows on its own (the rows-only assembly of pcg-only plans,
+// rowsop.hip): scal_out[SC_NROWS_CONS] += rows of the data-sparse nodes
 hipError_t launch_count_sparse(const Grid &g, const unsigned char *spf, double *scal_out, hipStream_t st);
-long long constraint_table_doubles(const Grid &g);
-hipError_t launch_constraint_table(const Grid &g, double *ctab, hipStream_t st);
+
+// ---- residual.hip
 // refinement residual rho = A^T W (W y - W A x) [- C^T C x when `constraints`]; rcell: [ncell][nb] scratch,
 // tbuf: [ncol][ndim(ndim+1)/2] scratch; ssq != NULL: also the sum of squared row residuals, from the per-cell / per-node
 // shares in e2buf ([ncell + ncol] scratch) added in a fixed order
-hipError_t launch_sum_fixed(const double *v, long long n, double *out, hipStream_t st);      // out[0] = sum of v[0 .. n) in a fixed order
 hipError_t launch_residual(const Grid &g, const SortScratch &s, const double *xvec, double *rcell,
                            const double *dcw, const unsigned char *spf, const double *ctab, bool constraints,
                            double *tbuf, double *rho, double *ssq, double *e2buf, hipStream_t st);
@@ -117,8 +122,11 @@ hipError_t launch_residual(const Grid &g, const SortScratch &s, const double *xv
 hipError_t launch_backward_denominators(const Grid &g, const double *nst, const double *xvec, const double *rhs, double *den, hipStream_t st);
 hipError_t launch_backward_error(const Grid &g, const double *den, const double *rho, double *out, hipStream_t st);
 
-// coef[reference column] = xvec[internal column] (a plain copy when the plan did not reorder the dimensions)
-hipError_t launch_to_reference_order(const Grid &g, const double *xvec, double *coef, hipStream_t st);
+// ---- sums.hip
+// the single-workgroup reduction at the end of launch_gram on its own (the rows-only assembly of pcg-only plans, rowsop.hip):
+// scal[SC_TOTLWT] = sum of the histogram
+hipError_t launch_hist_total(const Grid &g, const double *hist, double *scal, hipStream_t st);
+hipError_t launch_sum_fixed(const double *v, long long n, double *out, hipStream_t st);      // out[0] = sum of v[0 .. n) in a fixed order
 
 // ---- bandchol.hip
 constexpr int NBLK = 256;     // block size of the band factorisation
@@ -158,10 +166,6 @@ struct Band {
                                     // use, released by band_pipeline_destroy -- owned by whoever owns the Band
 };
 size_t band_bytes(int n, int halfbw, Band *desc);
-struct DistMap;
-// zero the band, put 1 on the padded diagonal, scatter the half-stencil into it (the block columns
-// DistMap gives to this rank)
-hipError_t launch_expand(const Grid &g, const double *nst, const Band &b, const DistMap &dm, hipStream_t st);
 
 struct CholStats {            // optional per-kernel accounting (HIP events)
     bool enabled = false;
@@ -222,5 +226,12 @@ hipError_t launch_mask_owned(int n, const DistMap &dm, double *x, hipStream_t st
 hipError_t launch_axpy_absmax(int n, double *x, const double *dx, double *absmax2, hipStream_t st);
 // absmax2[0] = max |a|, absmax2[1] = max |b| (device doubles, non-negative => ordered like their bit patterns)
 hipError_t launch_absmax2(int n, const double *a, const double *b, double *absmax2, hipStream_t st);
+
+// ---- expand.hip
+// zero the band, put 1 on the padded diagonal, scatter the half-stencil into it (the block columns
+// DistMap gives to this rank)
+hipError_t launch_expand(const Grid &g, const double *nst, const Band &b, const DistMap &dm, hipStream_t st);
+// coef[reference column] = xvec[internal column] (a plain copy when the plan did not reorder the dimensions)
+hipError_t launch_to_reference_order(const Grid &g, const double *xvec, double *coef, hipStream_t st);
 
 }  // namespace splpak

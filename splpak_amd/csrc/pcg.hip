@@ -5,7 +5,7 @@
 // 476 GB of nested-dissection panels (band: 851 GB) against 309 GB of HBM, while its rows are 0.4 GB of points.  The reference
 // accepts any grid (src/splpak.F90:512-534); SURVEY section 7.2-H3 names PCG beside the two factorisations.
 //
-//   operator      q = N p = A^T W^2 A p + C^T C p from the rows themselves: the refinement's residual pass (assemble.hip:
+//   operator      q = N p = A^T W^2 A p + C^T C p from the rows themselves: the refinement's residual pass (residual.hip:
 //                 launch_residual) run with y = 0.  At 32^4 / 1e7 points the rows are 0.4 GB of sorted points and the per-cell
 //                 shares 1.45 GB, the assembled half stencil would be 10 GB per product.  The residual the iteration works on is
 //                 therefore the one the fit is judged by (rows, not the rounded N).
@@ -205,7 +205,6 @@ mode_pair_kernel(int na, int nb, long long inner, int ci, const double *__restri
 // issues one LDS read and one cached global read per multiply-add (43 us per launch at 32^4, 3 TFLOP/s); this one reads two LDS
 // operands per 1 024 of them.  LDS: T0 [nb][kpa][ci] and T1 [kpb][na][ci] with zero rows up to the next multiple of four (no
 // guards in the K loop), the two matrices zero-padded to [kp][mp].
-typedef double pcg_d4_t __attribute__((ext_vector_type(4)));
 __global__ void __launch_bounds__(256)
 mode_pair_mfma_kernel(int na, int nb, long long inner, int ci, const double *__restrict__ MTa, const double *__restrict__ MTb,
                       const double *__restrict__ X, double *__restrict__ Y, const double *__restrict__ scale)
@@ -243,7 +242,7 @@ mode_pair_mfma_kernel(int na, int nb, long long inner, int ci, const double *__r
             const int cc = okc ? col : 0, c = cc % ci, jb = cc / ci;
             const double *__restrict__ bp = T0 + c + ci * (kpa * jb + g4);
             const double *__restrict__ ap = SA + g4 * mpa + 16 * mt + l15;
-            pcg_d4_t acc = {0.0, 0.0, 0.0, 0.0};
+            d4_t acc = {0.0, 0.0, 0.0, 0.0};
             for (int s4 = 0; s4 < kpa; s4 += 4) {
                 const double bv = bp[ci * s4];
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[mpa * s4], okc ? bv : 0.0, acc, 0, 0, 0);
@@ -265,7 +264,7 @@ mode_pair_mfma_kernel(int na, int nb, long long inner, int ci, const double *__r
             const int cc = okc ? col : 0, c = cc % ci, ja = cc / ci;
             const double *__restrict__ bp = T1 + cc + ci * na * g4;
             const double *__restrict__ ap = SB + g4 * mpb + 16 * mt + l15;
-            pcg_d4_t acc = {0.0, 0.0, 0.0, 0.0};
+            d4_t acc = {0.0, 0.0, 0.0, 0.0};
             for (int s4 = 0; s4 < kpb; s4 += 4) {
                 const double bv = bp[ci * na * s4];
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[mpb * s4], okc ? bv : 0.0, acc, 0, 0, 0);

@@ -3,9 +3,9 @@
 //
 // The fit that the reference performs as "one dense row at a time through a dense
 // Householder solver" (splcw :512-1060 -> suprls :1375-1695) is done here as
-//   1. bin the points by 4-wide node window (counting sort),       assemble.hip
-//   2. per-window Gram blocks -> banded normal equations N, r,      assemble.hip
-//   3. derivative-constraint rows of data-sparse nodes -> N,        assemble.hip
+//   1. bin the points by 4-wide node window (counting sort),       binpoints.hip
+//   2. per-window Gram blocks -> banded normal equations N, r,      gram.hip
+//   3. derivative-constraint rows of data-sparse nodes -> N,        constraints.hip
 //   4. blocked band Cholesky on the f64 matrix cores,               bandchol.hip
 //   5. solve + iterative refinement with the residual recomputed FROM THE ROWS,
 //      rho = A^T W (W y - W A x) - C^T C x, which brings the normal-equation
@@ -226,7 +226,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     ok = ok && dev_alloc(p, &p->s.ys, (size_t)max_ndata);
     ok = ok && dev_alloc(p, &p->s.ws, (size_t)max_ndata);
     ok = ok && dev_alloc(p, &p->s.idx, (size_t)max_ndata);
-    {   // stable partition of the points (assemble.hip sp_*): count matrix, bin bases, tile-sorted records for grids of more cells than bins
+    {   // stable partition of the points (binpoints.hip sp_*): count matrix, bin bases, tile-sorted records for grids of more cells than bins
         const size_t nblk = (size_t)((max_ndata + SP_Q - 1) / SP_Q);
         ok = ok && dev_alloc(p, &p->s.cntm, nblk * SP_NB);
         ok = ok && dev_alloc(p, &p->s.binbase, (size_t)2 * SP_NB + 16);      // bin bases | bin totals
@@ -234,7 +234,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
         const long long rd = bin_record_doubles(g, max_ndata);
         if (rd > 0) ok = ok && dev_alloc(p, &p->s.rec, (size_t)rd);
     }
-    {   // per-cell shares of the residual passes of assemble.hip: 1-D .. 3-D grids; a 4-D grid's passes go tile by tile (rowsop.hip)
+    {   // per-cell shares of the residual passes of residual.hip: 1-D .. 3-D grids; a 4-D grid's passes go tile by tile (rowsop.hip)
         // and leave this scratch out (1.45 GB at 32^4) unless the A/B switches ask for the cell-by-cell forms
         const char *rt = splpak::opt_get("SPLPAK_ROWS_TILES");
         const bool tiled = g.ndim == 4 && !(rt && atoi(rt) == 0) && !splpak::opt_get("SPLPAK_RESIDUAL_CELLS");

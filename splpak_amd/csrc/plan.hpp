@@ -103,7 +103,7 @@ struct splpak_plan {
     // iterative solve (pcg.hip): NULL = none.  solver_mode: 0 a factorisation only, 2 the iteration only (no factor storage: grids
     // no factorisation fits, or by request), 3 the iteration first and the factorisation when it stagnates
     splpak::Options opt;                      // the switches as they were when the plan was created (+ splpak_plan_set_option)
-    splpak::RowsOp *rowsop = nullptr;         // 4-D grids: the tiled residual pass (NULL: the cell-by-cell passes of assemble.hip)
+    splpak::RowsOp *rowsop = nullptr;         // 4-D grids: the tiled residual pass (NULL: the cell-by-cell passes of residual.hip)
     splpak::PcgState *pcg = nullptr;
     int solver_mode = 0;
     double factor_flop = 0.0;     // flop of the plan's factorisation where known (nested dissection), else 0

@@ -1,7 +1,7 @@
 // The rows of a 4-D fit applied to a vector, tile by tile (round 6): rho = A^T W (W y - W A x) - C^T C x, the pass that the
 // refinement runs a few times per fit and the iterative solve (pcg.hip) runs once per iteration with y = 0.
 //
-// The cell-by-cell form of rounds 2-5 (assemble.hip: residual_cell4_kernel, constraint_dots_kernel, rho_gather_kernel) writes a
+// The cell-by-cell form of rounds 2-5 (residual.hip: residual_cell4_kernel, constraint_dots_kernel, rho_gather_kernel) writes a
 // 256-double share per cell (1.45 GB at 32^4) that a thread per node gathers back 8 bytes at a time from 256 different cells
 // (every 64-byte sector fetched for one double: 5.0 ms), evaluates the constraint rows entry by entry (1.8 ms + most of the
 // gather), and re-reads the cell's 256 coefficients from global memory for every cell: 10.3 ms per pass at 32^4 / 1e7 points
@@ -40,7 +40,6 @@ constexpr int TB4 = TBS[0] * TBS[1] * TBS[2] * TBS[3];              // nodes of 
 constexpr int NCT = TCS[0] * TCS[1] * TCS[2] * TCS[3];              // cells of a tile
 constexpr int PCHUNK = 16;               // points per trip of a wave
 constexpr int TLD = 17;                  // 16 table values per point + 1 (bank spread)
-typedef double d4_t __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // data rows
@@ -319,7 +318,7 @@ rows4_hist_kernel(Grid g, int nt0, int nt1, int nt2, const int *__restrict__ off
 #pragma unroll
                 for (int d = 0; d < 4; ++d) xv[d] = xs[(long long)d * cap + p0 + lane];
                 wv = ws[p0 + lane];
-                // nearest_slot (assemble.hip): the node's place in the cell's window, or outside it
+                // nearest_slot (gram.hip): the node's place in the cell's window, or outside it
                 bool inwin = true;
                 int loc = 0, m6 = 1;
 #pragma unroll
@@ -479,7 +478,7 @@ size_t rowsop_bytes(const RowsOp *r) { return r ? r->bytes : 0; }
 
 // 4-D grids only; NULL for the others.  (A 3-D form of the tile kernel -- 64 window functions, a lane each in the transposed product --
 // was built and measured in round 6: 22.4 ms of solves + refinement per fit at config 3 against 22.5 ms with the wave-per-cell pass of
-// assemble.hip, and 59.6 against 47.9 ms at 1e8 points (440 points per cell: the wave-per-cell pass takes 64 points per trip, the
+// residual.hip, and 59.6 against 47.9 ms at 1e8 points (440 points per cell: the wave-per-cell pass takes 64 points per trip, the
 // tile kernel 16).  Removed again.)
 int rowsop_create(const Grid &g, bool side_stream, RowsOp **out)
 {   // side_stream: the plan has no factorisation.  (Beside a nested-dissection plan's streams -- one of them bound to eight reserved CUs --

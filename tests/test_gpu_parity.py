@@ -1123,7 +1123,7 @@ FAR_CASES = [
     # SURVEY 8a3's own case (2-D 4x4: ONE window holds every node, the outlier's address 2 is a node of it)
     ("survey_2d4", 2, [4, 4], None, (5.0, 0.5), False),
     # grids with more than one window: the outlier's Horner address (its in-range dimensions alone, :899) is NOT a node of
-    # the window the point is binned into -> the one f64 atomicAdd left in the assembly (assemble.hip "far outside")
+    # the window the point is binned into -> the one f64 atomicAdd left in the assembly (gram.hip: stage_points, "far outside")
     ("2d8_wave", 2, [8, 8], 600, (5.0, 0.9), True),
     ("2d8_wave_both", 2, [8, 8], 600, (-7.0, 9.0), True),          # both dimensions skipped: address 0
     ("3d7_wave", 3, [7, 6, 8], 2500, (0.2, -4.0, 0.95), True),
@@ -1194,7 +1194,7 @@ for nd, nodes, m, far in [(2, [8, 8], 600, (5.0, 0.9)), (4, [6, 5, 6, 5], 5000, 
 
 
 def test_cells_of_more_than_1024_points_are_ordered_too():
-    """assemble.hip cell_order_kernel: the per-cell sums follow the storage order of the binned points, and the scatter's
+    """binpoints.hip cell_order_kernel: the per-cell sums follow the storage order of the binned points, and the scatter's
     atomic cursor hands out positions in a different order every run.  Cells of up to 1 024 points are re-ordered through
     LDS; larger ones (up to 65 536 points in one window) by the chunked rank count added in round 4.  2-D 5x5 nodes =
     4 windows, 30 000 points = 7 500 per window: four fits must agree bit for bit, coefficients AND histogram, and hold
@@ -1274,7 +1274,7 @@ def atomic_binning_results(tmp_path_factory):
 
 @pytest.mark.parametrize("case", SP_CASES)
 def test_stable_partition_gives_the_bits_of_the_atomic_binning(case, atomic_binning_results):
-    """Round 5 (assemble.hip sp_*): the points are binned by a counting sort without global atomics that is stable by
+    """Round 5 (binpoints.hip sp_*): the points are binned by a counting sort without global atomics that is stable by
     construction -- the points of a window end up in ascending original index, the order cell_order_kernel used to restore after
     the atomic scatter.  So every fit must return the SAME BITS through both forms (SPLPAK_BIN_ATOMIC=1 = rounds 1-4, in a child
     process: the switch is read once): goldens of one level (cells <= 4 095) and two levels (tiles of cells, then cells), zero

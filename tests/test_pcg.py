@@ -247,7 +247,7 @@ def test_forms_of_the_preconditioner_agree_with_the_factorisation(nodes, m, xtra
                       ("pairs_valu", {"SPLPAK_PCG_PAIRS_VALU": "1"}), ("no_pairs", {"SPLPAK_PCG_NO_PAIRS": "1"}),
                       # the constraint rows' passes behind the data rows' tile kernel instead of beside it (a stream of their own)
                       ("one_stream", {"SPLPAK_ROWS_ONE_STREAM": "1"}),
-                      # the final residual pass and reserr cell by cell (assemble.hip) instead of tile by tile
+                      # the final residual pass and reserr cell by cell (residual.hip) instead of tile by tile
                       ("cells", {"SPLPAK_RESIDUAL_CELLS": "1"})):
         old = {k: os.environ.get(k) for k in env}
         os.environ.update(env)

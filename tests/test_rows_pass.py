@@ -383,7 +383,7 @@ def test_rows_pass_matches_oracle(port, name, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["4d_13_12_14_11", "4d_5_21_4_6", "4d_big_cell"])
 def test_rows_pass_cell_by_cell_forms_match_oracle(port, name, monkeypatch):
-    """The 4-D passes in their cell-by-cell forms (assemble.hip): rows_tiles = 0 for the refinement pass, residual_cells for the
+    """The 4-D passes in their cell-by-cell forms (residual.hip): rows_tiles = 0 for the refinement pass, residual_cells for the
     diagnostics pass."""
     _rows_case(port, name, monkeypatch, SOLVERS_4D[:2], forms=({"SPLPAK_ROWS_TILES": "0"}, {"SPLPAK_RESIDUAL_CELLS": "1"}))
 
