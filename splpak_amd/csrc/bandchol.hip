@@ -3,7 +3,7 @@
 // Replaces the triangularisation + back-substitution of the reference's dense
 // row-streaming Householder solver suprls (src/splpak.F90:1375-1695) by a
 // factorisation of the (banded) normal equations; iterative refinement against
-// the rows (plan.hip) restores the accuracy of the orthogonal method.
+// the rows (planfit.hip) restores the accuracy of the orthogonal method.
 //
 // Storage: LAPACK-style lower band, column j holds A(j..j+ld-1, j) contiguously,
 // so that A(i,j) = ab[i + j*lda] with lda = ld-1: every sub-block of the band is

@@ -32,11 +32,7 @@ struct DevStage {
     {
         void *q = nullptr;
         if (count == 0) count = 1;
-        hipError_t e = hipMalloc(&q, count * sizeof(T));
-        if (e != hipSuccess && release_cached_plan_for_memory()) {      // the one-shot fit's cached plan (35 GB at 64^3) is in the way
-            (void)hipGetLastError();
-            e = hipMalloc(&q, count * sizeof(T));
-        }
+        const hipError_t e = hip_malloc_retry(&q, count * sizeof(T));      // (the one-shot fit's cached plan -- 35 GB at 64^3 -- may be in the way)
         if (e != hipSuccess) {
             char buf[160];
             snprintf(buf, sizeof buf, "hipMalloc of %.3f GB failed: %s", (double)(count * sizeof(T)) / 1e9, hipGetErrorString(e));

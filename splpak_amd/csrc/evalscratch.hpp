@@ -44,12 +44,9 @@ struct DevScratch {
         release();
         hipError_t e = hipEventCreateWithFlags(&last, hipEventDisableTiming);
         for (int i = 0; i < N && e == hipSuccess; ++i) {
-            e = hipMalloc(&buf[i], want[i]);
-            if (e != hipSuccess && may_release_plan && release_cached_plan_for_memory()) {
-                may_release_plan = false;
-                (void)hipGetLastError();
-                e = hipMalloc(&buf[i], want[i]);
-            }
+            bool released = false;
+            e = may_release_plan ? hip_malloc_retry(&buf[i], want[i], &released) : hipMalloc(&buf[i], want[i]);
+            if (released) may_release_plan = false;
             if (e == hipSuccess) bytes[i] = want[i];
             else buf[i] = nullptr;
         }

@@ -7,8 +7,17 @@
 
 namespace splpak {
 
-// after a failed allocation: release the plan / staging buffers the one-shot fit entry caches (plan.hip); true = retry
+// after a failed allocation: release the plan / staging buffers the one-shot fit entry caches (hostfit.hip); true = retry
 bool release_cached_plan_for_memory();
+// hipMalloc, once more after release_cached_plan_for_memory() where the first failed (released: whether that freed something)
+inline hipError_t hip_malloc_retry(void **ptr, size_t bytes, bool *released = nullptr)
+{
+    hipError_t e = hipMalloc(ptr, bytes);
+    const bool freed = e != hipSuccess && release_cached_plan_for_memory();
+    if (freed) { (void)hipGetLastError(); e = hipMalloc(ptr, bytes); }
+    if (released) *released = freed;
+    return e;
+}
 
 // ---- eval.hip (dispatchers; the sorted paths: evalpaths.hpp).  T = double or float: storage type of the coordinates,
 // the coefficients and the results (the arithmetic is double)

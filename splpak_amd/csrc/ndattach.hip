@@ -10,12 +10,7 @@ namespace nd {
 bool nd_alloc_bytes(NdState *s, void **ptr, size_t bytes)
 {
     void *q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes);
-    if (e != hipSuccess && release_cached_plan_for_memory()) {
-        (void)hipGetLastError();
-        e = hipMalloc(&q, bytes);
-    }
-    if (e != hipSuccess) {
+    if (hip_malloc_retry(&q, bytes) != hipSuccess) {
         (void)hipGetLastError();
         char buf[160];
         snprintf(buf, sizeof buf, "nested dissection: hipMalloc of %.3f GB failed", (double)bytes / 1e9);
@@ -426,7 +421,7 @@ int nd_attach(splpak_plan *p, double **factor_arena, long long *factor_doubles, 
     }
     p->fn_name = s->desc.c_str();
     p->fn_code = s->mdist ? 5 : 4;
-    p->factor_flop = t.flop;                 // (what the iteration in front of this factorisation may spend is weighed against it, plan.hip)
+    p->factor_flop = t.flop;                 // (what the iteration in front of this factorisation may spend is weighed against it, planfit.hip)
     if (factor_arena) *factor_arena = s->factor;
     if (factor_doubles) *factor_doubles = s->factor_doubles;
     if (splpak::opt_get("SPLPAK_DEBUG"))

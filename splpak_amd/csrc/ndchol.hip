@@ -4,7 +4,7 @@
 // row-streaming Householder triangularisation + back-substitution of suprls (src/splpak.F90:1375-1695, called
 // from splcw :849, :1025, :1052) -- by a factorisation in the nested-dissection order of ndtree.hpp: 1.2e13
 // flop and 14 GB of factor at 64^3 nodes instead of 4.1e13 / 26.9 GB, 2.7e14 flop at 24^4 instead of 6.2e14.
-// The refinement against the rows (plan.hip) is unchanged, so the result is the same minimiser.
+// The refinement against the rows (planfit.hip) is unchanged, so the result is the same minimiser.
 //
 // Every front is a dense column-major PANEL (rows: own | border, columns: own, padded to 256 with identity)
 // and, while it is being eliminated, a dense Schur buffer S (border x border):

@@ -16,7 +16,7 @@
 //                 dimension the generalised eigenvectors V_k of (K2_k, K0_k) diagonalise two of the four matrices exactly and the
 //                 other two nearly (all four are Toeplitz away from the ends); M^-1 = V diag^-1 V^T with V = (x)_k V_k costs
 //                 2 d mode products of nodes_k x nodes_k matrices (0.5 GFLOP at 32^4) -- nothing beside one pass over the rows.
-//   outer loop    the fit's own refinement against the rows (plan.hip) with this solve in place of the triangular solves.
+//   outer loop    the fit's own refinement against the rows (planfit.hip) with this solve in place of the triangular solves.
 //
 // Where it works and where it does not (measured): the preconditioner knows the DENSITY of data-sparse nodes,
 // not where they are.  4-D at config 5's density (26 % of the nodes data sparse, 10 rows each: the constraint rows alone have
@@ -892,7 +892,7 @@ int pcg_attach(splpak_plan *p, PcgState **out)
          pcg_alloc(s, &s->mom, 2);
     ok = ok && pcg_alloc(s, &s->mband, (size_t)mbtot) && hip_ok(hipMemcpy(s->mband, hmband.data(), sizeof(double) * (size_t)mbtot, hipMemcpyHostToDevice), "pcg: upload");
     for (int k = 0; k < MAXD; ++k) s->mbands.m[k] = s->mband + (k < g.ndim ? mboffs[k] : 0);
-    // (also for the plans that have a factorisation behind the iteration: their fits assemble nothing until it is needed, plan.hip "lazy")
+    // (also for the plans that have a factorisation behind the iteration: their fits assemble nothing until it is needed, planfit.hip "lazy")
     if (ok && g.ndim == 4 && p->rowsop && (p->rows_only || p->solver_mode == 3)) {
         if (p->rows_only) ok = pcg_alloc(s, &s->ddiag, n);
         else if (!pcg_alloc(s, &s->ddiag, n)) { (void)hipGetLastError(); s->ddiag = nullptr; }

@@ -1,10 +1,11 @@
-// The fit plan (internal): shared by plan.hip (single-GPU driver, C ABI) and dist.hip (several GPUs).
+// The fit plan (internal): shared by plan.hip (creation, C ABI), planfit.hip (single-GPU fit driver), hostfit.hip, plandebug.hip and dist.hip (several GPUs).
 #pragma once
 #include "kernels.hpp"
 #include "../../include/splpak_hip.h"
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdio>
 #include <mutex>
 #include <vector>
 
@@ -155,8 +156,32 @@ void nd_group_reset(NdGroup *g);
 bool nd_wanted_for(int ndim, const int *nodes, const double *xmin, const double *xmax);
 // the sharded fit's ranks are known: distribute the nested-dissection factorisation by subtrees (SPLPAK_ND_DIST=1; ndattach.hip)
 int nd_set_ranks(splpak_plan *p, int rank, int world);
-// sum over the ranks of the sharded fit through the caller's hook (plan.hip); 0 = fine (also with one rank)
+// sum over the ranks of the sharded fit through the caller's hook (planfit.hip); 0 = fine (also with one rank)
 int plan_allreduce(splpak_plan *p, double *buf, long long count, hipStream_t st);
+// planfit.hip: the pieces of a fit that the debug-plan entries (plandebug.hip) run alone; described where they are defined
+int plan_factor(splpak_plan *p, hipStream_t st, int *hinfo, double *minpiv, hipEvent_t e0, hipEvent_t e1);
+int plan_factor_solve(splpak_plan *p, double *v, hipStream_t st);
+int plan_diagnostics_pass(splpak_plan *p, bool rows_fit, hipStream_t st, hipEvent_t e0);
+// device memory the plan owns and frees with itself: count elements (one for none); false = set_error says why
+template <typename T> static bool dev_alloc(splpak_plan *p, T **ptr, size_t count)
+{
+    void *q = nullptr;
+    if (count == 0) count = 1;
+    const hipError_t e = hip_malloc_retry(&q, count * sizeof(T));      // (the one-shot entry's cached plan -- 35 GB at 64^3 -- may be in the way)
+    if (e != hipSuccess) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "hipMalloc of %.3f GB failed: %s", (double)(count * sizeof(T)) / 1e9, hipGetErrorString(e));
+        set_error(buf);
+        (void)hipGetLastError();
+        return false;
+    }
+    p->owned.push_back(q);
+    p->owned_bytes += count * sizeof(T);
+    *ptr = static_cast<T *>(q);
+    return true;
+}
+// plan.hip: the band's block inverses of nblocks diagonal blocks -- sweeps: with the sweep blocks of the one-GPU solves
+bool band_alloc_inverses(splpak_plan *p, Band &b, size_t nblocks, bool sweeps);
 // narrow bands on one GPU: install the two-ended factorisation (twoend.hip) when it shortens the chain
 void twoend_attach(splpak_plan *p);
 void twoend_detach(splpak_plan *p);

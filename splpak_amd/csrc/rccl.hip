@@ -91,7 +91,7 @@ void rccl_fail(const char *what, int rc)
 
 struct RcclHook { void *comm; };
 
-// the plan's sum-all-reduce: in place, enqueued on the fit's stream (SPLPAK_AR_STREAM_ORDERED: plan.hip does not synchronise
+// the plan's sum-all-reduce: in place, enqueued on the fit's stream (SPLPAK_AR_STREAM_ORDERED: planfit.hip does not synchronise
 // the stream around it)
 int32_t rccl_allreduce(void *buf, int64_t count, void *stream, void *user)
 {

@@ -1,6 +1,6 @@
 """The assembled normal equations and each factorisation on their own, without iterative refinement.
 
-Every fit refines against the ROWS (plan.hip plan_rows_residual), so an assembled N or a factor that is slightly wrong only
+Every fit refines against the ROWS (planfit.hip solve_and_refine), so an assembled N or a factor that is slightly wrong only
 costs refinement steps: the coefficients still meet the parity bar.  These tests look at the two objects directly.
 
 CPU tier: the oracle's normal equations (oracle/splpak_banded.c oracle_normal_equations, long double) against the oracle's

@@ -1,4 +1,4 @@
-"""Refit: new values on the points of a plan's last fit (splpak_plan_refit_dev, splpak_refit_f64 / _f32; splpak_amd/csrc/plan.hip).
+"""Refit: new values on the points of a plan's last fit (splpak_plan_refit_dev, splpak_refit_f64 / _f32; splpak_amd/csrc/planfit.hip, hostfit.hip).
 
 Only the solve of a fit depends on ydata; the binned points, the constraint rows, N = A^T W^2 A + C^T C, its factor and the
 iteration's preconditioner are kept by the plan.  What is checked, and against what:
@@ -205,6 +205,51 @@ def test_refit_factors_when_its_iteration_gives_up():
         cb, rc, info_b = s.refit(second_field(inp))
         assert rc == 0 and relmax(cb, c2) < PAIR_TOL
         assert info_b[6] == 0.0 and info_b[4] == info[4]
+    finally:
+        s.close()
+
+
+def test_stage_timing_after_a_fit_and_a_refit():
+    """include/splpak_hip.h on splpak_plan_stage_timing after a refit: [1] is the values gather + right-hand side, [0] and [2]
+    are 0, [3] is 0 unless the factorisation ran, [4] [5] as for the fit.  On the band (2d16) and on nested dissection (3d16) with
+    the held factor, and on 4d6 where the refit's iteration gives up and it factors.  Signs and zeros only, never durations."""
+    def timing(s):
+        t = s.plan.stage_timing()
+        print({k: float(v) for k, v in t.items()})
+        assert all(np.isfinite(v) and v >= 0.0 for v in t.values()), t
+        return t
+
+    for name in ("2d16", "3d16"):
+        inp = make_inputs(CASES[name])
+        s = Session(inp)
+        try:
+            s.plan.enable_kernel_timing()
+            _, rc, info = s.fit(second_field(inp))
+            assert rc == 0 and info[4] != 0.0                       # (a factorisation ran: the refit holds its factor)
+            t = timing(s)
+            assert t["bin_ms"] > 0.0 and t["gram_ms"] > 0.0 and t["expand_ms"] > 0.0 and t["solve_ms"] > 0.0, (name, t)
+            _, rc, info = s.refit(inp["ydata"])
+            assert rc == 0 and info[6] == 0.0
+            t = timing(s)
+            assert t["bin_ms"] == 0.0 and t["constraints_ms"] == 0.0 and t["expand_ms"] == 0.0, (name, t)
+            assert t["gram_ms"] > 0.0 and t["solve_ms"] > 0.0, (name, t)
+        finally:
+            s.close()
+    # the set-up of test_refit_factors_when_its_iteration_gives_up: the refit expands and factors
+    inp = make_inputs(CASES["4d6"])
+    s = Session(inp, env={"SPLPAK_SOLVER": "pcg+direct", "SPLPAK_PCG_ALWAYS": "1"})
+    try:
+        s.plan.enable_kernel_timing()
+        _, rc, info_fit = s.fit(second_field(inp))
+        assert rc == 0 and info_fit[4] == 0.0 and info_fit[6] == 0.0
+        timing(s)
+        s.plan.set_option("pcg_tol1", "-1")
+        _, rc, info = s.refit(inp["ydata"])
+        s.plan.set_option("pcg_tol1", None)
+        assert rc == 0 and info[4] > 0.0 and info[6] > 0.0
+        t = timing(s)
+        assert t["expand_ms"] > 0.0, t
+        assert t["bin_ms"] == 0.0 and t["constraints_ms"] == 0.0 and t["gram_ms"] > 0.0 and t["solve_ms"] > 0.0, t
     finally:
         s.close()
 
