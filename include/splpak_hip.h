@@ -485,6 +485,36 @@ int32_t splpak_debug_spd_band_solve_f64(int32_t n, int32_t halfbw, const double 
  * fit yet, a 4-D fit the iteration answered without assembling, a failed fit, or a splpak_debug_plan_solve since the fit). */
 int32_t splpak_debug_plan_normal_equations(const splpak_plan *plan, double *nst_ref, double *rhs);
 
+/* Diagnostics: how the Gram pass of the plan's last assembly was launched (csrc/gram.hip launch_gram).  The cells are worked slab
+ * by slab, a slab being as many whole hyper-rows of cells along the slowest internal dimension as the Gram scratch holds
+ * (SPLPAK_GRAM_SCRATCH_MB); in a 2-D or 3-D slab a wave owns a run of consecutive cells.  out6: [0] slabs, [1] hyper-rows per
+ * slab, [2] cells and [3] run of every slab but the last, [4] cells and [5] run of the last slab (= [2], [3] with one slab).  A
+ * run of 0: the grid's cell kernel does not work in runs (1-D, 4-D, SPLPAK_GRAM_VALU).  Returns 0, SPLPAK_E_BADARG for a null
+ * argument, SPLPAK_E_UNSUPPORTED where splpak_debug_plan_normal_equations has nothing to return. */
+int32_t splpak_debug_plan_gram_shape(const splpak_plan *plan, int32_t *out6);
+
+/* Diagnostics: the binning of the data points by window (csrc/binpoints.hip launch_bin_points), the first stage of every
+ * assembly, on its own: no plan, no factor storage, no normal equations -- the scratch of the binning alone, allocated as a plan
+ * allocates it and released before the entry returns.  Everything comes back RAW, in the library's internal numbering, so that
+ * no translation can hide a mistake.  Inputs on the host as for splpak_fit_f64 (xdata(l1xdat, ndata), wdata may be NULL; a
+ * negative first weight has no special meaning here).  SPLPAK_BIN_ATOMIC and SPLPAK_NO_REORDER are read from the process
+ * defaults / the environment.  Outputs (all required):
+ *   perm, cells, cellstride [ndim]: internal dimension d is the caller's dimension perm[d]; windows per dimension and their strides;
+ *   *route: 0 the atomic route (SPLPAK_BIN_ATOMIC, or a grid of more than 4095^2 cells), 1 the stable partition in one level, 2 in
+ *           two levels with tiles of at most 256 cells, 3 with tiles of up to 4095 cells; *cpt: cells per tile (0: too many cells);
+ *   key [ndata]: cell of every point, sum_d ws_d cellstride[d], ncell = prod cells for a point of zero weight (not placed);
+ *           (on the atomic route too: scratch made for that route keeps its re-sort out of the key array);
+ *   offset [ncell + 1]: first sorted position of every cell; *placed = offset[ncell];
+ *   idx [ndata]: original index of the sorted points (the first *placed entries are set; likewise below);
+ *   xs [ndim][ndata] (plane d, internal order, at xs + d * ndata), ys, ws [ndata]: the sorted copies;
+ *   *nrows_data: the scalar the fit reports as its number of data rows.
+ * Returns 0; 101/102/103 (grid checks); SPLPAK_E_BADARG for a null argument, ndata < 1 or l1xdat < ndim; SPLPAK_E_NOMEM;
+ * SPLPAK_E_NODEVICE, with the message of the failing call, when a launch or a copy fails or the placed count is impossible. */
+int32_t splpak_debug_bin_points(int32_t ndim, const int32_t *nodes, const double *xmin, const double *xmax, int64_t ndata,
+                                const double *xdata, int32_t l1xdat, const double *ydata, const double *wdata, int32_t *perm,
+                                int32_t *cells, int32_t *cellstride, int32_t *route, int32_t *cpt, int32_t *key, int32_t *offset,
+                                int32_t *idx, double *xs, double *ys, double *ws, int64_t *placed, double *nrows_data);
+
 /* Diagnostics: loads the caller's matrix (layout of splpak_debug_plan_normal_equations) into the plan and solves N x = b with
  * the plan's own factorisation, exactly as a fit runs it -- expansion into the factor storage, factorisation, one solve --
  * without iterative refinement.  b, x: [ncol] in the caller's column order; minpiv (may be NULL): the smallest pivot.

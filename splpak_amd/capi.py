@@ -39,6 +39,7 @@ SYMBOLS = [
     "splpak_mplan_create", "splpak_mplan_destroy", "splpak_mplan_device", "splpak_mplan_rank_bytes", "splpak_mplan_factorisation", "splpak_mplan_fit_dev", "splpak_fit_multi_f64",
     "splpak_plan_device_bytes", "splpak_plan_pcg_stats", "splpak_set_default_option", "splpak_plan_set_option", "splpak_plan_get_option",
     "splpak_debug_spd_band_solve_f64", "splpak_debug_plan_normal_equations", "splpak_debug_plan_solve", "splpak_debug_nd_fronts",
+    "splpak_debug_bin_points", "splpak_debug_plan_gram_shape",
     "splpak_debug_plan_rows_gradient", "splpak_debug_plan_precondition", "splpak_debug_plan_pcg_tables", "splpak_debug_plan_pcg_diagonal",
     "splpak_debug_nd_tree", "splpak_debug_nd_partition", "splpak_debug_nd_schedule", "splpak_debug_window_values", "splpak_shutdown", "splpak_set_eval_mode",
     "splpak_last_error_message", "splpak_device_name",
@@ -169,6 +170,11 @@ def lib() -> C.CDLL:
     L.splpak_debug_plan_normal_equations.argtypes = [vp, _dp, _dp]
     L.splpak_debug_plan_solve.restype = i32
     L.splpak_debug_plan_solve.argtypes = [vp, _dp, _dp, _dp, _dp]
+    L.splpak_debug_plan_gram_shape.restype = i32
+    L.splpak_debug_plan_gram_shape.argtypes = [vp, _ip]
+    L.splpak_debug_bin_points.restype = i32
+    L.splpak_debug_bin_points.argtypes = [i32, _ip, _dp, _dp, i64, _dp, i32, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, _dp,
+                                          C.POINTER(i64), _dp]
     L.splpak_debug_plan_rows_gradient.restype = i32
     L.splpak_debug_plan_rows_gradient.argtypes = [vp, _dp, i32, _dp, _dp, _dp]
     L.splpak_debug_plan_precondition.restype = i32
@@ -685,6 +691,13 @@ class Plan:
         _check(self._L.splpak_debug_plan_normal_equations(self._h, _p(N, _dp), _p(rhs, _dp)))
         return N, rhs
 
+    def gram_shape(self):
+        """How the Gram pass of the last assembly was launched (diagnostics, splpak_debug_plan_gram_shape) -> dict(slabs, rows: hyper-rows
+        of cells per slab, cells, run: of every slab but the last, last_cells, last_run); run 0: a cell kernel without runs."""
+        out = np.zeros(6, dtype=np.int32)
+        _check(self._L.splpak_debug_plan_gram_shape(self._h, _p(out, _ip)))
+        return dict(zip(("slabs", "rows", "cells", "run", "last_cells", "last_run"), (int(v) for v in out)))
+
     def debug_solve(self, N, b):
         """Solve N x = b once with the plan's own factorisation, no refinement (diagnostics) -> (x, ierror, minpiv);
         ierror 0 or 107."""
@@ -918,6 +931,38 @@ def debug_window_values(nodes, xmin, xmax, x):
     if rc != 0:
         raise SplpakError(f"grid rejected: {rc}")
     return ws, used, gen, form
+
+
+def debug_bin_points(nodes, xmin, xmax, x, y, w=None):
+    """The binning of the points by window alone, without a plan (diagnostics, splpak_debug_bin_points), everything raw in the
+    library's internal numbering.  x: (ndata, l1xdat) with l1xdat >= ndim.  -> dict(perm, cells, cellstride, route, cpt, key,
+    offset, placed, nrows_data, idx [placed], xs [ndim, placed], ys, ws [placed])."""
+    nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+    nd = len(nodes)
+    xmin = np.ascontiguousarray(xmin, dtype=np.float64)
+    xmax = np.ascontiguousarray(xmax, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+    m, ldx = x.shape
+    assert y.shape == (m,) and (w is None or w.shape == (m,)) and xmin.shape == (nd,) and xmax.shape == (nd,)
+    ncell = int(np.prod(np.maximum(nodes.astype(np.int64) - 3, 1)))
+    perm, cells, stride = (np.zeros(nd, dtype=np.int32) for _ in range(3))
+    route, cpt = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32)
+    key, idx = np.zeros(m, dtype=np.int32), np.zeros(m, dtype=np.int32)
+    offset = np.zeros(ncell + 1, dtype=np.int32)
+    xs, ys, ws = np.zeros((nd, m)), np.zeros(m), np.zeros(m)
+    placed = C.c_int64(-1)
+    rows = C.c_double(-1.0)
+    rc = _check(lib().splpak_debug_bin_points(nd, _p(nodes, _ip), _p(xmin, _dp), _p(xmax, _dp), m, _p(x, _dp), ldx, _p(y, _dp), _p(w, _dp),
+                                              _p(perm, _ip), _p(cells, _ip), _p(stride, _ip), _p(route, _ip), _p(cpt, _ip), _p(key, _ip),
+                                              _p(offset, _ip), _p(idx, _ip), _p(xs, _dp), _p(ys, _dp), _p(ws, _dp), C.byref(placed),
+                                              C.byref(rows)))
+    if rc != 0:
+        raise SplpakError(f"grid rejected: {rc}")
+    n = int(placed.value)
+    return dict(perm=perm, cells=cells, cellstride=stride, route=int(route[0]), cpt=int(cpt[0]), key=key, offset=offset, placed=n,
+                nrows_data=rows.value, idx=idx[:n], xs=xs[:, :n], ys=ys[:n], ws=ws[:n])
 
 
 def debug_spd_band_solve(a_lower, halfbw, b):

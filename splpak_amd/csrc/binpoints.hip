@@ -148,7 +148,7 @@ scatter_kernel(Grid g, long long m, const double *__restrict__ x, int ldx,
 // bit for bit.  One workgroup per cell.  Cells of up to ORDER_CAP points are permuted through an image
 // in LDS.  Larger cells (round 4; up to ORDER_BIG_CAP points): the rank of every point is counted against
 // the cell's original indices streamed through LDS in chunks of 1 024, the ordered indices are parked in
-// `ordtmp` (the key array, dead once the scatter has run) and the cell's image is rebuilt from the caller's
+// `ordtmp` (SortScratch::ordtmp, or the key array, dead once the scatter has run) and the cell's image is rebuilt from the caller's
 // arrays.  Cells beyond ORDER_BIG_CAP (65 536 points in ONE window of the grid) keep the scatter's order:
 // their sums are correct, only not reproducible from run to run.
 constexpr int ORDER_CAP = 1024;
@@ -652,12 +652,21 @@ long long bin_record_doubles(const Grid &g, long long max_ndata)
     return cpt > 1 ? max_ndata * (long long)sp_rec(g.ndim) : 0;
 }
 
-hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ldx, const double *y,
-                             const double *w, const SortScratch &s, double *scal, hipStream_t st)
+int bin_route(const Grid &g, const SortScratch &s, int *cpt_out)
 {
     const bool old_form = splpak::opt_get("SPLPAK_BIN_ATOMIC") != nullptr;      // A/B switch: rounds 1-4 (global atomics + in-cell re-sort)
     const int cpt = sp_cells_per_bin(g);
-    if (!old_form && cpt > 0 && s.cntm && s.binbase && s.sppart && (cpt == 1 || s.rec)) {
+    if (cpt_out) *cpt_out = cpt;
+    if (old_form || cpt <= 0 || !s.cntm || !s.binbase || !s.sppart || (cpt > 1 && !s.rec)) return 0;
+    return cpt == 1 ? 1 : cpt <= 256 ? 2 : 3;
+}
+
+hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ldx, const double *y,
+                             const double *w, const SortScratch &s, double *scal, hipStream_t st)
+{
+    int cpt = 0;
+    const int route = bin_route(g, s, &cpt);
+    if (route != 0) {
         if (m <= 0) return hipMemsetAsync(s.offset, 0, sizeof(int) * (size_t)(g.ncell + 2), st);
         const int nblk = (int)((m + SP_Q - 1) / SP_Q), nchunk = (nblk + SP_ROWS - 1) / SP_ROWS;
         double *rec = cpt > 1 ? s.rec : nullptr;
@@ -670,9 +679,9 @@ hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ld
         hipLaunchKernelGGL(sp_blockbase_kernel, dim3(SP_NB / 256, (unsigned)nchunk), dim3(256), 0, st, nblk, s.cntm, s.sppart, s.binbase);
         DISPATCH_D(g.ndim, hipLaunchKernelGGL(sp_scatter_kernel<D>, dim3((unsigned)nblk), dim3(SP_NT), 0, st, g, m, x, ldx, y, w, cpt, ntile, s.key,
                                               s.cntm, rec, s.xs, s.ys, s.ws, s.idx, s.cap));
-        if (cpt == 1)      // the bins are the cells: their bases are the offsets (bins ncell .. SP_NB - 2 are empty)
+        if (route == 1)    // the bins are the cells: their bases are the offsets (bins ncell .. SP_NB - 2 are empty)
             return hipMemcpyAsync(s.offset, s.binbase, sizeof(int) * (size_t)(g.ncell + 1), hipMemcpyDeviceToDevice, st);
-        if (cpt <= 256) {
+        if (route == 2) {
             DISPATCH_D(g.ndim, hipLaunchKernelGGL((sp_bin2_kernel<D, 256>), dim3((unsigned)ntile), dim3(SP_NT), 0, st, g, cpt, ntile, s.binbase,
                                                   rec, s.offset, s.xs, s.ys, s.ws, s.idx, s.cap));
         } else {
@@ -696,7 +705,7 @@ hipError_t launch_bin_points(const Grid &g, long long m, const double *x, int ld
         DISPATCH_D(g.ndim, hipLaunchKernelGGL(scatter_kernel<D>, gr, bl, 0, st, g, m, x, ldx, y, w,
                                               s.key, s.offset, s.cursor, s.xs, s.ys, s.ws, s.idx, s.cap));
         DISPATCH_D(g.ndim, hipLaunchKernelGGL(cell_order_kernel<D>, dim3((unsigned)g.ncell), dim3(256), 0, st, g,
-                                              s.offset, s.xs, s.ys, s.ws, s.idx, s.cap, x, ldx, y, w, s.key));
+                                              s.offset, s.xs, s.ys, s.ws, s.idx, s.cap, x, ldx, y, w, s.ordtmp ? s.ordtmp : s.key));
     }
     return hipGetLastError();
 }

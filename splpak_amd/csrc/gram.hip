@@ -784,17 +784,41 @@ long long gram_scratch_min_doubles(const Grid &g)
 }
 
 
-// -> true when the blocks of empty cells were written as zeros (the gather then reads every block unconditionally)
+// cells per wave of gram_wave_kernel in a slab of ncells cells: GW_RUN where that still leaves four rounds of waves for the chip
+// (two per SIMD), fewer on a small grid; 0: the slab goes to a kernel that does not work in runs
+static int gram_run(int ndim, int ncells)
+{
+    if ((ndim != 2 && ndim != 3) || splpak::opt_get("SPLPAK_GRAM_VALU") != nullptr) return 0;      // A/B switch: the workgroup-per-cell form
+    const int run = (int)(ncells / (4LL * 2048));
+    return run < 1 ? 1 : run > GW_RUN ? GW_RUN : run;
+}
+
+bool gram_shape(const Grid &g, long long scratch_doubles, GramShape *out)
+{
+    const long long per_cell = gram_tri(g.nb) + 2LL * g.nb;
+    const int hrow = g.cellstride[g.ndim - 1];              // cells per hyper-row
+    const int nhrow = g.cells[g.ndim - 1];
+    long long fit_rows = scratch_doubles / (per_cell * hrow);
+    if (fit_rows < 1) return false;
+    if (fit_rows > nhrow) fit_rows = nhrow;
+    out->rows = (int)fit_rows;
+    out->nslab = (nhrow + out->rows - 1) / out->rows;
+    out->cells = out->rows * hrow;
+    out->last_cells = (nhrow - (out->nslab - 1) * out->rows) * hrow;
+    out->run = gram_run(g.ndim, out->cells);
+    out->last_run = gram_run(g.ndim, out->last_cells);
+    return true;
+}
+
+// run: gram_run of the slab.  -> true when the blocks of empty cells were written as zeros (the gather then reads every block
+// unconditionally)
 template <int D>
 static bool gram_cells(const Grid &g, const SortScratch &s, double *blk, double *rblk, double *hblk, double *hist, int cell0,
-                       int ncells, hipStream_t st)
+                       int ncells, int run, hipStream_t st)
 {
     const bool old_form = splpak::opt_get("SPLPAK_GRAM_VALU") != nullptr;       // A/B switch: the workgroup-per-cell form
     if constexpr (D == 2 || D == 3) {
-        if (!old_form) {
-            // cells per wave: GW_RUN where that still leaves four rounds of waves for the chip (two per SIMD), fewer on a small grid
-            int run = (int)(ncells / (4LL * 2048));
-            run = run < 1 ? 1 : run > GW_RUN ? GW_RUN : run;
+        if (run > 0) {
             hipLaunchKernelGGL(gram_wave_kernel<D>, dim3((unsigned)((ncells + 4 * run - 1) / (4 * run))), dim3(256), 0, st, g, s.offset,
                                s.xs, s.ys, s.ws, s.cap, blk, rblk, hblk, hist, cell0, ncells, run);
             return true;
@@ -815,27 +839,27 @@ static bool gram_cells(const Grid &g, const SortScratch &s, double *blk, double 
 }
 
 hipError_t launch_gram(const Grid &g, const SortScratch &s, double *scratch, long long scratch_doubles, bool smooth,
-                       double *nst, double *rhs, double *hist, double *scalH, hipStream_t st)
+                       double *nst, double *rhs, double *hist, double *scalH, hipStream_t st, GramShape *shape)
 {
     // The per-cell blocks are produced and gathered slab by slab: as many whole hyper-rows of cells (along
     // the slowest dimension) as the scratch holds -- all of them at 64^3 (3.9 GB), two or three slabs of
     // the 189 GB that the 29^4 cells of the 4-D 32^4 grid would need at once.
-    const long long per_cell = gram_tri(g.nb) + 2LL * g.nb;
+    GramShape sh;
+    if (!gram_shape(g, scratch_doubles, &sh)) return hipErrorInvalidValue;
+    if (shape) *shape = sh;
     const int hrow = g.cellstride[g.ndim - 1];              // cells per hyper-row
     const int nhrow = g.cells[g.ndim - 1];
-    long long fit_rows = scratch_doubles / (per_cell * hrow);
-    if (fit_rows < 1) return hipErrorInvalidValue;
-    if (fit_rows > nhrow) fit_rows = nhrow;
     const int nstride = g.colstride[g.ndim - 1];            // nodes per hyper-row of nodes
-    for (int h0 = 0; h0 < nhrow; h0 += (int)fit_rows) {
-        const int h1 = (h0 + fit_rows < nhrow) ? h0 + (int)fit_rows : nhrow;
+    for (int h0 = 0; h0 < nhrow; h0 += sh.rows) {
+        const int h1 = (h0 + sh.rows < nhrow) ? h0 + sh.rows : nhrow;
         const int cell0 = h0 * hrow, cell1 = h1 * hrow, ncells = cell1 - cell0;
+        const int run = h1 < nhrow ? sh.run : sh.last_run;
         const int node0 = h0 * nstride, node1 = (h1 + 3) * nstride;     // window starts h0..h1-1 touch nodes h0..h1+2
         double *blk = scratch;
         double *rblk = blk + (long long)ncells * gram_tri(g.nb);
         double *hblk = smooth ? rblk + (long long)ncells * g.nb : nullptr;
         DISPATCH_D(g.ndim, {
-            const bool zeroed = gram_cells<D>(g, s, blk, rblk, hblk, hist, cell0, ncells, st);
+            const bool zeroed = gram_cells<D>(g, s, blk, rblk, hblk, hist, cell0, ncells, run, st);
             const dim3 gg((unsigned)((node1 - node0 + 3) / 4));
             if (zeroed)
                 hipLaunchKernelGGL((stencil_gather_kernel<D, true>), gg, dim3(256), 0, st, g, s.offset, blk, rblk, hblk,

@@ -63,6 +63,8 @@ enum { SC_TOTLWT = 0, SC_NROWS_DATA = 1, SC_NROWS_CONS = 2, SC_ERRFLAG = 3, SC_S
 
 struct SortScratch {
     int *key;        // [max_ndata] cell key per point (ncell = zero-weight sentinel)
+    int *ordtmp;     // [max_ndata] the atomic route's re-sort parks the ordered indices of a cell of more than 1 024 points here; allocated where
+                     // that route is known when the scratch is made (bin_route), else NULL: the re-sort then parks them in `key`, dead by then
     int *count;      // [ncell + 2]
     int *offset;     // [ncell + 2] exclusive scan of count
     int *cursor;     // [ncell + 1]
@@ -82,6 +84,10 @@ constexpr int SP_Q = 8192;         // points per block of the stable partition
 constexpr int SP_NB = 4096;        // bins (the last one holds the zero-weight points)
 // doubles of SortScratch::rec a grid needs (0: one level suffices)
 long long bin_record_doubles(const Grid &g, long long max_ndata);
+// the form launch_bin_points takes on this grid with this scratch, under the options as they are now: 0 the atomic route
+// (SPLPAK_BIN_ATOMIC, or a grid of too many cells for the partition), 1 the stable partition in one level, 2 in two levels with
+// tiles of at most 256 cells, 3 with tiles of up to SP_NB - 1 cells.  *cpt: the cells per bin of the first level (0: too many cells)
+int bin_route(const Grid &g, const SortScratch &s, int *cpt);
 
 // binning: window keys + per-cell counts + scalars -> scan -> counting-sort scatter -> points of every
 // cell ordered by original index
@@ -97,10 +103,21 @@ hipError_t launch_regather_values(const Grid &g, const SortScratch &s, long long
 // right-hand sides, histogram shares), and the least it can work with (one hyper-row of cells)
 long long gram_scratch_doubles(const Grid &g);
 long long gram_scratch_min_doubles(const Grid &g);
+// How launch_gram cuts a grid into slabs (whole hyper-rows of cells along the slowest dimension: as many as the scratch holds) and
+// how many consecutive cells a wave of the cell kernel owns in each: every slab but the last has `cells` cells, the last
+// `last_cells`.  A run of 0: the grid's cell kernel does not work in runs (1-D, 4-D, SPLPAK_GRAM_VALU).
+struct GramShape {
+    int nslab, rows;          // slabs; hyper-rows per slab (the last one: what is left)
+    int cells, run;           // every slab but the last
+    int last_cells, last_run;
+};
+// false: the scratch does not hold one hyper-row.  Read under the options of the fit (SPLPAK_GRAM_VALU)
+bool gram_shape(const Grid &g, long long scratch_doubles, GramShape *out);
 // per-cell Gram blocks -> (owner gathers) half-stencil normal equations nst[ncol][hstencil], rhs[ncol] and,
-// when smooth, the nearest-node histogram hist[ncol] (caller's order; must be zero on entry) + its total
+// when smooth, the nearest-node histogram hist[ncol] (caller's order; must be zero on entry) + its total.
+// shape != NULL: the slabs and runs it launched (gram_shape)
 hipError_t launch_gram(const Grid &g, const SortScratch &s, double *scratch, long long scratch_doubles, bool smooth,
-                       double *nst, double *rhs, double *hist, double *scalH, hipStream_t st);
+                       double *nst, double *rhs, double *hist, double *scalH, hipStream_t st, GramShape *shape = nullptr);
 // the table of the constraint rows' factors (constraints.hip), once per plan: built beside the Gram kernels, see gram.hip
 long long constraint_table_doubles(const Grid &g);
 hipError_t launch_constraint_table(const Grid &g, double *ctab, hipStream_t st);

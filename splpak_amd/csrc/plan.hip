@@ -97,6 +97,31 @@ bool band_alloc_inverses(splpak_plan *p, Band &b, size_t nblocks, bool sweeps)
            (!sweeps || (dev_alloc(p, &b.mfwd, nblocks * NBLK * NBLK) && dev_alloc(p, &b.mbwd, nblocks * NBLK * NBLK)));
 }
 
+bool sort_scratch_alloc(splpak_plan *owner, const Grid &g, long long max_ndata, SortScratch *s)
+{
+    bool ok = true;
+    s->cap = max_ndata;
+    ok = ok && dev_alloc(owner, &s->key, (size_t)max_ndata);
+    ok = ok && dev_alloc(owner, &s->count, (size_t)g.ncell + 2);
+    ok = ok && dev_alloc(owner, &s->scanpart, (size_t)256);
+    ok = ok && dev_alloc(owner, &s->offset, (size_t)g.ncell + 2);
+    ok = ok && dev_alloc(owner, &s->cursor, (size_t)g.ncell + 2);
+    ok = ok && dev_alloc(owner, &s->xs, (size_t)max_ndata * g.ndim);
+    ok = ok && dev_alloc(owner, &s->ys, (size_t)max_ndata);
+    ok = ok && dev_alloc(owner, &s->ws, (size_t)max_ndata);
+    ok = ok && dev_alloc(owner, &s->idx, (size_t)max_ndata);
+    {   // stable partition of the points (binpoints.hip sp_*): count matrix, bin bases, tile-sorted records for grids of more cells than bins
+        const size_t nblk = (size_t)((max_ndata + SP_Q - 1) / SP_Q);
+        ok = ok && dev_alloc(owner, &s->cntm, nblk * SP_NB);
+        ok = ok && dev_alloc(owner, &s->binbase, (size_t)2 * SP_NB + 16);      // bin bases | bin totals
+        ok = ok && dev_alloc(owner, &s->sppart, ((nblk + 15) / 16) * SP_NB);
+        const long long rd = bin_record_doubles(g, max_ndata);
+        if (rd > 0) ok = ok && dev_alloc(owner, &s->rec, (size_t)rd);
+    }
+    if (ok && bin_route(g, *s, nullptr) == 0) ok = dev_alloc(owner, &s->ordtmp, (size_t)max_ndata);      // the atomic route: the keys survive its re-sort
+    return ok;
+}
+
 int device_ready()
 {
     int n = 0;
@@ -158,26 +183,7 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     p->g = g;
     p->xtrap = xtrap;
     p->max_ndata = max_ndata;
-    bool ok = true;
-    // sort scratch
-    p->s.cap = max_ndata;
-    ok = ok && dev_alloc(p, &p->s.key, (size_t)max_ndata);
-    ok = ok && dev_alloc(p, &p->s.count, (size_t)g.ncell + 2);
-    ok = ok && dev_alloc(p, &p->s.scanpart, (size_t)256);
-    ok = ok && dev_alloc(p, &p->s.offset, (size_t)g.ncell + 2);
-    ok = ok && dev_alloc(p, &p->s.cursor, (size_t)g.ncell + 2);
-    ok = ok && dev_alloc(p, &p->s.xs, (size_t)max_ndata * g.ndim);
-    ok = ok && dev_alloc(p, &p->s.ys, (size_t)max_ndata);
-    ok = ok && dev_alloc(p, &p->s.ws, (size_t)max_ndata);
-    ok = ok && dev_alloc(p, &p->s.idx, (size_t)max_ndata);
-    {   // stable partition of the points (binpoints.hip sp_*): count matrix, bin bases, tile-sorted records for grids of more cells than bins
-        const size_t nblk = (size_t)((max_ndata + SP_Q - 1) / SP_Q);
-        ok = ok && dev_alloc(p, &p->s.cntm, nblk * SP_NB);
-        ok = ok && dev_alloc(p, &p->s.binbase, (size_t)2 * SP_NB + 16);      // bin bases | bin totals
-        ok = ok && dev_alloc(p, &p->s.sppart, ((nblk + 15) / 16) * SP_NB);
-        const long long rd = bin_record_doubles(g, max_ndata);
-        if (rd > 0) ok = ok && dev_alloc(p, &p->s.rec, (size_t)rd);
-    }
+    bool ok = sort_scratch_alloc(p, g, max_ndata, &p->s);
     {   // per-cell shares of the residual passes of residual.hip: 1-D .. 3-D grids; a 4-D grid's passes go tile by tile (rowsop.hip)
         // and leave this scratch out (1.45 GB at 32^4) unless the A/B switches ask for the cell-by-cell forms
         const bool tiled = g.ndim == 4 && rows_tiles && !splpak::opt_get("SPLPAK_RESIDUAL_CELLS");

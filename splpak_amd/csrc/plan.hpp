@@ -110,6 +110,7 @@ struct splpak_plan {
     double factor_flop = 0.0;     // flop of the plan's factorisation where known (nested dissection), else 0
     bool rows_only = false;       // iteration-only 4-D plans: the normal equations are never assembled (right-hand side, histogram and
                                   // backward-error denominators come from the rows: rowsop.hip); no half stencil, no Gram scratch
+    splpak::GramShape gshape{};   // slabs and runs of the last launch_gram (splpak_debug_plan_gram_shape); nslab = 0: none yet
     bool ne_valid = false;        // nst / rhs hold what the last fit assembled (splpak_debug_plan_normal_equations)
     bool fit_valid = false;       // the binned points, dcw, spf and rhs are those of a completed single-rank fit (splpak_debug_plan_rows_gradient)
     bool fit_rows = false;        // ... which never assembled the normal equations (a rows-only plan, or a lazy fit the iteration answered)
@@ -180,6 +181,8 @@ template <typename T> static bool dev_alloc(splpak_plan *p, T **ptr, size_t coun
     *ptr = static_cast<T *>(q);
     return true;
 }
+// plan.hip: everything launch_bin_points needs for up to max_ndata points on the grid, owned by `owner`
+bool sort_scratch_alloc(splpak_plan *owner, const Grid &g, long long max_ndata, SortScratch *s);
 // plan.hip: the band's block inverses of nblocks diagonal blocks -- sweeps: with the sweep blocks of the one-GPU solves
 bool band_alloc_inverses(splpak_plan *p, Band &b, size_t nblocks, bool sweeps);
 // narrow bands on one GPU: install the two-ended factorisation (twoend.hip) when it shortens the chain

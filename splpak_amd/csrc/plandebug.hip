@@ -1,5 +1,6 @@
 // The debug entries of the C ABI (include/splpak_hip.h): one piece of a plan's fit alone, in the caller's (reference) column numbering --
-// the assembled normal equations, the factorisation, the pass over the rows, the preconditioner --, and the band Cholesky on a caller's matrix.
+// the assembled normal equations, the factorisation, the pass over the rows, the preconditioner --, the shape of the last Gram pass, and two
+// that need no plan: the binning of a caller's points in the library's internal numbering, and the band Cholesky on a caller's matrix.
 #include "plan.hpp"
 
 #include <cstring>
@@ -187,6 +188,80 @@ int32_t splpak_debug_plan_pcg_diagonal(const splpak_plan *p, double *dinv)
     if (int rc = pcg_debug_diagonal(p->pcg, v.data())) return rc;
     for (int i = 0; i < g.ncol; ++i) dinv[ref_column(g, i)] = v[(size_t)i];
     return 0;
+}
+
+int32_t splpak_debug_plan_gram_shape(const splpak_plan *p, int32_t *out6)
+{
+    if (!p || !out6) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (!p->ne_valid || p->gshape.nslab < 1) {
+        set_error("the plan's last fit did not assemble the normal equations: no Gram pass to describe");
+        return SPLPAK_E_UNSUPPORTED;
+    }
+    const GramShape &s = p->gshape;
+    const int v[6] = {s.nslab, s.rows, s.cells, s.run, s.last_cells, s.last_run};
+    for (int i = 0; i < 6; ++i) out6[i] = v[i];
+    return 0;
+}
+
+int32_t splpak_debug_bin_points(int32_t ndim, const int32_t *nodes, const double *xmin, const double *xmax, int64_t ndata,
+                                const double *xdata, int32_t l1xdat, const double *ydata, const double *wdata, int32_t *perm,
+                                int32_t *cells, int32_t *cellstride, int32_t *route, int32_t *cpt, int32_t *key, int32_t *offset,
+                                int32_t *idx, double *xs, double *ys, double *ws, int64_t *placed, double *nrows_data)
+{
+    if (!nodes || !xmin || !xmax || !xdata || !ydata || !perm || !cells || !cellstride || !route || !cpt || !key || !offset || !idx ||
+        !xs || !ys || !ws || !placed || !nrows_data) {
+        set_error("null argument");
+        return SPLPAK_E_BADARG;
+    }
+    if (ndata < 1 || ndata > (int64_t)std::numeric_limits<int32_t>::max() - 1024) { set_error("ndata outside 1 .. 2^31 - 1025"); return SPLPAK_E_BADARG; }
+    Grid g;
+    const int v = build_grid(ndim, nodes, xmin, xmax, g, nullptr, splpak::opt_get("SPLPAK_NO_REORDER") == nullptr);
+    if (v != 0) {
+        if (v == SPLPAK_E_UNSUPPORTED) set_error("ndim > 4 or more than 2^30 nodes is not supported");
+        return v;
+    }
+    if (l1xdat < ndim) { set_error("l1xdat < ndim"); return SPLPAK_E_BADARG; }
+    if (int r = device_ready()) return r;
+    for (int d = 0; d < ndim; ++d) { perm[d] = g.perm[d]; cells[d] = g.cells[d]; cellstride[d] = g.cellstride[d]; }
+    splpak_plan holder;
+    SortScratch s{};
+    double *dx = nullptr, *dy = nullptr, *dw = nullptr, *dscal = nullptr;
+    const size_t m = (size_t)ndata;
+    const bool ok = sort_scratch_alloc(&holder, g, ndata, &s) && dev_alloc(&holder, &dx, m * (size_t)l1xdat) && dev_alloc(&holder, &dy, m) &&
+                    (!wdata || dev_alloc(&holder, &dw, m)) && dev_alloc(&holder, &dscal, (size_t)SC_COUNT);
+    int rc = ok ? 0 : SPLPAK_E_NOMEM;
+    if (ok) {
+        *route = bin_route(g, s, cpt);
+        double hscal[SC_COUNT];
+        int np = 0;
+        hipError_t e = hipMemcpy(dx, xdata, sizeof(double) * m * (size_t)l1xdat, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dy, ydata, sizeof(double) * m, hipMemcpyHostToDevice);
+        if (e == hipSuccess && wdata) e = hipMemcpy(dw, wdata, sizeof(double) * m, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(dscal, 0, sizeof(double) * SC_COUNT);
+        if (e == hipSuccess) e = launch_bin_points(g, ndata, dx, l1xdat, dy, dw, s, dscal, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipMemcpy(hscal, dscal, sizeof hscal, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(key, s.key, sizeof(int) * m, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(offset, s.offset, sizeof(int) * ((size_t)g.ncell + 1), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) np = offset[g.ncell];
+        if (!hip_ok(e, "binning")) rc = SPLPAK_E_NODEVICE;
+        else if (np < 0 || (int64_t)np > ndata) {
+            set_error("the binning placed " + std::to_string(np) + " of " + std::to_string((long long)ndata) + " points");
+            rc = SPLPAK_E_NODEVICE;
+        } else {
+            const size_t n = (size_t)np;
+            e = hipMemcpy(idx, s.idx, sizeof(int) * n, hipMemcpyDeviceToHost);
+            for (int d = 0; d < ndim && e == hipSuccess; ++d)
+                e = hipMemcpy(xs + (size_t)d * m, s.xs + (size_t)d * (size_t)s.cap, sizeof(double) * n, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(ys, s.ys, sizeof(double) * n, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(ws, s.ws, sizeof(double) * n, hipMemcpyDeviceToHost);
+            if (!hip_ok(e, "binning")) rc = SPLPAK_E_NODEVICE;
+            *placed = np;
+            *nrows_data = hscal[SC_NROWS_DATA];
+        }
+    }
+    for (void *q : holder.owned) (void)hipFree(q);
+    return rc;
 }
 
 int32_t splpak_debug_spd_band_solve_f64(int32_t n, int32_t halfbw, const double *a_lower,

@@ -26,6 +26,13 @@ def test_library_exports_every_declared_symbol():
     assert sorted(capi.SYMBOLS) == declared
 
 
+def test_assembly_debug_entries_are_declared_and_exported():
+    L = capi.lib()
+    declared = _declared_symbols()
+    for name in ("splpak_debug_bin_points", "splpak_debug_plan_gram_shape"):
+        assert name in declared and name in capi.SYMBOLS and hasattr(L, name), name
+
+
 def test_fit_validation_order_without_gpu():
     """101..106 are decided on the host before any device work (:716-781)."""
     x = np.linspace(0, 1, 20).reshape(-1, 1)

@@ -8,7 +8,8 @@ rows (rhs - N c is the rows' gradient at any c); the new diagnostic entries' arg
 nested-dissection tree (splpak_debug_nd_fronts).
 GPU tier:
   A. what a fit assembled (splpak_debug_plan_normal_equations) against the oracle, entry by entry, with exact zeros where the
-     oracle has no term at all (a contribution scattered into the wrong slot);
+     oracle has no term at all (a contribution scattered into the wrong slot); the same on the grids where a wave of the Gram pass
+     owns a run of 2, 3 or 8 cells (test_gram_runs_match_oracle);
   B. every factorisation alone (splpak_debug_plan_solve): synthetic SPD matrices with independent random entries on the 7^d
      pattern (forward error) and the fits' own N (backward error; and bitwise the coefficients of a fit without refinement);
   C. a matrix that is not positive definite at a chosen column: 107 from every factorisation, then the same plan solves again.
@@ -325,6 +326,126 @@ def test_assembly_variants_match_oracle(port, name, monkeypatch):
             monkeypatch.delenv(k)
         assert ierr == 0
         _compare_ne(f"{name} {env}", inp, N, rhs, info, ne)
+
+
+# ---- Gram passes in which a wave owns a RUN of consecutive cells (gram.hip gram_wave_kernel, 2-D and 3-D): launch_gram gives a
+# wave min(8, cells of the slab / 8192) cells, so every grid above stays at run 1.  What exists only for runs -- the offsets of a
+# run in one register, the next cell's first chunk fetched before the current cell's products, the empty-cell shortcut inside a
+# run, a last wave with fewer cells than its run -- is reached by grid size here, and the run is asserted from the plan.
+# name -> nodes, points, seed, run, whether the cell count leaves a short last run, xtrap, SPLPAK_GRAM_SCRATCH_MB, expected shape
+GRAM_RUN_CASES = {
+    "2d131_run2": dict(nodes=[131, 131], m=40000, seed=31, run=2, short=False),           # 16 384 cells = 2 * 8 192: no short run
+    "2d184_run3": dict(nodes=[184, 184], m=75000, seed=32, run=3, short=True),            # 32 761 = 3 * 10 920 + 1
+    "2d260_run8": dict(nodes=[260, 260], m=150000, seed=33, run=8, short=True),           # 66 049 = 32 * 2 064 + 1: one wave, one cell
+    "3d29_run2": dict(nodes=[29, 29, 29], m=60000, seed=34, run=2, short=False),          # 17 576 cells = 2 * 8 788: no short run
+    "3d44_run8": dict(nodes=[44, 44, 44], m=150000, seed=35, run=8, short=True),          # 68 921 = 8 * 8 615 + 1
+    # slabs of 69 hyper-rows of 257 cells (23 MB of scratch / 345 408 bytes per hyper-row): run 2 where the whole grid takes 8
+    "2d260_slabs_run2": dict(nodes=[260, 260], m=150000, seed=33, run=2, short=True, scratch_mb=23,
+                             shape=dict(slabs=4, rows=69, cells=17733, run=2, last_cells=12850, last_run=1)),
+    # no smoothing: the kernel without a histogram (hblk == nullptr); no cell may be empty, so only the busy-cell pattern applies
+    "2d131_run2_xtrap0": dict(nodes=[131, 131], m=600000, seed=36, run=2, short=False, xtrap=0.0),
+}
+
+
+def _cell_keys(inp):
+    """Cell of every point (dimension 0 fastest), with the library's own arithmetic (basis.hpp window_start)."""
+    nodes = np.asarray(inp["nodes"], dtype=np.int64)
+    dx = (inp["xmax"] - inp["xmin"]) / (nodes - 1).astype(np.float64)
+    t = (1.0 / dx) * (inp["xdata"][:, :inp["ndim"]] - inp["xmin"])
+    ws = np.clip(np.trunc(t).astype(np.int64) - 1, 0, nodes - 4)
+    return np.ravel_multi_index(ws[:, ::-1].T, (nodes - 3)[::-1])
+
+
+def _run_patterns(pop, slabs):
+    """What the runs of the slabs [(first cell, cells, run)] contain, from the points per cell."""
+    found = dict(busy_then_some=False, empty_then_some=False, first_empty=False, all_empty=False, short_last=False)
+    for c0, n, run in slabs:
+        nfull = n // run
+        groups = [pop[c0:c0 + nfull * run].reshape(nfull, run)]
+        if n % run:
+            groups.append(pop[c0 + nfull * run:c0 + n][None, :])
+            found["short_last"] = True
+        for g in groups:
+            if g.shape[1] > 1:
+                found["busy_then_some"] |= bool(np.any((g[:, :-1] > 64) & (g[:, 1:] > 0)))
+                found["empty_then_some"] |= bool(np.any((g[:, :-1] == 0) & (g[:, 1:] > 0)))
+            found["first_empty"] |= bool(np.any((g[:, 0] == 0) & (g.max(axis=1) > 0)))
+            found["all_empty"] |= bool(np.any(g.max(axis=1) == 0))
+    return found
+
+
+def _gram_run_inputs(name):
+    """The seeded stream of synth_points, permuted, a third of it moved into a patch of 5 % of the box's side; then, in the middle of
+    the first slab, the points of one whole run and of the first cell of another are taken out, and a cell of 70 points followed by one of 2
+    is put in: every pattern a run can hold is there whatever the stream happens to give."""
+    c = GRAM_RUN_CASES[name]
+    nd, run = len(c["nodes"]), c["run"]
+    inp = _seeded(nd, c["nodes"], c["m"], c["seed"], xtrap=c.get("xtrap", 1.0))
+    x, y, w = inp["xdata"].copy(), inp["ydata"].copy(), inp["wdata"].copy()
+    third = c["m"] // 3
+    x[:third] = 0.3 + 0.05 * x[:third]
+    inp.update(xdata=x, ydata=y, wdata=w)
+    if c.get("xtrap", 1.0) == 0.0:
+        return inp
+    cells = np.asarray(c["nodes"]) - 3
+    b = (c.get("shape", dict(cells=int(np.prod(cells))))["cells"] // run) // 2       # a run in the middle of the first slab ...
+    while np.any(np.unravel_index(np.arange(b * run, (b + 4) * run), cells[::-1])[-1] < 2):
+        b += 1                                                  # ... of interior cells along dimension 0
+    key = _cell_keys(inp)
+    keep = ~(((key >= b * run) & (key < (b + 1) * run)) | (key == (b + 2) * run))
+    rng = np.random.default_rng(c["seed"] + 100)
+    newc = np.concatenate([np.full(2, (b + 2) * run + 1), np.full(70, (b + 3) * run), np.full(2, (b + 3) * run + 1)])
+    ws = np.stack(np.unravel_index(newc, cells[::-1])[::-1], axis=1)
+    xn = (ws + 1.0 + rng.uniform(0.05, 0.95, ws.shape)) / (np.asarray(c["nodes"]) - 1.0)
+    inp.update(xdata=np.ascontiguousarray(np.vstack([x[keep], xn])), ydata=np.concatenate([y[keep], np.sin(xn.sum(axis=1))]),
+               wdata=np.concatenate([w[keep], rng.uniform(0.5, 1.5, newc.size)]))
+    return inp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(GRAM_RUN_CASES))
+def test_gram_runs_match_oracle(port, name, monkeypatch):
+    """The normal equations of grids on which a wave of the Gram pass owns 2, 3 or 8 cells, entry by entry against the oracle
+    under the rule of test_assembly_matches_oracle, with exact zeros where the rows have no term.  The run (and with
+    SPLPAK_GRAM_SCRATCH_MB the slabs) comes from splpak_debug_plan_gram_shape and must be what the case names; the points per
+    cell are asserted to hold, inside a run: a cell of more than 64 points followed by a non-empty one (a second chunk while the
+    next cell's prefetch is pending), an empty cell followed by a non-empty one, a run starting with an empty cell, a run of empty
+    cells only, and -- where the cell count is no multiple of the run: not at 16 384 and 17 576 cells with run 2 -- the short
+    last run.  xtrap = 0 allows no empty cell: that case is about the kernel without a histogram and rests on the fit returning 0.
+    The oracle's own time is the long part: about 8 s for 44^3 on 16 threads, below 2 s for the others."""
+    c = GRAM_RUN_CASES[name]
+    monkeypatch.setenv("SPLPAK_SOLVER", "direct")
+    inp = _gram_run_inputs(name)
+    nd, ncell = inp["ndim"], int(np.prod(np.asarray(c["nodes"]) - 3))
+    raw = capi.debug_bin_points(inp["nodes"], inp["xmin"], inp["xmax"], inp["xdata"], inp["ydata"], inp["wdata"])
+    assert np.array_equal(raw["perm"], np.arange(nd))          # equal node counts: the internal cell order is the caller's
+    key = _cell_keys(inp)
+    pop = np.bincount(key[inp["wdata"] != 0], minlength=ncell)
+    assert np.array_equal(np.diff(raw["offset"]), pop)
+    if "scratch_mb" in c:
+        monkeypatch.setenv("SPLPAK_GRAM_SCRATCH_MB", str(c["scratch_mb"]))
+    ierr, info, _, N, rhs, _, plan = _fit_ne(inp)
+    try:
+        shape = plan.gram_shape()
+    finally:
+        plan.close()
+    want = c.get("shape", dict(slabs=1, rows=int(c["nodes"][-1]) - 3, cells=ncell, run=c["run"], last_cells=ncell, last_run=c["run"]))
+    slabs = [(i * shape["cells"], shape["cells"], shape["run"]) for i in range(shape["slabs"] - 1)]
+    slabs.append(((shape["slabs"] - 1) * shape["cells"], shape["last_cells"], shape["last_run"]))
+    found = _run_patterns(pop, slabs)
+    empty = int(np.count_nonzero(pop == 0))
+    print(f"{name}: {shape}; {inp['xdata'].shape[0]} points, {empty} of {ncell} cells empty, {int(np.count_nonzero(pop > 64))} of more "
+          f"than 64 points; {found}")
+    assert shape == want, name
+    if c.get("xtrap", 1.0) == 0.0:
+        assert empty == 0 and found["busy_then_some"], found
+    else:
+        assert found == dict(busy_then_some=True, empty_then_some=True, first_empty=True, all_empty=True, short_last=c["short"]), found
+    assert ierr == 0
+    ne = _oracle_ne(port, inp)
+    big = _busiest_cell(inp)
+    tol = min(max(NE_TOL, big * 2.0 ** -53), NE_CEIL)
+    _compare_ne(f"{name} (run {shape['run']}, busiest cell {big} points)", inp, N, rhs, info, ne, tol)
 
 
 @pytest.mark.gpu
