@@ -407,8 +407,58 @@ int32_t splpak_eval_grid_dev_f32(int32_t ndim, const int64_t *npts /* host */, c
 int64_t splpak_eval_grid_scratch_bytes(int32_t ndim, const int64_t *npts);
 /* Diagnostics: how many workgroup tiles of the calling thread's last grid call contracted a coefficient box staged in
  * LDS (out2[0]) and how many gathered every window from global memory (out2[1]: boxes beyond the LDS budget -- coarse
- * or unsorted axes -- and every 1-D call).  Waits for that call.  Both forms return the same values. */
+ * or unsorted axes -- and every 1-D call).  Waits for that call.  Both forms return the same values.  A
+ * splpak_eval_grid_derivs_* call is a grid call too: after one, these are the counts of its tiles. */
 int32_t splpak_debug_eval_grid_stats(int64_t out2[2]);
+
+/* Value, gradient and (order 2) Hessian of the fit on a tensor-product grid of points in one pass: what a loop of
+ * splpak_eval_grid_* calls over the 1 + ndim (+ ndim(ndim+1)/2) nderiv patterns returns -- normals of an iso-surface,
+ * the velocity of a potential, strain, vorticity or curvature volumes on the sample splpak_eval_grid_* resamples to --
+ * with one table pass, one staging of the coefficients per tile, and the partial sums the patterns share formed once.
+ *   npts, axes  exactly as for splpak_eval_grid_*;  order  1 or 2;
+ *   out    in PLANES: entry e of grid point idx is out[e*ldout + idx], ldout >= prod_d npts[d];
+ *          idx = i0 + npts[0]*(i1 + npts[1]*(i2 + ...)) is the ordering of splpak_eval_grid_*, and e runs over the entries
+ *          of splpak_eval_derivs_* in its order: f, df/dx_1 .. df/dx_ndim, (order 2:) the upper triangle of the Hessian
+ *          row by row.  Each plane is a volume as splpak_eval_grid_* writes it.  The words between the planes,
+ *          [prod npts, ldout), are neither read nor written.
+ * Plane e >= 1 holds the very values (identical bits) of splpak_eval_grid_* called with entry e's nderiv pattern: the
+ * same factor tables and the same order of summation, whichever outputs share a partial sum.  Plane 0 is summed in that
+ * order on the GENERAL-form factor tables (what every nderiv != NULL call uses), whereas splpak_eval_grid_* with
+ * nderiv == NULL takes the closed-form value tables: plane 0 agrees with it to rounding, not to the bit.  Plane 0 has the
+ * same bits for order 1 and 2.
+ * Status, decided on the host before any device work, the first failing check wins:
+ *   SPLPAK_E_BADARG       npts, nodes, xmin or xmax null;
+ *   101                   out[0] alone is set to 0 (if `out` is not null), as the grid entries do;
+ *   SPLPAK_E_UNSUPPORTED  ndim > 4;
+ *   SPLPAK_E_BADARG       a negative npts[d] or a product of npts beyond int64; then order outside 1..2; then
+ *                         ldout < prod npts or (number of planes)*ldout beyond int64;
+ *   102 / 103             the prod npts results of EVERY plane are set to 0 (if `out` is not null), the words between
+ *                         the planes stay as they are;
+ *   a count of 0          the status so far; nothing is written;
+ *   SPLPAK_E_BADARG       axes, coef or out null.
+ * There is no nderiv argument, hence no 104. */
+int32_t splpak_eval_grid_derivs_f64(int32_t ndim, const int64_t *npts, const double *axes, int32_t order,
+                                    const double *coef, const double *xmin, const double *xmax, const int32_t *nodes,
+                                    double *out, int64_t ldout);
+int32_t splpak_eval_grid_derivs_f32(int32_t ndim, const int64_t *npts, const float *axes, int32_t order,
+                                    const float *coef, const float *xmin, const float *xmax, const int32_t *nodes,
+                                    float *out, int64_t ldout);
+/* the same on resident data (asynchronous on `stream`); npts, xmin, xmax and nodes are host arrays */
+int32_t splpak_eval_grid_derivs_dev_f64(int32_t ndim, const int64_t *npts /* host */, const double *axes_dev, int32_t order,
+                                        const double *coef_dev, const double *xmin, const double *xmax,
+                                        const int32_t *nodes, double *out_dev, int64_t ldout, void *stream);
+int32_t splpak_eval_grid_derivs_dev_f32(int32_t ndim, const int64_t *npts /* host */, const float *axes_dev, int32_t order,
+                                        const float *coef_dev, const float *xmin, const float *xmax,
+                                        const int32_t *nodes, float *out_dev, int64_t ldout, void *stream);
+/* Device memory (bytes) such a call keeps per calling thread until splpak_shutdown: the two tile counters and, per axis
+ * coordinate, a window start and order + 1 factor quadruples: 16 + (32*(order + 1) + 8) * sum_d npts[d].  It is the scratch of
+ * splpak_eval_grid_*, grown on demand: a thread holds the larger of the two needs, not their sum.  0 when a count is 0;
+ * SPLPAK_E_BADARG for a shape or an order the entries reject. */
+int64_t splpak_eval_grid_derivs_scratch_bytes(int32_t ndim, const int64_t *npts, int32_t order);
+/* Host only: the outputs per workgroup tile per dimension (1 beyond ndim) of a splpak_eval_grid_derivs_* call with this
+ * ndim and order, so that the tiles splpak_debug_eval_grid_stats counts can be predicted.  Every (ndim, order) class runs
+ * the fused tile kernel.  SPLPAK_E_BADARG: ndim outside 1..4, order outside 1..2 or a null pointer. */
+int32_t splpak_debug_eval_grid_derivs_tile(int32_t ndim, int32_t order, int32_t out4[4]);
 
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
  * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one

@@ -33,6 +33,8 @@ SYMBOLS = [
     "splpak_eval_dev_f64", "splpak_eval_dev_f32", "splpak_eval_derivs_f64", "splpak_eval_derivs_f32", "splpak_eval_derivs_dev_f64",
     "splpak_eval_grid_f64", "splpak_eval_grid_f32", "splpak_eval_grid_dev_f64", "splpak_eval_grid_dev_f32",
     "splpak_eval_grid_scratch_bytes", "splpak_debug_eval_grid_stats",
+    "splpak_eval_grid_derivs_f64", "splpak_eval_grid_derivs_f32", "splpak_eval_grid_derivs_dev_f64", "splpak_eval_grid_derivs_dev_f32",
+    "splpak_eval_grid_derivs_scratch_bytes", "splpak_debug_eval_grid_derivs_tile",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
     "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
@@ -150,6 +152,18 @@ def lib() -> C.CDLL:
     L.splpak_eval_grid_scratch_bytes.argtypes = [i32, _lp]
     L.splpak_debug_eval_grid_stats.restype = i32
     L.splpak_debug_eval_grid_stats.argtypes = [_lp]
+    L.splpak_eval_grid_derivs_f64.restype = i32
+    L.splpak_eval_grid_derivs_f64.argtypes = [i32, _lp, _dp, i32, _dp, _dp, _dp, _ip, _dp, i64]
+    L.splpak_eval_grid_derivs_f32.restype = i32
+    L.splpak_eval_grid_derivs_f32.argtypes = [i32, _lp, _fp, i32, _fp, _fp, _fp, _ip, _fp, i64]
+    L.splpak_eval_grid_derivs_dev_f64.restype = i32
+    L.splpak_eval_grid_derivs_dev_f64.argtypes = [i32, _lp, vp, i32, vp, _dp, _dp, _ip, vp, i64, vp]
+    L.splpak_eval_grid_derivs_dev_f32.restype = i32
+    L.splpak_eval_grid_derivs_dev_f32.argtypes = [i32, _lp, vp, i32, vp, _fp, _fp, _ip, vp, i64, vp]
+    L.splpak_eval_grid_derivs_scratch_bytes.restype = i64
+    L.splpak_eval_grid_derivs_scratch_bytes.argtypes = [i32, _lp, i32]
+    L.splpak_debug_eval_grid_derivs_tile.restype = i32
+    L.splpak_debug_eval_grid_derivs_tile.argtypes = [i32, i32, _ip]
     L.splpak_eval_fields_f64.restype = i32
     L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
     L.splpak_eval_fields_f32.restype = i32
@@ -451,6 +465,37 @@ def debug_eval_grid_stats():
     v = np.zeros(2, dtype=np.int64)
     _check(lib().splpak_debug_eval_grid_stats(_p(v, C.POINTER(C.c_int64))))
     return int(v[0]), int(v[1])
+
+
+def evaluate_grid_derivs(ndim, axes, order, coef, xmin, xmax, nodes, real32=False):
+    """Value, gradient and (order 2) Hessian at every point of the tensor-product grid axes[0] x axes[1] x ...
+    (splpak_eval_grid_derivs_*).  -> (array of shape (nplanes, len(axes[ndim-1]), ..., len(axes[0])): plane e is entry e of
+    evaluate_derivs, each plane a volume as evaluate_grid returns it; ierror)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
+    npts = np.array([a.size for a in axes], dtype=np.int64)
+    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    coef = np.ascontiguousarray(coef, dtype=dt)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    out = np.zeros((derivs_nout(max(int(ndim), 0), order),) + tuple(int(n) for n in npts[::-1]), dtype=dt)
+    fn = lib().splpak_eval_grid_derivs_f32 if real32 else lib().splpak_eval_grid_derivs_f64
+    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, rp), int(order), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), _p(out, rp), int(np.prod(npts)) if npts.size else 1))
+    return out, rc
+
+
+def eval_grid_derivs_scratch_bytes(npts, order) -> int:
+    """Bytes of per-thread device scratch a grid-derivatives call of this shape keeps until shutdown()."""
+    npts = np.ascontiguousarray(npts, dtype=np.int64)
+    return _check(lib().splpak_eval_grid_derivs_scratch_bytes(int(npts.size), _p(npts, C.POINTER(C.c_int64)), int(order)))
+
+
+def debug_eval_grid_derivs_tile(ndim, order):
+    """Outputs per workgroup tile per dimension (1 beyond ndim) of a grid-derivatives call with this ndim and order."""
+    v = np.zeros(4, dtype=np.int32)
+    _check(lib().splpak_debug_eval_grid_derivs_tile(int(ndim), int(order), _p(v, _ip)))
+    return tuple(int(t) for t in v)
 
 
 def evaluate_fields(ndim, xq, nderiv, coefs, xmin, xmax, nodes, real32=False, ldcoef=None, ldout=None):
@@ -797,6 +842,25 @@ def evaluate_grid_dev(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, st
     return _check(lib().splpak_eval_grid_dev_f64(ndim, _p(npts, lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
                                                  _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), out.data_ptr(),
                                                  C.c_void_p(stream)))
+
+
+def evaluate_grid_derivs_dev(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, stream=0):
+    """Value, gradient and (order 2) Hessian planes on torch device tensors (asynchronous on `stream`): `axes` as for
+    evaluate_grid_dev; `out` is a 2-D tensor (nplanes, >= prod(npts)) with unit stride inside a row, its row stride is passed
+    as ldout.  float32 tensors take the REAL32 entry."""
+    npts = np.ascontiguousarray(npts, dtype=np.int64)
+    lp = C.POINTER(C.c_int64)
+    if out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
+        raise SplpakError("evaluate_grid_derivs_dev: out must be 2-D (planes, points) with contiguous planes")
+    if order in (1, 2) and int(out.shape[0]) < derivs_nout(max(int(ndim), 0), order):
+        raise SplpakError("evaluate_grid_derivs_dev: out has fewer rows than there are planes")
+    ldo = int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1])
+    real32 = str(axes.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    fn = lib().splpak_eval_grid_derivs_dev_f32 if real32 else lib().splpak_eval_grid_derivs_dev_f64
+    rp = _fp if real32 else _dp
+    return _check(fn(ndim, _p(npts, lp), axes.data_ptr(), int(order), coef.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip),
+                     out.data_ptr(), ldo, C.c_void_p(stream)))
 
 
 EVAL_AUTO, EVAL_DIRECT, EVAL_BINNED = 0, 1, 2

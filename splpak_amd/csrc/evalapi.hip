@@ -2,7 +2,7 @@
 // pointers, the evaluation mode, and the host-only / synthetic-data helpers that need no plan.
 //
 // Every entry family has ONE ladder of argument checks (point_validate for the value and the derivative entries,
-// fields_validate, grid_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
+// fields_validate, grid_validate, grid_derivs_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
 // Where two entries of a family have always answered differently, the difference is a named parameter of the ladder.
 #include "plan.hpp"
 #include "basis.hpp"
@@ -431,6 +431,141 @@ int32_t splpak_debug_eval_grid_stats(int64_t out2[2])
     SPLPAK_HIP_TRY(eval_grid_stats(v), SPLPAK_E_NODEVICE);
     out2[0] = v[0];
     out2[1] = v[1];
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- value, gradient and Hessian planes on a tensor-product grid of points (evalgridderivs.hip) ----
+// The checks of a grid-derivatives entry before it touches a device: the ladder of grid_validate with the order and ldout
+// checks between the shape and the 102 / 103 checks.  True: the caller goes on to compute; false: rc is the status to
+// return, and zero_n results are zeroed first -- of out[0] alone (101) or, `planes`, of every plane (102 / 103).
+template <typename T>
+static bool grid_derivs_validate(int32_t ndim, const int64_t *npts, const T *axes, int32_t order, const T *coef, const T *xmin_t,
+                                 const T *xmax_t, const int32_t *nodes, const T *out, int64_t ldout, Grid &g, long long &nout,
+                                 int &rc, long long &zero_n, bool &planes)
+{
+    nout = 0;
+    zero_n = 0;
+    planes = false;
+    if (!npts) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    double xmin[MAXD], xmax[MAXD];
+    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, xmin, xmax, rc, zero_n)) return false;
+    long long ntab = 0, total = 0;
+    if (!grid_counts(ndim, npts, nout, ntab)) {
+        set_error("negative npts, or an output count beyond int64");
+        rc = SPLPAK_E_BADARG;
+        return false;
+    }
+    if (order < 1 || order > 2) { set_error("order must be 1 (gradient) or 2 (gradient and Hessian)"); rc = SPLPAK_E_BADARG; return false; }
+    if (ldout < nout || __builtin_mul_overflow((long long)derivs_nout(ndim, order), (long long)ldout, &total)) {
+        set_error("ldout smaller than the number of grid points, or the planes beyond int64");
+        rc = SPLPAK_E_BADARG;
+        return false;
+    }
+    rc = eval_validate(ndim, nullptr, xmin, xmax, nodes, g);
+    if (rc != 0) {
+        if (rc > 0 && out) { zero_n = nout; planes = true; }
+        return false;
+    }
+    if (nout == 0) return false;
+    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (int r = device_ready()) { rc = r; return false; }
+    return true;
+}
+
+template <typename T>
+static int32_t eval_grid_derivs_dev(int32_t ndim, const int64_t *npts, const T *axes_dev, int32_t order, const T *coef_dev, const T *xmin,
+                                    const T *xmax, const int32_t *nodes, T *out_dev, int64_t ldout, void *stream)
+{
+    Grid g;
+    long long nout = 0, zero_n = 0;
+    int rc = 0;
+    bool planes = false;
+    if (!grid_derivs_validate(ndim, npts, axes_dev, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, g, nout, rc, zero_n, planes)) {
+        const int np = planes ? derivs_nout(ndim, order) : 1;
+        if (zero_n > 0)
+            for (int e = 0; e < np; ++e) (void)hipMemsetAsync(out_dev + (long long)e * ldout, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
+        return rc;
+    }
+    SPLPAK_HIP_TRY(launch_eval_grid_derivs<T>(g, npts, axes_dev, order, coef_dev, out_dev, ldout, (hipStream_t)stream), SPLPAK_E_NODEVICE);
+    return rc;
+}
+
+// the host form stages through the device as staged_call does; the planes are packed there (prod npts apart) and copied
+// back one by one, so that the caller's words between the planes keep their contents
+template <typename T>
+static int32_t eval_grid_derivs_host(int32_t ndim, const int64_t *npts, const T *axes, int32_t order, const T *coef, const T *xmin,
+                                     const T *xmax, const int32_t *nodes, T *out, int64_t ldout)
+{
+    Grid g;
+    long long nout = 0, zero_n = 0;
+    int rc = 0;
+    bool planes = false;
+    if (!grid_derivs_validate(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, ldout, g, nout, rc, zero_n, planes)) {
+        const int np = planes ? derivs_nout(ndim, order) : 1;
+        for (int e = 0; e < np; ++e)
+            for (long long i = 0; i < zero_n; ++i) out[(long long)e * ldout + i] = (T)0;
+        return rc;
+    }
+    const int np = derivs_nout(ndim, order);
+    size_t ntab = 0;
+    for (int d = 0; d < ndim; ++d) ntab += (size_t)npts[d];
+    DevStage stage;
+    T *da = nullptr, *dc = nullptr, *dout = nullptr;
+    if (!stage.alloc(&da, ntab) || !stage.alloc(&dc, (size_t)g.ncol) || !stage.alloc(&dout, (size_t)np * (size_t)nout)) return SPLPAK_E_NOMEM;
+    hipError_t e = hipMemcpy(da, axes, sizeof(T) * ntab, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * (size_t)g.ncol, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_eval_grid_derivs<T>(g, npts, da, order, dc, dout, nout, nullptr);
+    for (int k = 0; k < np && e == hipSuccess; ++k)
+        e = hipMemcpy(out + (long long)k * ldout, dout + (long long)k * nout, sizeof(T) * (size_t)nout, hipMemcpyDeviceToHost);
+    return hip_ok(e, "grid evaluation of derivatives") ? rc : SPLPAK_E_NODEVICE;
+}
+
+extern "C" {
+
+int32_t splpak_eval_grid_derivs_f64(int32_t ndim, const int64_t *npts, const double *axes, int32_t order, const double *coef,
+                                    const double *xmin, const double *xmax, const int32_t *nodes, double *out, int64_t ldout)
+{
+    return eval_grid_derivs_host<double>(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, ldout);
+}
+
+int32_t splpak_eval_grid_derivs_f32(int32_t ndim, const int64_t *npts, const float *axes, int32_t order, const float *coef,
+                                    const float *xmin, const float *xmax, const int32_t *nodes, float *out, int64_t ldout)
+{
+    return eval_grid_derivs_host<float>(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, ldout);
+}
+
+int32_t splpak_eval_grid_derivs_dev_f64(int32_t ndim, const int64_t *npts, const double *axes_dev, int32_t order, const double *coef_dev,
+                                        const double *xmin, const double *xmax, const int32_t *nodes, double *out_dev, int64_t ldout,
+                                        void *stream)
+{
+    return eval_grid_derivs_dev<double>(ndim, npts, axes_dev, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, stream);
+}
+
+int32_t splpak_eval_grid_derivs_dev_f32(int32_t ndim, const int64_t *npts, const float *axes_dev, int32_t order, const float *coef_dev,
+                                        const float *xmin, const float *xmax, const int32_t *nodes, float *out_dev, int64_t ldout,
+                                        void *stream)
+{
+    return eval_grid_derivs_dev<float>(ndim, npts, axes_dev, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, stream);
+}
+
+int64_t splpak_eval_grid_derivs_scratch_bytes(int32_t ndim, const int64_t *npts, int32_t order)
+{
+    long long nout = 0, ntab = 0;
+    if (!npts || ndim < 1 || ndim > MAXD || order < 1 || order > 2 || !grid_counts(ndim, npts, nout, ntab)) {
+        set_error("bad grid shape or order");
+        return SPLPAK_E_BADARG;
+    }
+    return nout == 0 ? 0 : eval_grid_derivs_scratch_bytes(ntab, order);
+}
+
+// host only
+int32_t splpak_debug_eval_grid_derivs_tile(int32_t ndim, int32_t order, int32_t out4[4])
+{
+    int t[4];
+    if (!out4 || !eval_grid_derivs_tile(ndim, order, t)) { set_error("bad ndim, order or pointer"); return SPLPAK_E_BADARG; }
+    for (int d = 0; d < 4; ++d) out4[d] = t[d];
     return 0;
 }
 

@@ -28,8 +28,7 @@
 // HBM traffic by construction: 8 bytes per output (4 for REAL32) + the coefficient boxes (each coefficient is
 // read by the tiles whose boxes hold it, from L2 after the first) + the tables.  Output counts are 64-bit;
 // coefficient indices stay int as in Grid.
-#include "evalcore.hpp"
-#include "evalscratch.hpp"
+#include "evalgrid.hpp"
 #include <climits>
 
 namespace splpak {
@@ -46,14 +45,6 @@ template <> struct GTile<1> { static constexpr int T[4] = {256, 1, 1, 1}; static
 template <> struct GTile<2> { static constexpr int T[4] = {64, 16, 1, 1}; static constexpr int LDS = 4096; };
 template <> struct GTile<3> { static constexpr int T[4] = {64, 8, 8, 1}; static constexpr int LDS = 5376; };
 template <> struct GTile<4> { static constexpr int T[4] = {16, 4, 4, 4}; static constexpr int LDS = 7424; };
-constexpr int GRID_NT = 256;
-
-struct GridShape {
-    long long npts[MAXD];      // outputs per dimension
-    long long off[MAXD + 1];   // first table entry of every dimension (prefix of npts)
-    long long ntile[MAXD];     // tiles per dimension
-};
-
 // ---- table pass ---------------------------------------------------------------------------------------------------
 template <typename T, bool VAL>
 __global__ void __launch_bounds__(256)
@@ -275,7 +266,10 @@ eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 // per-thread scratch (evalscratch.hpp): tile counters | factors [ntab][4] | window starts [ntab] of the last call
+// (evalgridderivs.hip: factors [ntab][order + 1][4])
 static thread_local DevScratch<1> g_gscratch;
+
+DevScratch<1> &eval_grid_scratch() { return g_gscratch; }
 
 long long eval_grid_scratch_bytes(long long ntab) { return 40 * ntab + 16; }      // 32 (factors) + 4 (start), rounded; counters
 

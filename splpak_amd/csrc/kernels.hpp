@@ -51,6 +51,16 @@ long long eval_grid_scratch_bytes(long long ntab);
 hipError_t eval_grid_stats(long long out2[2]);
 void eval_grid_scratch_shutdown();
 
+// ---- evalgridderivs.hip
+// out[e ldout + idx]: entry e of launch_eval_derivs (value, gradient, order 2: Hessian upper triangle) at grid point idx of
+// launch_eval_grid; order = 1 or 2.  Shares the scratch and the tile counters of launch_eval_grid.
+template <typename T>
+hipError_t launch_eval_grid_derivs(const Grid &g, const int64_t *npts, const T *axes, int order, const T *coef, T *out, long long ldout,
+                                   hipStream_t st);
+long long eval_grid_derivs_scratch_bytes(long long ntab, int order);
+// outputs of a workgroup tile per dimension (1 beyond ndim); false: ndim outside 1 .. MAXD or order outside 1 .. 2
+bool eval_grid_derivs_tile(int ndim, int order, int out4[4]);
+
 // ---- synth.hip
 hipError_t launch_synth_points(int ndim, long long first, long long n, double *x, double *y,
                                double *w, hipStream_t st);

@@ -23,6 +23,8 @@
 !!    `evaluate_derivatives` value + gradient (+ Hessian) of a batch in one pass,
 !!    `refit` fits new values on the points of the last `initialize` with the factorisation that fit left on the GPU,
 !!    `evaluate_fields` evaluates several coefficient sets (what `refit` returns) at the same batch of points in one call,
+!!    `evaluate_grid` evaluates every point of a tensor-product grid of points from its axes alone,
+!!    `evaluate_grid_derivatives` value + gradient (+ Hessian) on such a grid, one plane per entry, in one pass,
 !!    `last_fit_info` returns the diagnostics of the last fit (the residual norm `reserr` that the
 !!    reference computes, suprls :1693, and drops, splcw :690; row counts; refinement steps).
 !!
@@ -72,6 +74,7 @@ module splpak_module
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
         procedure,public :: evaluate_grid => splpak_eval_grid       !! every point of a tensor-product grid of points (additive)
+        procedure,public :: evaluate_grid_derivatives => splpak_eval_grid_derivs !! value + gradient (+ Hessian) planes on such a grid (additive)
         procedure,public :: evaluate_fields => splpak_eval_fields   !! several coefficient sets at the same batch of points (additive)
         procedure,public :: refit         => splpak_refit           !! new values on the points of the last `initialize` (additive)
         procedure,public :: destroy       => destroy_splpak
@@ -87,6 +90,7 @@ module splpak_module
         procedure,private :: splde_many
         procedure,private :: splpak_derivs_many
         procedure,private :: splpak_eval_grid
+        procedure,private :: splpak_eval_grid_derivs
         procedure,private :: splpak_eval_fields
     end type splpak_type
 
@@ -140,6 +144,18 @@ module splpak_module
             integer(c_int32_t),value :: ndim
             type(c_ptr),value :: npts, axes, nderiv, coef, xmin, xmax, nodes, out
         end function c_eval_grid
+#ifdef REAL32
+        integer(c_int32_t) function c_eval_grid_derivs(ndim,npts,axes,order,coef,xmin,xmax,nodes,out,ldout) &
+                                                       bind(C,name='splpak_eval_grid_derivs_f32')
+#else
+        integer(c_int32_t) function c_eval_grid_derivs(ndim,npts,axes,order,coef,xmin,xmax,nodes,out,ldout) &
+                                                       bind(C,name='splpak_eval_grid_derivs_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr
+            integer(c_int32_t),value :: ndim, order
+            integer(c_int64_t),value :: ldout
+            type(c_ptr),value :: npts, axes, coef, xmin, xmax, nodes, out
+        end function c_eval_grid_derivs
 #ifdef REAL32
         integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
                                                   bind(C,name='splpak_eval_fields_f32')
@@ -873,6 +889,111 @@ module splpak_module
             if (ierror < 0) call report_library_failure(ierror,'evaluate_grid')
         end select
     end subroutine splpak_eval_grid
+
+    !> Value, gradient and (order = 2) Hessian of a fit on the grid of `evaluate_grid`, in planes: f(i,e) is entry e of
+    !! `evaluate_derivatives` -- the value, d/dx_1 .. d/dx_ndim, then for order 2 the upper triangle of the Hessian row by
+    !! row -- at grid point i = i1 + npts(1)*((i2-1) + npts(2)*((i3-1) + ...)), what `evaluate_grid` returns there under the
+    !! matching `nderiv`.  f is f(ldf,nplanes) with ldf >= product(npts); rows of f beyond product(npts) are not touched.
+    !! One call of the HIP library (splpak_eval_grid_derivs_f64); under set_host(.true.), in the -DREAL128 build, for
+    !! ndim > 4 or with SPLPAK_HOST_IF_NO_GPU=1 the loop of `evaluate_grid` on the host, once per pattern.
+    !! ierror: 101..103 as splde, -3 for a negative npts, an order outside 1..2 or an ldf too small.
+    subroutine splpak_eval_grid_derivs(me,ndim,npts,axes,order,coef,xmin,xmax,nodes,f,ldf,ierror)
+        class(splpak_type),intent(inout) :: me
+        integer,intent(in) :: ndim, order, ldf
+        integer,intent(in) :: npts(*)
+        real(wp),intent(in),target :: axes(*)
+        real(wp),intent(in),target :: coef(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(inout),target :: f(ldf,*)
+        integer,intent(out) :: ierror
+        integer(c_int32_t) :: rc
+        integer(c_int64_t),target :: np64(max(ndim,1))
+        integer(c_int64_t) :: iq, nq
+        integer :: idim, jdm, ie, col, nplanes, nder(max(ndim,1)), k(max(ndim,1)), off(max(ndim,1))
+        real(wp) :: x(max(ndim,1))
+        me%mdim = ndim
+        rc = 0
+        np64 = 0
+        do idim = 1, ndim
+            np64(idim) = int(npts(idim),c_int64_t)
+        end do
+#ifndef REAL128
+        if (.not. (host_takes(me,ndim) .and. ndim >= 1)) &
+            rc = c_eval_grid_derivs(int(ndim,c_int32_t), c_loc(np64), c_loc(axes), int(order,c_int32_t), c_loc(coef), &
+                                    c_loc(xmin), c_loc(xmax), c_loc(nodes), c_loc(f), int(ldf,c_int64_t))
+#endif
+        if ((host_takes(me,ndim) .or. host_if_no_gpu(int(rc))) .and. ndim >= 1) then   ! host solver: the scalar evaluation per pattern
+            ierror = 0
+            nq = 1
+            do idim = 1, ndim
+                if (npts(idim) < 0) then
+                    ierror = -3
+                    call report(ierror,' evaluate_grid_derivatives - NPTS(IDIM) is negative for some IDIM')
+                    return
+                end if
+                off(idim) = int(sum(np64(1:idim-1)))
+                nq = nq*np64(idim)
+            end do
+            if (order < 1 .or. order > 2 .or. int(ldf,c_int64_t) < nq) then
+                ierror = -3
+                call report(ierror,' evaluate_grid_derivatives - order must be 1 or 2 and ldf at least product(NPTS)')
+                return
+            end if
+            nplanes = 1 + ndim + merge(ndim*(ndim+1)/2, 0, order == 2)
+            idim = 0                                        ! the pattern of plane `col`, as evaluate_derivatives forms them
+            jdm = 0
+            do col = 1, nplanes
+                nder = 0
+                if (col > 1 .and. col <= 1 + ndim) then
+                    nder(col-1) = 1
+                else if (col > 1 + ndim) then
+                    if (col == 2 + ndim) then
+                        idim = 1
+                        jdm = 1
+                    else if (jdm == ndim) then
+                        idim = idim + 1
+                        jdm = idim
+                    else
+                        jdm = jdm + 1
+                    end if
+                    nder(idim) = nder(idim) + 1
+                    nder(jdm) = nder(jdm) + 1
+                end if
+                k = 1
+                do iq = 1, nq
+                    do ie = 1, ndim
+                        x(ie) = axes(off(ie) + k(ie))
+                    end do
+                    f(iq,col) = eval_point(me,ndim,x,nder,coef,xmin,xmax,nodes,ie)
+                    if (ie /= 0) then
+                        ierror = ie
+                        return
+                    end if
+                    ie = 1                                  ! odometer, first dimension fastest
+                    do while (ie <= ndim)
+                        k(ie) = k(ie) + 1
+                        if (k(ie) <= npts(ie)) exit
+                        k(ie) = 1
+                        ie = ie + 1
+                    end do
+                end do
+            end do
+            return
+        end if
+#ifdef REAL128
+        rc = -1
+#endif
+        ierror = int(rc)
+        select case (ierror)
+        case (0)
+        case (101); call report(ierror,' splfe or splde - NDIM is less than 1')
+        case (102); call report(ierror,' splfe or splde - NODES(IDIM) is less than  4for some IDIM')
+        case (103); call report(ierror,' splfe or splde - XMIN(IDIM) = XMAX(IDIM) for some IDIM')
+        case default
+            if (ierror < 0) call report_library_failure(ierror,'evaluate_grid_derivatives')
+        end select
+    end subroutine splpak_eval_grid_derivs
 
     !> Several coefficient sets at the same batch of points -- the evaluation half of `refit`: f(i,k) is the spline of
     !! coef(:,k) (with `nderiv`, that partial derivative) at x(:,i), the very value `evaluate_many` returns for that field.
