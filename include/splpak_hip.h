@@ -92,8 +92,10 @@ int32_t splpak_fit_f32(int32_t ndim, const float *xdata, int32_t l1xdat,
  * process draws a fresh one); 0 if there was none, or after a multi-GPU fit. */
 int64_t splpak_fit_token(void);
 /* Field k is the `ndata` values at ydata + k*ldy, in the point order of that fit (ldy >= ndata); its coefficients go to
- * coef + k*ldcoef (ldcoef >= ncol).  The fields are solved one after another with what the fit left on the device -- its
- * factorisation, or its iteration -- as splpak_plan_refit_dev describes; info (10 doubles per field, may be NULL) likewise.
+ * coef + k*ldcoef (ldcoef >= ncol).  The fields are solved with what the fit left on the device -- its factorisation, or its
+ * iteration -- as splpak_plan_refit_dev describes: on a held nested-dissection factor in chunks of up to 8 fields that share
+ * every sweep of the factor (every field the bits of its own single-field refit; a chunk with a failing field is run again
+ * field by field), otherwise one after another; info (10 doubles per field, may be NULL) likewise.
  * Returns 0; 107 as the fit would (that field's coefficients as the fit would return them, the later fields zeroed);
  * SPLPAK_E_BADARG for a null pointer, nfields < 1, ldy < ndata or ldcoef < ncol; SPLPAK_E_UNSUPPORTED, with the message "the
  * fit is no longer resident: fit again", when `token` is not that of the fit the library still holds or `ndata` is not its
@@ -209,9 +211,17 @@ int32_t splpak_plan_fit_dev(splpak_plan *plan, const double *xdata_dev, int32_t 
 /* New values on the points of the plan's last fit.  Only the solve depends on ydata: the binned points, the histogram, the
  * data-sparse flags, the constraint rows, N = A^T W^2 A + C^T C, its factor and the iteration's preconditioner are functions of
  * xdata, wdata and the grid, and a successful single-rank fit leaves them in the plan.  Field k is the `ndata` values (of that
- * fit) at ydata_dev + k*ldy, in that fit's point order; its ncol coefficients go to coef_dev + k*ldcoef.  The fields are
- * processed one after another: the values are gathered into the binned order, A^T W^2 y is one pass over the rows, and the
- * solve, the refinement against the rows, the diagnostics and the decisions that end in 107 are the fit's own.  The solver
+ * fit) at ydata_dev + k*ldy, in that fit's point order; its ncol coefficients go to coef_dev + k*ldcoef.  For every field
+ * the values are gathered into the binned order, A^T W^2 y is one pass over the rows, and the solve, the refinement against
+ * the rows, the diagnostics and the decisions that end in 107 are the fit's own.  Two or more fields on a held factor of the
+ * single-GPU nested dissection are solved in chunks of up to 8 fields that share every sweep of the factor (option
+ * refit_batch: fields per sweep, 1 .. 8, default 8; 1 = field by field): the first solve and every refinement step read the
+ * factor's panels once for all fields of the chunk that are still refining.  Every field's coefficients and its info [0..4],
+ * [8], [9] are bit for bit those of its single-field refit; [7] is the chunk's solve time divided by its fields.  If any
+ * field of a chunk does not end with status 0 the chunk's results are discarded and the chunk is run again field by field,
+ * which decides what a 107 returns.  The per-field copies this needs (8 x (2 vectors of the solve + partial sums), 8 x
+ * max_ndata values, 8 x 3 vectors) are allocated at the first such call and counted in splpak_plan_device_bytes; without the
+ * memory for them the plan refits field by field.  Every other call processes the fields one after another.  The solver
  * follows what the fit left: a held factor is used as it is (no expansion, no factorisation); a fit the iteration answered is
  * iterated again on the prepared preconditioner, and if that gives up and the plan has a factorisation the normal equations
  * are assembled from the binned points and factored as the fit does -- the later fields then use the factor.
@@ -225,9 +235,15 @@ int32_t splpak_plan_fit_dev(splpak_plan *plan, const double *xdata_dev, int32_t 
  * After a successful refit splpak_debug_plan_rows_gradient and splpak_debug_plan_normal_equations describe the LAST FIELD: N is
  * the fit's, rhs and the values of the rows are the field's; after a refit that returned 107 the former refuses, as after a
  * failed fit.  splpak_plan_stage_timing after a refit: [1] is the values gather + right-hand side, [0] and [2] are 0, [3] is 0
- * unless the factorisation ran, [4] [5] as for the fit. */
+ * unless the factorisation ran, [4] [5] as for the fit; after a batched refit [1] is the last field's gather + right-hand
+ * side, [5] the last chunk's first sweep, [4] a residual pass, [0] [2] [3] are 0. */
 int32_t splpak_plan_refit_dev(splpak_plan *plan, int32_t nfields, const double *ydata_dev, int64_t ldy,
                               double *coef_dev, int64_t ldcoef, void *stream, double *info);
+/* How the plan's last splpak_plan_refit_dev went (host counters; diagnostics): out4[0] its route -- 0 none yet, 1 field by
+ * field, 2 batched sweeps --, [1] the tree solves it launched (single and batched sweeps together; the solves of a band factor
+ * count too), [2] the right-hand sides those solves carried in total, [3] the fields run again field by field because their
+ * chunk did not end in 0.  SPLPAK_E_BADARG for a null argument. */
+int32_t splpak_debug_plan_refit_stats(const splpak_plan *plan, int64_t out4[4]);
 /* device pointer to the (all-reduced) sparse-area histogram of the last fit */
 const double *splpak_plan_hist_dev(const splpak_plan *plan);
 /* device memory the plan holds (bytes) */

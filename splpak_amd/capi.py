@@ -25,7 +25,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_voi
 # every symbol include/splpak_hip.h declares
 SYMBOLS = [
     "splpak_fit_f64", "splpak_fit_f32", "splpak_eval_f64", "splpak_eval_f32",
-    "splpak_fit_token", "splpak_refit_f64", "splpak_refit_f32", "splpak_plan_refit_dev",
+    "splpak_fit_token", "splpak_refit_f64", "splpak_refit_f32", "splpak_plan_refit_dev", "splpak_debug_plan_refit_stats",
     "splpak_plan_comm_len", "splpak_plan_create", "splpak_plan_destroy",
     "splpak_plan_set_allreduce", "splpak_plan_set_allreduce_ex", "splpak_plan_set_rccl", "splpak_rccl_unique_id", "splpak_rccl_comm_create",
     "splpak_rccl_comm_create_from_file", "splpak_rccl_comm_create_from_file_ex", "splpak_rccl_comm_destroy", "splpak_plan_set_refine", "splpak_plan_fit_dev",
@@ -89,6 +89,8 @@ def lib() -> C.CDLL:
     L.splpak_refit_f32.argtypes = [i64, i32, _fp, i64, i64, _fp, i64, _dp]
     L.splpak_plan_refit_dev.restype = i32
     L.splpak_plan_refit_dev.argtypes = [vp, i32, vp, i64, vp, i64, vp, _dp]
+    L.splpak_debug_plan_refit_stats.restype = i32
+    L.splpak_debug_plan_refit_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.splpak_eval_f64.restype = i32
     L.splpak_eval_f64.argtypes = [i32, i64, _dp, i32, _ip, _dp, _dp, _dp, _ip, _dp]
     L.splpak_eval_f32.restype = i32
@@ -723,6 +725,13 @@ class Plan:
         rc = self._L.splpak_plan_refit_dev(self._h, nfields, ydata.data_ptr(), ldy, coef.data_ptr(), ldc,
                                            C.c_void_p(stream), _p(info, _dp))
         return _check(rc), (info[0] if single else info)
+
+    def refit_stats(self):
+        """The last refit of this plan (splpak_debug_plan_refit_stats) -> [route (0 none yet, 1 field by field, 2 batched sweeps),
+        tree solves launched, right-hand sides they carried, fields run again field by field]."""
+        out = (C.c_int64 * 4)()
+        _check(self._L.splpak_debug_plan_refit_stats(self._h, out))
+        return [int(v) for v in out]
 
     def hist_ptr(self):
         return self._L.splpak_plan_hist_dev(self._h)

@@ -457,6 +457,9 @@ bwd_step_kernel(const double *__restrict__ Linvt0, const double *__restrict__ Nk
     }
 }
 
+// max that keeps a NaN (fmax drops it: a correction that is NaN all over used to read as |dx| = 0, "converged")
+__device__ __forceinline__ double max_or_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+
 __global__ void __launch_bounds__(256)
 axpy_absmax_kernel(int n, double *__restrict__ x, const double *__restrict__ dx,
                    unsigned long long *__restrict__ absmax2)
@@ -467,13 +470,13 @@ axpy_absmax_kernel(int n, double *__restrict__ x, const double *__restrict__ dx,
         const double d = dx[i];
         const double xv = x[i] + d;
         x[i] = xv;
-        mdx = fmax(mdx, fabs(d));
-        mx = fmax(mx, fabs(xv));
+        mdx = max_or_nan(mdx, fabs(d));
+        mx = max_or_nan(mx, fabs(xv));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        mdx = fmax(mdx, __shfl_xor(mdx, o, 64));
-        mx = fmax(mx, __shfl_xor(mx, o, 64));
+        mdx = max_or_nan(mdx, __shfl_xor(mdx, o, 64));
+        mx = max_or_nan(mx, __shfl_xor(mx, o, 64));
     }
     // one pair of atomics per workgroup (a pair per wave of 1 024 workgroups queued 8 192 atomics on two words: 96 us for a
     // 2 MB vector, twice per fit; round 3)
@@ -484,8 +487,8 @@ axpy_absmax_kernel(int n, double *__restrict__ x, const double *__restrict__ dx,
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        mdx = fmax(fmax(red[0][0], red[0][1]), fmax(red[0][2], red[0][3]));
-        mx = fmax(fmax(red[1][0], red[1][1]), fmax(red[1][2], red[1][3]));
+        mdx = max_or_nan(max_or_nan(red[0][0], red[0][1]), max_or_nan(red[0][2], red[0][3]));
+        mx = max_or_nan(max_or_nan(red[1][0], red[1][1]), max_or_nan(red[1][2], red[1][3]));
         // non-negative doubles order like their bit patterns; NaN (sign clear) sorts above inf
         atomicMax(&absmax2[0], (unsigned long long)__double_as_longlong(mdx));
         atomicMax(&absmax2[1], (unsigned long long)__double_as_longlong(mx));

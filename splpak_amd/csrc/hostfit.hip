@@ -157,30 +157,53 @@ static int32_t refit_host(int64_t token, int32_t nfields, const void *ydata, int
     if (ldcoef < ncol) { set_error("ldcoef < number of coefficients"); return SPLPAK_E_BADARG; }
     std::vector<double> wide;
     if (real32) wide.resize((size_t)(ndata > ncol ? ndata : ncol));
-    for (int k = 0; k < nfields; ++k) {
-        const double *src = nullptr;
-        if (real32) {
-            const float *yf = static_cast<const float *>(ydata) + (size_t)k * (size_t)ldy;
-            for (long long i = 0; i < ndata; ++i) wide[(size_t)i] = yf[i];
-            src = wide.data();
+    // Several fields are staged in groups of up to 8, so that the plan's refit can solve them in shared sweeps (splpak_plan_refit_dev);
+    // one field, or no memory for the group's staging, goes through the cache's own buffers one field at a time
+    struct Staging {
+        void *y = nullptr, *c = nullptr;
+        ~Staging() { if (y) (void)hipFree(y); if (c) (void)hipFree(c); }
+    } own;
+    int group = 1;
+    double *dy = hc.dy, *dc = hc.dc;
+    if (nfields >= 2) {
+        const int want = nfields < 8 ? nfields : 8;
+        if (hipMalloc(&own.y, sizeof(double) * (size_t)want * (size_t)ndata) == hipSuccess &&
+            hipMalloc(&own.c, sizeof(double) * (size_t)want * (size_t)ncol) == hipSuccess) {
+            group = want;
+            dy = static_cast<double *>(own.y);
+            dc = static_cast<double *>(own.c);
         } else
-            src = static_cast<const double *>(ydata) + (size_t)k * (size_t)ldy;
-        if (!hip_ok(hipMemcpy(hc.dy, src, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice), "hipMemcpy H2D")) { hc.release(); return SPLPAK_E_NODEVICE; }
-        int rc = splpak_plan_refit_dev(p, 1, hc.dy, ndata, hc.dc, ncol, nullptr, info ? info + 10 * (size_t)k : nullptr);
+            (void)hipGetLastError();
+    }
+    if (info) for (size_t i = 0; i < 10 * (size_t)nfields; ++i) info[i] = 0.0;      // (a field behind a 107 keeps these zeros)
+    for (int k0 = 0; k0 < nfields; k0 += group) {
+        const int n = nfields - k0 < group ? nfields - k0 : group;
+        for (int i = 0; i < n; ++i) {
+            const double *src = nullptr;
+            if (real32) {
+                const float *yf = static_cast<const float *>(ydata) + (size_t)(k0 + i) * (size_t)ldy;
+                for (long long q = 0; q < ndata; ++q) wide[(size_t)q] = yf[q];
+                src = wide.data();
+            } else
+                src = static_cast<const double *>(ydata) + (size_t)(k0 + i) * (size_t)ldy;
+            if (!hip_ok(hipMemcpy(dy + (size_t)i * (size_t)ndata, src, sizeof(double) * (size_t)ndata, hipMemcpyHostToDevice), "hipMemcpy H2D")) { hc.release(); return SPLPAK_E_NODEVICE; }
+        }
+        int rc = splpak_plan_refit_dev(p, n, dy, ndata, dc, ncol, nullptr, info ? info + 10 * (size_t)k0 : nullptr);
         // (a refusal -- the plan's state or an argument -- leaves the resident fit as it was; a device failure does not)
         if (rc == SPLPAK_E_UNSUPPORTED || rc == SPLPAK_E_BADARG) return rc;
         if (rc < 0) { hc.release(); return rc; }
-        double *dst = real32 ? wide.data() : static_cast<double *>(coef) + (size_t)k * (size_t)ldcoef;
-        if (!hip_ok(hipMemcpy(dst, hc.dc, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost), "hipMemcpy D2H")) { hc.release(); return SPLPAK_E_NODEVICE; }
-        if (real32) {
-            float *cf = static_cast<float *>(coef) + (size_t)k * (size_t)ldcoef;
-            for (long long i = 0; i < ncol; ++i) cf[i] = (float)wide[(size_t)i];
+        for (int i = 0; i < n; ++i) {
+            double *dst = real32 ? wide.data() : static_cast<double *>(coef) + (size_t)(k0 + i) * (size_t)ldcoef;
+            if (!hip_ok(hipMemcpy(dst, dc + (size_t)i * (size_t)ncol, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost), "hipMemcpy D2H")) { hc.release(); return SPLPAK_E_NODEVICE; }
+            if (real32) {
+                float *cf = static_cast<float *>(coef) + (size_t)(k0 + i) * (size_t)ldcoef;
+                for (long long q = 0; q < ncol; ++q) cf[q] = (float)wide[(size_t)q];
+            }
         }
-        if (rc != 0) {                 // 107: the later fields are zeroed, as splpak_plan_refit_dev leaves them
-            for (int j = k + 1; j < nfields; ++j) {
+        if (rc != 0) {                 // 107: the later fields are zeroed, as splpak_plan_refit_dev leaves them (those of this group it zeroed itself)
+            for (int j = k0 + n; j < nfields; ++j) {
                 if (real32) std::memset(static_cast<float *>(coef) + (size_t)j * (size_t)ldcoef, 0, sizeof(float) * (size_t)ncol);
                 else std::memset(static_cast<double *>(coef) + (size_t)j * (size_t)ldcoef, 0, sizeof(double) * (size_t)ncol);
-                if (info) for (int i = 0; i < 10; ++i) info[10 * (size_t)j + i] = 0.0;
             }
             return rc;
         }

@@ -435,5 +435,63 @@ hipError_t nd_solve(splpak_plan *p, double *x, double *tmp, hipStream_t st, void
     return hipGetLastError();
 }
 
+// The batch copies of V, Y and part for nd_solve_many, allocated at the first call (a batched refit): true when the plan's solver
+// is the single-GPU nested dissection and they exist.  An allocation that fails is not an error of the caller's: it is tried
+// once, the error is cleared, and the plan solves one right-hand side at a time from then on.
+bool nd_batch_ready(splpak_plan *p)
+{
+    NdState *s = p && p->fn_code == 4 && p->solve_fn == nd_solve ? static_cast<NdState *>(p->fn_user) : nullptr;
+    if (!s || s->dist || s->mdist) return false;
+    if (s->bV || s->batch_tried) return s->bV != nullptr;
+    s->batch_tried = true;
+    const size_t vec = (size_t)s->t.vec_doubles, bytes = sizeof(double) * (size_t)ND_BATCH_MAX * (2 * vec + (size_t)s->part_cap);
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    s->owned.push_back(q);
+    s->owned_bytes += bytes;
+    s->bV = static_cast<double *>(q);
+    s->bY = s->bV + (size_t)ND_BATCH_MAX * vec;
+    s->bpart = s->bY + (size_t)ND_BATCH_MAX * vec;
+    return true;
+}
+
+// x[r] <- N^-1 x[r] for R right-hand sides in ONE sweep of the tree: the depth loop of nd_solve with one launch where it has one,
+// every launch over the R copies of the vectors (slot r = x[r], whatever field that is).  Each x[r] receives the bits nd_solve
+// gives it.  R = 1 is nd_solve.  Single-GPU plans only, after nd_batch_ready.
+hipError_t nd_solve_many(splpak_plan *p, int R, double *const *x, hipStream_t st)
+{
+    NdState *s = static_cast<NdState *>(p->fn_user);
+    if (R == 1) return nd_solve(p, x[0], nullptr, st, s);
+    if (R < 2 || R > ND_BATCH_MAX || !s->bV || s->dist || s->mdist) return hipErrorInvalidValue;
+    NdTree &t = s->t;
+    SolveTables &T = s->sol;
+    const long long n = t.vec_doubles;
+    const BatchVec w{s->bV, s->bY, s->bpart, n, s->part_cap, s->V, s->Y, s->part};
+    BatchPtrs b{};
+    for (int r = 0; r < R; ++r) b.p[r] = x[r];
+    launch_gather_many(n, s->rowsrc, b, w, R, st);
+    // forward, bottom-up
+    for (int d = t.maxdepth; d >= 0; --d) {
+        if (d < t.maxdepth)
+            for (int sl = 0; sl < 2; ++sl) launch_map_many(T.map, T.map.l[(size_t)(d + 1)][(size_t)sl], false, w, R, st);
+        const int steps = (int)T.mv.l[(size_t)d].size();
+        for (int k = 0; k < steps; ++k) {
+            launch_mv_many(T.mv, T.mv.l[(size_t)d][(size_t)k], w, R, st);
+            launch_fwd_many(T.fwd, T.fwd.l[(size_t)d][(size_t)k], w, R, st);
+        }
+    }
+    // backward, top-down
+    for (int d = 0; d <= t.maxdepth; ++d) {
+        if (d >= 1) launch_map_many(T.map, T.map.l[(size_t)d][2], true, w, R, st);
+        const int steps = (int)T.mv.l[(size_t)d].size();
+        for (int k = steps - 1; k >= 0; --k) {
+            launch_dot_many(T.dot, T.dot.l[(size_t)d][(size_t)k], w, R, st);
+            launch_bwd_many(T.bwd, T.bwd.l[(size_t)d][(size_t)k], w, R, st);
+        }
+    }
+    launch_scatter_many(n, s->rowsrc, b, w, R, st);
+    return hipGetLastError();
+}
+
 }  // namespace nd
 }  // namespace splpak

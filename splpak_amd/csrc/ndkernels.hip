@@ -792,6 +792,249 @@ nd_bwd_kernel(const BwdJob *__restrict__ jobs)
     }
 }
 
+// ---- solves of R right-hand sides in one sweep (nd_solve_many) -----------------------------------------------
+// The kernels above with the vectors of slot r in copy r of V, Y and part (BatchVec): a thread loads its piece of L or of a
+// block inverse ONCE and multiplies it by the R vectors one after another, every vector in the order of operations of the single
+// kernel -- the bits of R single solves for one reading of the factor.
+__device__ __forceinline__ double *batch_at(double *base, long long stride, int r, const double *job, const double *base0)
+{
+    return base + (long long)r * stride + (job - base0);
+}
+
+__global__ void __launch_bounds__(256)
+nd_gather_many_kernel(long long n, const int *__restrict__ rowsrc, BatchPtrs b, BatchVec w)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int s = rowsrc[i];
+        (w.V + (long long)blockIdx.y * w.vstride)[i] = s >= 0 ? b.p[blockIdx.y][s] : 0.0;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+nd_scatter_many_kernel(long long n, const int *__restrict__ rowsrc, BatchVec w, BatchPtrs x)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int s = rowsrc[i];
+        if (s >= 0) x.p[blockIdx.y][s] = (w.V + (long long)blockIdx.y * w.vstride)[i];
+    }
+}
+
+// grid (8, jobs, R)
+template <bool TAKE>
+__global__ void __launch_bounds__(256)
+nd_map_many_kernel(const MapJob *__restrict__ jobs, BatchVec w)
+{
+    const MapJob j = jobs[blockIdx.y];
+    double *child = batch_at(w.V, w.vstride, blockIdx.z, j.child, w.V0);
+    double *par = batch_at(w.V, w.vstride, blockIdx.z, j.par, w.V0);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < j.h; i += gridDim.x * blockDim.x) {
+        const int r = j.pm[i];
+        if (TAKE) child[i] = par[r];
+        else par[r] += child[i];
+    }
+}
+
+template <int R>
+__global__ void __launch_bounds__(256)
+nd_mv_many_kernel(const MvJob *__restrict__ jobs, BatchVec w)
+{
+    const MvJob j = jobs[blockIdx.y];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 16 + wave * 4;
+    double m[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) m[i][u] = j.M[(r0 + i) * NBLK + lane + 64 * u];
+#pragma unroll
+    for (int f = 0; f < R; ++f) {
+        const double *__restrict__ v = batch_at(w.V, w.vstride, f, j.v, w.V0);
+        double *__restrict__ out = batch_at(w.Y, w.vstride, f, j.out, w.Y0);
+        double vv[4], s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vv[u] = v[lane + 64 * u];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s[i] = 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s[i] += m[i][u] * vv[u];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] = wave_sum(s[i]);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) out[r0 + i] = s[i];
+        }
+    }
+}
+
+// The R vectors y in LDS (R x 256 doubles); the column groups' partial sums of up to four right-hand sides at a time (4 x 16 x 64
+// doubles: 48 KiB with the vectors at R = 8, where one round over all eight would take 80), L in registers across the rounds.
+template <int R>
+__global__ void __launch_bounds__(512)
+nd_fwd_many_kernel(const FwdJob *__restrict__ jobs, int njobs, BatchVec w)
+{
+    constexpr int RC = R < 4 ? R : 4;
+    __shared__ double sy[R][NBLK];
+    __shared__ double part[RC][16][64];
+    const int b = blockIdx.x;
+    const int ji = find_job(jobs, njobs, b, [](const FwdJob &t) { return t.wg0; });
+    const FwdJob j = jobs[ji];
+    const int wg = b - j.wg0;
+    if (wg * 64 >= j.nrows) return;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = tid; i < R * NBLK; i += 512) sy[i >> 8][i & 255] = batch_at(w.Y, w.vstride, i >> 8, j.y, w.Y0)[i & 255];
+    const int rp = tid & 31, cg = tid >> 5;
+    const int r = wg * 64 + 2 * rp;
+    const double *__restrict__ Lr = j.L + r + (long long)(cg * 16) * j.ld;
+    d2_t l[16];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) l[c] = *reinterpret_cast<const d2_t *>(Lr + (long long)c * j.ld);
+    __syncthreads();
+#pragma unroll
+    for (int f0 = 0; f0 < R; f0 += RC) {
+        const int nf = R - f0 < RC ? R - f0 : RC;
+#pragma unroll
+        for (int ff = 0; ff < RC; ++ff) {
+            if (ff < nf) {
+                double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const double yv = sy[f0 + ff][cg * 16 + c];
+                    s0 += l[c][0] * yv;
+                    s1 += l[c][1] * yv;
+                }
+                part[ff][cg][2 * rp] = s0;
+                part[ff][cg][2 * rp + 1] = s1;
+            }
+        }
+        __syncthreads();
+        if (tid < 64 * nf) {
+            const int ff = tid >> 6, t = tid & 63;
+            double s = 0.0;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) s += part[ff][g][t];
+            batch_at(w.V, w.vstride, f0 + ff, j.v, w.V0)[wg * 64 + t] -= s;
+        }
+        if (f0 + RC < R) __syncthreads();
+    }
+}
+
+template <int R>
+__global__ void __launch_bounds__(256)
+nd_dot_many_kernel(const DotJob *__restrict__ jobs, int njobs, BatchVec w)
+{
+    const int b = blockIdx.x;
+    const int ji = find_job(jobs, njobs, b, [](const DotJob &t) { return t.wg0; });
+    const DotJob j = jobs[ji];
+    const int lw = b - j.wg0;
+    const int cg = lw & 15, split = lw >> 4;
+    if (split >= j.nsplit) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = cg * 16 + wave * 4;
+    const int rbeg = split * j.rps;
+    const int rend = rbeg + j.rps < j.nrows ? rbeg + j.rps : j.nrows;
+    double acc[R][4];
+#pragma unroll
+    for (int f = 0; f < R; ++f)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[f][c] = 0.0;
+    const double *__restrict__ Lc = j.L + lane + (long long)c0 * j.ld;
+    const double *__restrict__ x0 = batch_at(w.V, w.vstride, 0, j.x, w.V0);
+    int r = rbeg;
+    for (; r + 192 < rend; r += 256) {
+        double l[4][4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) l[t][c] = Lc[r + 64 * t + (long long)c * j.ld];
+#pragma unroll
+        for (int f = 0; f < R; ++f) {
+            double xr[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) xr[t] = x0[(long long)f * w.vstride + r + 64 * t + lane];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[f][c] += l[t][c] * xr[t];
+        }
+    }
+    for (; r < rend; r += 64) {
+        double l[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) l[c] = Lc[r + (long long)c * j.ld];
+#pragma unroll
+        for (int f = 0; f < R; ++f) {
+            const double xr = x0[(long long)f * w.vstride + r + lane];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[f][c] += l[c] * xr;
+        }
+    }
+#pragma unroll
+    for (int f = 0; f < R; ++f) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[f][c] = wave_sum(acc[f][c]);
+        if (lane == 0) {
+            double *__restrict__ pp = batch_at(w.part, w.pstride, f, j.part, w.part0);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) pp[(long long)split * NBLK + c0 + c] = acc[f][c];
+        }
+    }
+}
+
+template <int R>
+__global__ void __launch_bounds__(256)
+nd_bwd_many_kernel(const BwdJob *__restrict__ jobs, BatchVec w)
+{
+    const BwdJob j = jobs[blockIdx.y];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r0 = blockIdx.x * 16 + wave * 4;
+    double mt[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) mt[i][u] = j.Mt[(r0 + i) * NBLK + lane + 64 * u];
+#pragma unroll
+    for (int f = 0; f < R; ++f) {
+        const double *__restrict__ y = batch_at(w.Y, w.vstride, f, j.y, w.Y0);
+        const double *__restrict__ part = batch_at(w.part, w.pstride, f, j.part, w.part0);
+        double *__restrict__ x = batch_at(w.V, w.vstride, f, j.x, w.V0);
+        double vv[4], s[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) vv[u] = y[lane + 64 * u];
+        int sp = 0;
+        for (; sp + 1 < j.nsplit; sp += 2) {
+            double p0[4], p1[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                p0[u] = part[(long long)sp * NBLK + lane + 64 * u];
+                p1[u] = part[(long long)(sp + 1) * NBLK + lane + 64 * u];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) vv[u] = (vv[u] - p0[u]) - p1[u];
+        }
+        if (sp < j.nsplit) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) vv[u] -= part[(long long)sp * NBLK + lane + 64 * u];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s[i] = 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s[i] += mt[i][u] * vv[u];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] = wave_sum(s[i]);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[r0 + i] = s[i];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // launchers.  Diagonal blocks: a workgroup per job, 8 waves each (SPLPAK_ND_POTRF_WAVES = 4: the band path's form, 16)
 static void potrf_dispatch(int waves, const PotrfJob *jobs, unsigned n, hipStream_t st, int *info_dev, double *minpiv_dev)
@@ -928,6 +1171,56 @@ void launch_unflag(int *info, const double *flag, hipStream_t st) { hipLaunchKer
 void launch_whoami(unsigned wgs, unsigned *map, hipStream_t st) { hipLaunchKernelGGL(nd_whoami_kernel, dim3(wgs), dim3(64), 0, st, map); }
 void launch_gather(long long n, const int *rowsrc, const double *b, double *V, hipStream_t st) { hipLaunchKernelGGL(nd_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, rowsrc, b, V); }
 void launch_scatter(long long n, const int *rowsrc, const double *V, double *x, hipStream_t st) { hipLaunchKernelGGL(nd_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, rowsrc, V, x); }
+
+// the forms for R right-hand sides: the grids of the single launches (gather, scatter and map: a grid dimension over the slots)
+#define ND_MANY(R, GO)                                                                                                         \
+    switch (R) {                                                                                                               \
+    case 2: GO(2); break; case 3: GO(3); break; case 4: GO(4); break; case 5: GO(5); break;                                    \
+    case 6: GO(6); break; case 7: GO(7); break; case 8: GO(8); break;                                                          \
+    default: break;                                                                                                            \
+    }
+void launch_gather_many(long long n, const int *rowsrc, const BatchPtrs &b, const BatchVec &w, int R, hipStream_t st)
+{
+    hipLaunchKernelGGL(nd_gather_many_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)R), dim3(256), 0, st, n, rowsrc, b, w);
+}
+void launch_scatter_many(long long n, const int *rowsrc, const BatchPtrs &x, const BatchVec &w, int R, hipStream_t st)
+{
+    hipLaunchKernelGGL(nd_scatter_many_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)R), dim3(256), 0, st, n, rowsrc, w, x);
+}
+void launch_map_many(const JobTable<MapJob> &tab, const Launch &l, bool take, const BatchVec &w, int R, hipStream_t st)
+{
+    if (!l.grid) return;
+    hipLaunchKernelGGL(take ? nd_map_many_kernel<true> : nd_map_many_kernel<false>, dim3(8, l.grid, (unsigned)R), dim3(256), 0, st, (const MapJob *)(tab.dev + l.first), w);
+}
+void launch_mv_many(const JobTable<MvJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st)
+{
+    if (!l.grid) return;
+#define GO(N) hipLaunchKernelGGL(nd_mv_many_kernel<N>, dim3(16, l.grid), dim3(256), 0, st, (const MvJob *)(tab.dev + l.first), w)
+    ND_MANY(R, GO)
+#undef GO
+}
+void launch_bwd_many(const JobTable<BwdJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st)
+{
+    if (!l.grid) return;
+#define GO(N) hipLaunchKernelGGL(nd_bwd_many_kernel<N>, dim3(16, l.grid), dim3(256), 0, st, (const BwdJob *)(tab.dev + l.first), w)
+    ND_MANY(R, GO)
+#undef GO
+}
+void launch_fwd_many(const JobTable<FwdJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st)
+{
+    if (!l.count || !l.grid) return;
+#define GO(N) hipLaunchKernelGGL(nd_fwd_many_kernel<N>, dim3(l.grid), dim3(512), 0, st, (const FwdJob *)(tab.dev + l.first), l.count, w)
+    ND_MANY(R, GO)
+#undef GO
+}
+void launch_dot_many(const JobTable<DotJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st)
+{
+    if (!l.count || !l.grid) return;
+#define GO(N) hipLaunchKernelGGL(nd_dot_many_kernel<N>, dim3(l.grid), dim3(256), 0, st, (const DotJob *)(tab.dev + l.first), l.count, w)
+    ND_MANY(R, GO)
+#undef GO
+}
+#undef ND_MANY
 
 }  // namespace nd
 

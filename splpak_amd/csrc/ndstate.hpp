@@ -58,6 +58,12 @@ struct TopColDev { long long off, ld; };          // block column of a top front
 // block column from wherever the child's columns live (another GPU's memory, read through the peer mapping)
 struct PullJob { const double *src; long long lds; const int *pm; double *dst; long long ldd; int c0, c1, h, row0, tile0, ntr, ntc, pad; };
 
+// Solves of several right-hand sides in one sweep (nd_solve_many): right-hand side r keeps its vectors in copy r of V, Y and part
+// -- vstride / pstride doubles apart --, and the kernels address the operand a job names in s->V (V0), s->Y (Y0) or s->part
+// (part0) at the same offset in that copy.  The job tables are those of the single solves.
+struct BatchVec { double *V; double *Y; double *part; long long vstride, pstride; const double *V0; const double *Y0; const double *part0; };
+struct BatchPtrs { double *p[ND_BATCH_MAX]; };      // where slot r's right-hand side is read from and its solution written to
+
 constexpr int DOT_RPS = 1024;          // rows per split of the backward sweep's column dots
 // ints per item queue: [0] item counter, [1] waves that stepped aside, [2 .. 9] item counters of the eight XCD slices (xmode)
 constexpr int ND_QSTRIDE = 16;
@@ -242,6 +248,9 @@ struct NdState {
     long long sarena_doubles = 0;
     double *V = nullptr, *Y = nullptr, *part = nullptr;
     long long part_cap = 0;                        // doubles of the backward sweep's partial sums (one launch at a time)
+    // ND_BATCH_MAX copies each of V, Y and part for nd_solve_many, allocated at the first batched refit (nd_batch_ready)
+    double *bV = nullptr, *bY = nullptr, *bpart = nullptr;
+    bool batch_tried = false;
     int *pos = nullptr, *front_of = nullptr, *bpos = nullptr, *pmap = nullptr, *rowsrc = nullptr;
     int *ipos = nullptr;                           // node at an elimination position (-1: none)
     std::vector<int> rowsrc_host;                  // [vec_doubles] variable of every front row (-1: border / padding)
@@ -352,6 +361,14 @@ void launch_mv(const JobTable<MvJob> &tab, const Launch &l, hipStream_t st);
 void launch_fwd(const JobTable<FwdJob> &tab, const Launch &l, hipStream_t st);
 void launch_dot(const JobTable<DotJob> &tab, const Launch &l, hipStream_t st);
 void launch_bwd(const JobTable<BwdJob> &tab, const Launch &l, hipStream_t st);
+// ... the same launches over R = 2 .. ND_BATCH_MAX right-hand sides (the vectors of slot r: copy r of w)
+void launch_gather_many(long long n, const int *rowsrc, const BatchPtrs &b, const BatchVec &w, int R, hipStream_t st);
+void launch_scatter_many(long long n, const int *rowsrc, const BatchPtrs &x, const BatchVec &w, int R, hipStream_t st);
+void launch_map_many(const JobTable<MapJob> &tab, const Launch &l, bool take, const BatchVec &w, int R, hipStream_t st);
+void launch_mv_many(const JobTable<MvJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st);
+void launch_fwd_many(const JobTable<FwdJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st);
+void launch_dot_many(const JobTable<DotJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st);
+void launch_bwd_many(const JobTable<BwdJob> &tab, const Launch &l, const BatchVec &w, int R, hipStream_t st);
 
 }  // namespace nd
 }  // namespace splpak

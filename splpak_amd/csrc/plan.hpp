@@ -121,6 +121,13 @@ struct splpak_plan {
     bool factor_valid = false;    // the factor storage holds the factor of these points' N (cleared by whatever rewrites the storage)
     long long fit_ndata = 0;      // of that fit: its points, row counts, sum of w^2 and the factor's smallest pivot
     double fit_rows_data = 0, fit_rows_cons = 0, fit_sumw2 = 0, fit_minpiv = 0;
+    // a refit of several fields in lock-step (planfit.hip): per-field copies of ys, xvec, rhs and rho and of the correction's
+    // (absmax, max) pair, allocated at the first batched refit; the counters splpak_debug_plan_refit_stats reports
+    struct RefitBatch {
+        double *ys = nullptr, *x = nullptr, *rhs = nullptr, *rho = nullptr, *small = nullptr;
+        bool tried = false;
+        long long stats[4] = {0, 0, 0, 0};
+    } rb;
     const char *fn_name = nullptr;                 // what the hooks are (splpak_plan_factorisation); fn_code: 2 two-ended band, 4 nested dissection, 3 distributed band
     int fn_code = 0;
 };
@@ -157,6 +164,12 @@ void nd_group_reset(NdGroup *g);
 bool nd_wanted_for(int ndim, const int *nodes, const double *xmin, const double *xmax);
 // the sharded fit's ranks are known: distribute the nested-dissection factorisation by subtrees (SPLPAK_ND_DIST=1; ndattach.hip)
 int nd_set_ranks(splpak_plan *p, int rank, int world);
+// ndchol.hip: several right-hand sides in one sweep of a single-GPU nested-dissection factor (described where they are defined)
+namespace nd {
+constexpr int ND_BATCH_MAX = 8;        // right-hand sides per sweep
+bool nd_batch_ready(splpak_plan *p);
+hipError_t nd_solve_many(splpak_plan *p, int R, double *const *x, hipStream_t st);
+}
 // sum over the ranks of the sharded fit through the caller's hook (planfit.hip); 0 = fine (also with one rank)
 int plan_allreduce(splpak_plan *p, double *buf, long long count, hipStream_t st);
 // planfit.hip: the pieces of a fit that the debug-plan entries (plandebug.hip) run alone; described where they are defined

@@ -19,9 +19,12 @@
 #include "plan.hpp"
 
 #include <cmath>
+#include <cstdlib>
 #include <limits>
 
 using namespace splpak;
+
+constexpr int REFIT_BATCH_MAX = nd::ND_BATCH_MAX;        // fields per sweep of a batched refit: the right-hand sides nd_solve_many carries
 
 // SPLPAK_DEBUG_SUMS: sum and absolute sum of a device buffer, printed with a label (diagnosing the sharded fit)
 static void debug_sum(const splpak_plan *p, const char *what, const double *buf, long long count, hipStream_t st)
@@ -188,6 +191,39 @@ struct Refinement {
     double est_err() const { return steps >= 2 && ratio > 0.0 && ratio < 1.0 ? last_rel * ratio / (1.0 - ratio) : last_rel; }
 };
 
+// One step of the refinement's stopping rules, for the step `it` whose correction measured am = (max |dx|, max |x|): counts it,
+// and decides.  true: the solve ends here (rf says how); false: it goes on, prev_rel carried to the next step.  Shared by the
+// solve of one field (solve_and_refine) and the lock-step solve of several (refit_chunk_batched): the same rules, field by field.
+static bool refinement_advance(const splpak_plan *p, Refinement &rf, double &prev_rel, int it, const double am[2])
+{
+    ++rf.steps;
+    rf.last_rel = (am[1] > 0.0) ? am[0] / am[1] : 0.0;
+    if (am[0] != am[0] || am[1] != am[1]) rf.last_rel = std::numeric_limits<double>::quiet_NaN();      // (NaN > 0 is false: not "no correction")
+    if (splpak::opt_get("SPLPAK_DEBUG"))
+        fprintf(stderr, "[splpak] refinement step %d: |dx|/|x| = %.3e\n", rf.steps, rf.last_rel);
+    if (!(rf.last_rel == rf.last_rel)) return true;             // NaN
+    if (rf.last_rel <= p->tol) { rf.converged = true; return true; }
+    if (it >= 1) {
+        // linear convergence: after this step the error is ~ dx * ratio / (1 - ratio); stop as soon
+        // as that estimate is below the tolerance instead of paying for one more solve
+        rf.ratio = rf.last_rel / prev_rel;
+        if (rf.ratio < 0.9 && rf.last_rel * rf.ratio / (1.0 - rf.ratio) <= p->tol) { rf.converged = true; return true; }
+        if (rf.ratio >= 0.9) {                                // stagnation: fine at the rounding floor, a failure if the
+            rf.diverged = rf.last_rel > 1e-8;                 // corrections are still large; in between (1e-10 .. 1e-8) the
+            rf.converged = !rf.diverged;                      // MEASURED backward error decides below (round-2 advice: the
+            rf.stagnated = rf.converged && rf.last_rel > 1e-10;   // estimate alone let coefficients that miss the bar through)
+            return true;
+        }
+        // 0.5 .. 0.9: an ill-conditioned grid whose corrections still shrink -- go on (up to max_refine_hard):
+        // stopping here left 1-D grids of 2 000-3 000 nodes 1e-7 .. 1e-10 away from the converged solution
+        // (randomized sweep, tools/fuzz_parity.py big)
+    }
+    prev_rel = rf.last_rel;
+    if (it + 1 >= p->max_refine && it + 1 < p->max_refine_hard && splpak::opt_get("SPLPAK_DEBUG"))
+        fprintf(stderr, "[splpak] still contracting after %d steps: continuing\n", it + 1);
+    return false;
+}
+
 // Solve + refinement against the rows, around any solver of N z = v, from the right-hand side in p->rhs to the coefficients in
 // p->xvec.  solve(v, first): v <- N^-1 v; 0, a status to return (negative, SPLPAK_E_COMM), or 1 = this solver gives up (the iteration)
 template <typename Solve>
@@ -214,30 +250,7 @@ static int solve_and_refine(splpak_plan *p, hipStream_t st, Refinement &rf, Solv
         double am[2];
         SPLPAK_HIP_TRY(hipMemcpyAsync(am, p->small, 2 * sizeof(double), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
         SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
-        ++rf.steps;
-        rf.last_rel = (am[1] > 0.0) ? am[0] / am[1] : 0.0;
-        if (splpak::opt_get("SPLPAK_DEBUG"))
-            fprintf(stderr, "[splpak] refinement step %d: |dx|/|x| = %.3e\n", rf.steps, rf.last_rel);
-        if (!(rf.last_rel == rf.last_rel)) break;             // NaN
-        if (rf.last_rel <= p->tol) { rf.converged = true; break; }
-        if (it >= 1) {
-            // linear convergence: after this step the error is ~ dx * ratio / (1 - ratio); stop as soon
-            // as that estimate is below the tolerance instead of paying for one more solve
-            rf.ratio = rf.last_rel / prev_rel;
-            if (rf.ratio < 0.9 && rf.last_rel * rf.ratio / (1.0 - rf.ratio) <= p->tol) { rf.converged = true; break; }
-            if (rf.ratio >= 0.9) {                                // stagnation: fine at the rounding floor, a failure if the
-                rf.diverged = rf.last_rel > 1e-8;                 // corrections are still large; in between (1e-10 .. 1e-8) the
-                rf.converged = !rf.diverged;                      // MEASURED backward error decides below (round-2 advice: the
-                rf.stagnated = rf.converged && rf.last_rel > 1e-10;   // estimate alone let coefficients that miss the bar through)
-                break;
-            }
-            // 0.5 .. 0.9: an ill-conditioned grid whose corrections still shrink -- go on (up to max_refine_hard):
-            // stopping here left 1-D grids of 2 000-3 000 nodes 1e-7 .. 1e-10 away from the converged solution
-            // (randomized sweep, tools/fuzz_parity.py big)
-        }
-        prev_rel = rf.last_rel;
-        if (it + 1 >= p->max_refine && it + 1 < p->max_refine_hard && splpak::opt_get("SPLPAK_DEBUG"))
-            fprintf(stderr, "[splpak] still contracting after %d steps: continuing\n", it + 1);
+        if (refinement_advance(p, rf, prev_rel, it, am)) break;
     }
     return 0;
 }
@@ -363,7 +376,10 @@ static int plan_solve_stage(splpak_plan *p, hipStream_t st, double *coef_dev, do
         if (hinfo != 0) return fit_fails_107(g, coef_dev, st, "normal equations not positive definite (suprls 34)");
     }
     if (!solved)
-        if (int r = solve_and_refine(p, st, rf, [=](double *v, bool) -> int { return plan_factor_solve(p, v, st); })) return r;
+        if (int r = solve_and_refine(p, st, rf, [=](double *v, bool) -> int {
+                if (a.refit) { ++p->rb.stats[1]; ++p->rb.stats[2]; }       // (splpak_debug_plan_refit_stats)
+                return plan_factor_solve(p, v, st);
+            })) return r;
     const double est_err = rf.est_err();
     const bool unconverged = !rf.converged && !rf.diverged && rf.last_rel == rf.last_rel && est_err > 1e-10;
     SPLPAK_HIP_TRY(launch_to_reference_order(g, p->xvec, coef_dev, st), SPLPAK_E_NODEVICE);   // internal -> caller's dimension order
@@ -421,6 +437,227 @@ static int plan_solve_stage(splpak_plan *p, hipStream_t st, double *coef_dev, do
     }
     p->fit_valid = p->world <= 1 && !p->ar && p->dm.R == 1;
     p->fit_rows = rows_fit;
+    return 0;
+}
+
+// The arguments of one splpak_plan_refit_dev
+struct RefitCall {
+    int nfields;
+    const double *ydata_dev;
+    long long ldy;
+    double *coef_dev;
+    long long ldcoef;
+    double *info;
+    const double *y(int k) const { return ydata_dev + (size_t)k * (size_t)ldy; }
+    double *coef(int k) const { return coef_dev + (size_t)k * (size_t)ldcoef; }
+    double *inf(int k) const { return info ? info + 10 * (size_t)k : nullptr; }
+};
+
+// The fields [k0, k1) of a refit one after another, each through the solve stage of a fit.  0, or the status the call returns:
+// negative at once; 107 with the failing field's coefficients, every later field of the CALL zeroed and the plan still refit-able
+static int refit_field_by_field(splpak_plan *p, const RefitCall &c, int k0, int k1, hipStream_t st)
+{
+    const Grid &g = p->g;
+    const long long ndata = p->fit_ndata;
+    for (int k = k0; k < k1; ++k) {
+        double *inf = c.inf(k);
+        if (inf) for (int i = 0; i < 10; ++i) inf[i] = 0.0;
+        // the values and the right-hand side are being replaced: until the field is through, the plan describes no fit
+        p->fit_valid = false;
+        p->geom_valid = false;
+        SolveStart a;
+        a.rows_cons = p->fit_rows_cons;
+        a.sumw2 = p->fit_sumw2;
+        a.rows_fit = p->fit_rows;
+        a.refit = true;
+        a.t1 = std::chrono::steady_clock::now();
+        stamp(p, 1, st);
+        SPLPAK_HIP_TRY(launch_regather_values(g, p->s, ndata, c.y(k), p->s.ys, st), SPLPAK_E_NODEVICE);
+        // A^T W^2 y: the refinement's pass over the rows at x = 0, without the constraint rows
+        SPLPAK_HIP_TRY(hipMemsetAsync(p->xvec, 0, sizeof(double) * (size_t)p->band.npad, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemsetAsync(p->rhs, 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(plan_rows_residual(p, p->s, p->xvec, false, p->rhs, st), SPLPAK_E_NODEVICE);
+        stamp(p, 2, st);
+        if (inf) { inf[0] = p->fit_rows_data; inf[1] = p->fit_rows_cons; }
+        const int rc = plan_solve_stage(p, st, c.coef(k), inf, a);
+        if (rc < 0) return rc;
+        p->geom_valid = true;                  // (107 too: the points, N and the factor or preconditioner are those of the fit still)
+        if (rc != 0) {
+            for (int j = k + 1; j < c.nfields; ++j)
+                SPLPAK_HIP_TRY(hipMemsetAsync(c.coef(j), 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
+            SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+            return rc;
+        }
+    }
+    return 0;
+}
+
+// Option refit_batch: fields per sweep of a batched refit, 1 .. 8 (clamped; default, and text that is no number: 8; 1: field by field)
+static int refit_batch_option()
+{
+    const char *e = splpak::opt_get("SPLPAK_REFIT_BATCH");
+    if (!e) return REFIT_BATCH_MAX;
+    char *end = nullptr;
+    const long v = std::strtol(e, &end, 10);
+    while (end && (*end == ' ' || *end == '\t')) ++end;
+    if (end == e || (end && *end)) return REFIT_BATCH_MAX;
+    return v < 1 ? 1 : (v > REFIT_BATCH_MAX ? REFIT_BATCH_MAX : (int)v);
+}
+
+// doubles between the per-field copies of ys, and of the vectors (multiples of 32: every copy as aligned as the plan's own)
+static size_t refit_ystride(const splpak_plan *p) { return ((size_t)p->s.cap + 31) / 32 * 32; }
+static size_t refit_vstride(const splpak_plan *p) { return ((size_t)p->band.npad + SC_COUNT + 31) / 32 * 32; }
+
+// The per-field copies a batched refit works in: REFIT_BATCH_MAX x (ys | xvec | rhs | rho) and the pairs of the corrections,
+// allocated at the first batched refit and counted in splpak_plan_device_bytes.  No memory for them is no error: it is asked
+// for once, and the plan refits field by field from then on.
+static bool refit_buffers_ready(splpak_plan *p)
+{
+    splpak_plan::RefitBatch &rb = p->rb;
+    if (rb.ys || rb.tried) return rb.ys != nullptr;
+    rb.tried = true;
+    const size_t sy = refit_ystride(p), sv = refit_vstride(p);
+    const size_t bytes = sizeof(double) * ((size_t)REFIT_BATCH_MAX * (sy + 3 * sv) + 32);
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    p->owned.push_back(q);
+    p->owned_bytes += bytes;
+    rb.ys = static_cast<double *>(q);
+    rb.x = rb.ys + (size_t)REFIT_BATCH_MAX * sy;
+    rb.rhs = rb.x + (size_t)REFIT_BATCH_MAX * sv;
+    rb.rho = rb.rhs + (size_t)REFIT_BATCH_MAX * sv;
+    rb.small = rb.rho + (size_t)REFIT_BATCH_MAX * sv;
+    return true;
+}
+
+// The fields [k0, k0 + n) of a refit, 2 <= n <= REFIT_BATCH_MAX, in lock-step on the held nested-dissection factor: every field has
+// its own values, right-hand side, coefficients and residual; the row passes run field after field as the single refit launches
+// them, and every solve is ONE sweep of the factor over the fields that are still refining (nd_solve_many).  A field leaves the
+// sweeps when the rules of solve_and_refine end its solve, so every field gets the operations -- and the bits -- of its own
+// single-field refit, info[0..4], [8], [9] included; info[7] is the chunk's share per field, [5] and [6] are 0.
+// *redo: a field did not end in status 0 -- nothing of the chunk is reported, the caller runs it field by field.
+// Returns 0 or a negative status.  After a chunk without redo the plan describes its last field.
+static int refit_chunk_batched(splpak_plan *p, const RefitCall &c, int k0, int n, hipStream_t st, bool *redo)
+{
+    using clk = std::chrono::steady_clock;
+    const Grid &g = p->g;
+    const Band &b = p->band;
+    const bool smooth = p->xtrap != 0.0;
+    const bool stamps = p->stats.enabled;
+    const long long ndata = p->fit_ndata;
+    const size_t sy = refit_ystride(p), sv = refit_vstride(p), vbytes = sizeof(double) * (size_t)b.npad, cbytes = sizeof(double) * (size_t)g.ncol;
+    splpak_plan::RefitBatch &rb = p->rb;
+    struct KeepYs {                         // the diagnostics pass reads the values through p->s
+        splpak_plan *p;
+        double *ys;
+        ~KeepYs() { p->s.ys = ys; }
+    } keep{p, p->s.ys};
+    SortScratch rows[REFIT_BATCH_MAX];
+    double *x[REFIT_BATCH_MAX], *rhs[REFIT_BATCH_MAX], *rho[REFIT_BATCH_MAX];
+    for (int i = 0; i < n; ++i) {
+        rows[i] = p->s;
+        rows[i].ys = rb.ys + (size_t)i * sy;
+        x[i] = rb.x + (size_t)i * sv;
+        rhs[i] = rb.rhs + (size_t)i * sv;
+        rho[i] = rb.rho + (size_t)i * sv;
+    }
+    *redo = false;
+    p->fit_valid = false;
+    p->geom_valid = false;
+    // ---- the values and A^T W^2 y of every field (the refinement's pass at x = 0, without the constraint rows)
+    for (int i = 0; i < n; ++i) {
+        if (i == n - 1) stamp(p, 1, st);
+        SPLPAK_HIP_TRY(launch_regather_values(g, p->s, ndata, c.y(k0 + i), rows[i].ys, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemsetAsync(x[i], 0, vbytes, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemsetAsync(rhs[i], 0, cbytes, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(plan_rows_residual(p, rows[i], x[i], false, rhs[i], st), SPLPAK_E_NODEVICE);
+        if (i == n - 1) stamp(p, 2, st);
+    }
+    const auto t2 = clk::now();
+    // ---- the first solve: one sweep for all
+    for (int i = 0; i < n; ++i) SPLPAK_HIP_TRY(hipMemcpyAsync(x[i], rhs[i], cbytes, hipMemcpyDeviceToDevice, st), SPLPAK_E_NODEVICE);
+    stamp(p, 6, st);
+    SPLPAK_HIP_TRY(nd::nd_solve_many(p, n, x, st), SPLPAK_E_NODEVICE);
+    stamp(p, 7, st);
+    rb.stats[1] += 1;
+    rb.stats[2] += n;
+    // ---- refinement in lock-step: the fields still refining share the sweep of every step
+    Refinement rf[REFIT_BATCH_MAX];
+    double prev_rel[REFIT_BATCH_MAX];
+    bool active[REFIT_BATCH_MAX];
+    for (int i = 0; i < n; ++i) {
+        rf[i] = Refinement();
+        rf[i].converged = p->max_refine == 0;
+        prev_rel[i] = std::numeric_limits<double>::infinity();
+        active[i] = !rf[i].converged;
+    }
+    for (int it = 0; it < p->max_refine_hard; ++it) {
+        int act[REFIT_BATCH_MAX], na = 0;
+        for (int i = 0; i < n; ++i)
+            if (active[i]) act[na++] = i;
+        if (na == 0) break;
+        double *v[REFIT_BATCH_MAX];
+        for (int a = 0; a < na; ++a) {
+            const int i = act[a];
+            SPLPAK_HIP_TRY(hipMemsetAsync(rho[i], 0, sizeof(double) * (size_t)(b.npad + SC_COUNT), st), SPLPAK_E_NODEVICE);
+            SPLPAK_HIP_TRY(plan_rows_residual(p, rows[i], x[i], smooth && p->rank == 0, rho[i], st), SPLPAK_E_NODEVICE);
+            v[a] = rho[i];
+        }
+        SPLPAK_HIP_TRY(nd::nd_solve_many(p, na, v, st), SPLPAK_E_NODEVICE);
+        rb.stats[1] += 1;
+        rb.stats[2] += na;
+        for (int a = 0; a < na; ++a)
+            SPLPAK_HIP_TRY(launch_axpy_absmax(g.ncol, x[act[a]], rho[act[a]], rb.small + 2 * a, st), SPLPAK_E_NODEVICE);
+        double am[2 * REFIT_BATCH_MAX];
+        SPLPAK_HIP_TRY(hipMemcpyAsync(am, rb.small, 2 * sizeof(double) * (size_t)na, hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+        for (int a = 0; a < na; ++a)
+            if (refinement_advance(p, rf[act[a]], prev_rel[act[a]], it, am + 2 * a)) active[act[a]] = false;
+    }
+    // ---- coefficients out; the diagnostics pass of every field, with the plan's own vectors holding that field (the last
+    // field's stay: the plan describes it)
+    double ssq[REFIT_BATCH_MAX], omega[REFIT_BATCH_MAX];
+    hipEvent_t r0 = stamps ? p->evStage[8] : nullptr, r1 = stamps ? p->evStage[9] : nullptr;
+    for (int i = 0; i < n; ++i) {
+        const bool last = i == n - 1;
+        ssq[i] = omega[i] = 0.0;
+        SPLPAK_HIP_TRY(launch_to_reference_order(g, x[i], c.coef(k0 + i), st), SPLPAK_E_NODEVICE);
+        const bool diag = c.info || rf[i].stagnated;
+        if (!diag && !last) continue;
+        SPLPAK_HIP_TRY(hipMemcpyAsync(p->xvec, x[i], vbytes, hipMemcpyDeviceToDevice, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemcpyAsync(p->rhs, rhs[i], cbytes, hipMemcpyDeviceToDevice, st), SPLPAK_E_NODEVICE);
+        if (last) SPLPAK_HIP_TRY(hipMemcpyAsync(keep.ys, rows[i].ys, sizeof(double) * (size_t)ndata, hipMemcpyDeviceToDevice, st), SPLPAK_E_NODEVICE);
+        if (!diag) continue;
+        p->s.ys = rows[i].ys;
+        const bool timed = last && r0 && r1;
+        if (int r = plan_diagnostics_pass(p, p->fit_rows, st, timed ? r0 : nullptr)) return r;
+        if (timed) (void)hipEventRecord(r1, st);
+        SPLPAK_HIP_TRY(launch_backward_error(g, p->tmp, p->rho, p->small + 3, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemcpyAsync(&ssq[i], p->rho + b.npad, sizeof(double), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemcpyAsync(&omega[i], p->small + 3, sizeof(double), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+    }
+    SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+    const double share_s = std::chrono::duration<double>(clk::now() - t2).count() / (double)n;
+    // ---- verdicts: those of the solve stage.  Any field that would not return 0 sends the chunk to the field-by-field loop
+    for (int i = 0; i < n; ++i) {
+        const Refinement &r = rf[i];
+        const bool unconverged = !r.converged && !r.diverged && r.last_rel == r.last_rel && r.est_err() > 1e-10;
+        if (!(r.last_rel == r.last_rel) || r.diverged || (r.stagnated && !(omega[i] <= 1e-10)) || unconverged) *redo = true;
+    }
+    if (*redo) return 0;
+    if (stamps) {
+        plan_stage_times(p, true, false);
+        float ms = 0.f;
+        if (c.info && hipEventElapsedTime(&ms, r0, r1) == hipSuccess) p->stage_ms[4] = ms;
+        else (void)hipGetLastError();
+    }
+    for (int i = 0; i < n && c.info; ++i) {
+        double *inf = c.inf(k0 + i);
+        const double v[10] = {p->fit_rows_data, p->fit_rows_cons, (double)rf[i].steps, rf[i].last_rel, p->fit_minpiv, 0.0, 0.0, share_s, std::sqrt(ssq[i]), omega[i]};
+        for (int q = 0; q < 10; ++q) inf[q] = v[q];
+    }
+    p->fit_valid = true;                   // (single rank, no hook: splpak_plan_refit_dev refused the others)
+    p->geom_valid = true;
     return 0;
 }
 
@@ -565,37 +802,31 @@ int32_t splpak_plan_refit_dev(splpak_plan *p, int32_t nfields, const double *yda
     hipStream_t st = (hipStream_t)stream;
     p->comm_failed = false;
     if (int r = plan_stage_events(p)) return r;
-    for (int k = 0; k < nfields; ++k) {
-        double *inf = info ? info + 10 * (size_t)k : nullptr;
-        double *coef_k = coef_dev + (size_t)k * (size_t)ldcoef;
-        if (inf) for (int i = 0; i < 10; ++i) inf[i] = 0.0;
-        // the values and the right-hand side are being replaced: until the field is through, the plan describes no fit
-        p->fit_valid = false;
-        p->geom_valid = false;
-        SolveStart a;
-        a.rows_cons = p->fit_rows_cons;
-        a.sumw2 = p->fit_sumw2;
-        a.rows_fit = p->fit_rows;
-        a.refit = true;
-        a.t1 = std::chrono::steady_clock::now();
-        stamp(p, 1, st);
-        SPLPAK_HIP_TRY(launch_regather_values(g, p->s, ndata, ydata_dev + (size_t)k * (size_t)ldy, p->s.ys, st), SPLPAK_E_NODEVICE);
-        // A^T W^2 y: the refinement's pass over the rows at x = 0, without the constraint rows
-        SPLPAK_HIP_TRY(hipMemsetAsync(p->xvec, 0, sizeof(double) * (size_t)p->band.npad, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(hipMemsetAsync(p->rhs, 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(plan_rows_residual(p, p->s, p->xvec, false, p->rhs, st), SPLPAK_E_NODEVICE);
-        stamp(p, 2, st);
-        if (inf) { inf[0] = p->fit_rows_data; inf[1] = p->fit_rows_cons; }
-        const int rc = plan_solve_stage(p, st, coef_k, inf, a);
-        if (rc < 0) return rc;
-        p->geom_valid = true;                  // (107 too: the points, N and the factor or preconditioner are those of the fit still)
-        if (rc != 0) {
-            for (int j = k + 1; j < nfields; ++j)
-                SPLPAK_HIP_TRY(hipMemsetAsync(coef_dev + (size_t)j * (size_t)ldcoef, 0, sizeof(double) * (size_t)g.ncol, st), SPLPAK_E_NODEVICE);
-            SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
-            return rc;
+    const RefitCall c{nfields, ydata_dev, ldy, coef_dev, ldcoef, info};
+    // Fields that can share the sweeps of a held nested-dissection factor go in chunks of up to `refit_batch`; everything else --
+    // one field, the band factorisations, the iteration, refit_batch = 1, no memory for the copies -- field by field
+    const int batch = refit_batch_option();
+    const bool batched = nfields >= 2 && batch > 1 && p->factor_valid && nd::nd_batch_ready(p) && refit_buffers_ready(p);
+    p->rb.stats[0] = batched ? 2 : 1;
+    p->rb.stats[1] = p->rb.stats[2] = p->rb.stats[3] = 0;
+    if (!batched) return refit_field_by_field(p, c, 0, nfields, st);
+    for (int k0 = 0; k0 < nfields; k0 += batch) {
+        const int n = nfields - k0 < batch ? nfields - k0 : batch;
+        bool redo = n == 1;                    // (a last chunk of one field has nothing to share)
+        if (!redo) {
+            if (int rc = refit_chunk_batched(p, c, k0, n, st, &redo)) return rc;
+            if (redo) p->rb.stats[3] += n;     // a field of the chunk did not end in 0: the chunk again, by the loop that owns the 107 semantics
         }
+        if (redo)
+            if (int rc = refit_field_by_field(p, c, k0, k0 + n, st)) return rc;
     }
+    return 0;
+}
+
+int32_t splpak_debug_plan_refit_stats(const splpak_plan *p, int64_t out4[4])
+{
+    if (!p || !out4) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    for (int i = 0; i < 4; ++i) out4[i] = p->rb.stats[i];
     return 0;
 }
 

@@ -468,7 +468,9 @@ module splpak_module
     !! `refit` each -- the binning, the normal equations and their factorisation are functions of the points, the weights and
     !! the grid, and the HIP library keeps them on the device (include/splpak_hip.h, splpak_refit_f64).  The reference has no
     !! counterpart.  `ydata(ndata,nfields)`: the values, in the point order of that `initialize`; `coef(ncol,nfields)`: one
-    !! set of coefficients per field (`nfields` defaults to 1).  ierror: 0; 107 with the reference's message, as `initialize`;
+    !! set of coefficients per field (`nfields` defaults to 1).  On a grid whose factorisation is the nested dissection the fields of
+    !! a call are solved in chunks of up to 8 fields that share every sweep of the factor; every field's coefficients are bit for
+    !! bit those of its single-field `refit`, and a chunk with a failing field is run again field by field.  ierror: 0; 107 with the reference's message, as `initialize`;
     !! -3 for nfields < 1; -4, with a message, when there is nothing to refit on the device: no successful `initialize` of
     !! this object, another fit of the process since (the library holds one), `destroy`, or an object under set_host,
     !! set_gpus(n > 1) or with ndim > 4 -- `refit` never falls back to another path silently: call `initialize` per field there.

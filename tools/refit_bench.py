@@ -2,9 +2,11 @@
 """Fit against refit at BASELINE config 3 (3-D, 64^3 nodes, 1e7 weighted points of the seeded stream, xtrap = 1) through ONE plan
 on one MI355X: after a warm-up fit and refit, `--fits` fits and `--refits` refits of fresh values each, timed with a host clock
 around calls that end in a stream synchronise (both entries synchronise before they return).  Medians, the spread and the ratio;
-then, in a pass of its own with the plan's event timing on, the stages of one refit (splpak_plan_stage_timing).  One JSON line.
+then, in a pass of its own with the plan's event timing on, the stages of one refit (splpak_plan_stage_timing).  Then `--nfields`
+fresh fields cos((3 + k) sum x) three ways, median of 5 each: one call with refit_batch = 8 (shared sweeps of the factor), one call
+with refit_batch = 1 (field by field: the yardstick), and that many single-field calls; the stages of a batched call.  One JSON line.
 
-    python tools/refit_bench.py [--nodes 64] [--ndata 10000000] [--fits 3] [--refits 5]
+    python tools/refit_bench.py [--nodes 64] [--ndata 10000000] [--fits 3] [--refits 5] [--nfields 8]
 
 A measurement, not a test: nothing here asserts a time.  The refits are checked against the fit of the same values (2e-10).
 """
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--ndata", type=int, default=10_000_000)
     ap.add_argument("--fits", type=int, default=3)
     ap.add_argument("--refits", type=int, default=5)
+    ap.add_argument("--nfields", type=int, default=8)
     a = ap.parse_args()
     import torch
     from splpak_amd import capi
@@ -86,6 +89,49 @@ def main():
                refit_vs_fit_same_values=err,
                refit_stages_ms=dict(gather_and_rhs=float(stages["gram_ms"]), residual_pass=float(stages["residual_pass_ms"]),
                                     one_solve=float(stages["solve_ms"]), whole_call_with_events=ms_ev))
+    plan.enable_kernel_timing(False)
+    # ---- several fields in one call: batched sweeps against field by field
+    nf = a.nfields
+    if nf >= 1:
+        sx = x.sum(dim=1)
+        Y = torch.stack([torch.cos((3.0 + k) * sx) for k in range(nf)])
+        del sx
+        C = torch.zeros((nf, ncol), dtype=torch.float64, device=dev)
+
+        def calls(batch):
+            plan.set_option("refit_batch", str(batch))
+            return timed(lambda: plan.refit(Y, C, st))
+
+        def singles():
+            info = np.zeros((nf, 10))
+            rc = 0
+            for k in range(nf):
+                r, i = plan.refit(Y[k], C[k], st)
+                rc, info[k] = rc or r, i
+            return rc, info
+
+        res = {}
+        for label, run in (("batched", lambda: calls(8)), ("field_by_field", lambda: calls(1)), ("single_calls", lambda: timed(singles))):
+            run()                                           # warm-up (the first batched call allocates the per-field copies)
+            ms_all = []
+            for _ in range(5):
+                ms, rc, info = run()
+                assert rc == 0
+                ms_all.append(ms)
+            res[label] = dict(ms_median=float(np.median(ms_all)), ms=[round(v, 3) for v in ms_all], steps=[int(v) for v in info[:, 2]],
+                              stats=plan.refit_stats(), coef=C.clone())
+        same = bool(torch.equal(res["batched"]["coef"], res["field_by_field"]["coef"]) and torch.equal(res["batched"]["coef"], res["single_calls"]["coef"]))
+        assert same, "the batched refit does not give the bits of the field-by-field refit"
+        for r in res.values():
+            del r["coef"]
+        plan.enable_kernel_timing(True)
+        ms_ev, rc, _ = calls(8)
+        stages = plan.stage_timing()
+        plan.set_option("refit_batch", None)
+        out["fields"] = dict(nfields=nf, **res, equal_bits=same,
+                             ratio_field_by_field_over_batched=res["field_by_field"]["ms_median"] / res["batched"]["ms_median"],
+                             batched_stages_ms=dict(last_gather_and_rhs=float(stages["gram_ms"]), residual_pass=float(stages["residual_pass_ms"]),
+                                                    first_sweep=float(stages["solve_ms"]), whole_call_with_events=ms_ev))
     plan.close()
     print(json.dumps(out))
 
