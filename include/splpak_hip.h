@@ -476,6 +476,53 @@ int64_t splpak_eval_grid_derivs_scratch_bytes(int32_t ndim, const int64_t *npts,
  * the fused tile kernel.  SPLPAK_E_BADARG: ndim outside 1..4, order outside 1..2 or a null pointer. */
 int32_t splpak_debug_eval_grid_derivs_tile(int32_t ndim, int32_t order, int32_t out4[4]);
 
+/* Definite integrals of the fit over the cells of a tensor grid: the total over a box (ncell = 1 everywhere), the cell
+ * integrals of a finite-volume mesh (the mean is the caller's division by the cell volume: conservative remapping), a
+ * projection (a 3-D fit integrated along z onto an x-y image, a column density).  Exact: the fit is one global piecewise
+ * polynomial -- per dimension a cubic on every node cell [xmin + k*dx, xmin + (k+1)*dx], a straight line below xmin and
+ * above xmax -- so every cell is cut at the node lines and each piece integrated by two-point Gauss-Legendre.
+ *   mode   mode[d] = 1: dimension d is INTEGRATED, its axis holds ncell[d] + 1 edges and output index j is the cell from
+ *          e[j] to e[j+1];  mode[d] = 0: dimension d is EVALUATED, its axis holds ncell[d] coordinates as for
+ *          splpak_eval_grid_* (values only).  NULL: every dimension is integrated.
+ *   axes   the axes back to back, as splpak_eval_grid_* takes them.  Edges may be anything: unsorted, repeated
+ *          (e[j] == e[j+1] gives exactly 0), outside the grid (the integral of the linear extrapolation), reversed (the
+ *          exact negation of the cell taken the other way round).  Non-finite edges may give non-finite results.
+ *   out    prod_d ncell[d] values, dimension 1 fastest, in the ordering of splpak_eval_grid_*.
+ * Summation order: a piece of a cell is its part inside one node cell (or below xmin, or above xmax).  The integral over
+ * every product of pieces is formed by the contraction of splpak_eval_grid_*; each output is then the sum over its pieces
+ * in ascending piece order, dimension 1 innermost, one accumulator per dimension, plain additions.  The bits therefore do
+ * not depend on how a large call is cut into slabs (option integrate_scratch_mb: the cap of the double intermediate in
+ * MB, default 256; larger calls go in slabs of consecutive cells of the last dimension, a single layer above the cap is
+ * allocated whole).  REAL32: storage is float; edges and coefficients are widened first, every intermediate is double,
+ * and there is one rounding at the final store.  With every mode 0 the values are the bits of splpak_eval_grid_* with
+ * nderiv == NULL.
+ * Status, decided on the host before any device work, in the order of splpak_eval_grid_* with ncell in place of npts:
+ * 101/102/103 return without computing, `out` set to 0 (101: out[0] alone); SPLPAK_E_UNSUPPORTED: ndim > 4;
+ * SPLPAK_E_BADARG: a null pointer, a negative ncell[d], a mode[d] outside 0 and 1, a product of ncell beyond int64.  If
+ * any ncell[d] is 0 the validation status is returned and nothing is written.  There is no nderiv, hence no 104.
+ * SPLPAK_E_NOMEM: the tables and the intermediate could not be allocated. */
+int32_t splpak_integrate_grid_f64(int32_t ndim, const int64_t *ncell, const int32_t *mode, const double *axes,
+                                  const double *coef, const double *xmin, const double *xmax, const int32_t *nodes,
+                                  double *out);
+int32_t splpak_integrate_grid_f32(int32_t ndim, const int64_t *ncell, const int32_t *mode, const float *axes,
+                                  const float *coef, const float *xmin, const float *xmax, const int32_t *nodes,
+                                  float *out);
+/* the same on resident data; ncell, mode, xmin, xmax and nodes are host arrays.  NOT fully asynchronous: `stream` is
+ * synchronised ONCE, after the pass that counts the pieces of every cell -- the counts are read back to size the tables
+ * and the launches; everything after that is queued on `stream`.  (Hence not usable inside a stream capture.)  With
+ * every mode 0 the call is splpak_eval_grid_dev_* and waits for nothing. */
+int32_t splpak_integrate_grid_dev_f64(int32_t ndim, const int64_t *ncell /* host */, const int32_t *mode /* host, may be NULL */,
+                                      const double *axes_dev, const double *coef_dev, const double *xmin, const double *xmax,
+                                      const int32_t *nodes, double *out_dev, void *stream);
+int32_t splpak_integrate_grid_dev_f32(int32_t ndim, const int64_t *ncell /* host */, const int32_t *mode /* host, may be NULL */,
+                                      const float *axes_dev, const float *coef_dev, const float *xmin, const float *xmax,
+                                      const int32_t *nodes, float *out_dev, void *stream);
+/* Diagnostics, host counters of the calling thread's last splpak_integrate_grid_* call (nothing is waited for):
+ * [0] slabs, [1] doubles of intermediate held (piece products and the first reduction's result), [2..5] table entries per
+ * axis (the pieces; ncell[d] for an evaluated axis; 0 beyond ndim), [6] reduction launches, [7] 0.  The tables and the
+ * intermediate live in the scratch of splpak_eval_grid_*, grown on demand and released by splpak_shutdown. */
+int32_t splpak_debug_integrate_grid_stats(int64_t out8[8]);
+
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
  * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one
  * splpak_eval_* call per field -- each reading the coordinates, building the factor tables and, for a large batch on a

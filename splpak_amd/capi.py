@@ -35,6 +35,8 @@ SYMBOLS = [
     "splpak_eval_grid_scratch_bytes", "splpak_debug_eval_grid_stats",
     "splpak_eval_grid_derivs_f64", "splpak_eval_grid_derivs_f32", "splpak_eval_grid_derivs_dev_f64", "splpak_eval_grid_derivs_dev_f32",
     "splpak_eval_grid_derivs_scratch_bytes", "splpak_debug_eval_grid_derivs_tile",
+    "splpak_integrate_grid_f64", "splpak_integrate_grid_f32", "splpak_integrate_grid_dev_f64", "splpak_integrate_grid_dev_f32",
+    "splpak_debug_integrate_grid_stats",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
     "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
@@ -166,6 +168,16 @@ def lib() -> C.CDLL:
     L.splpak_eval_grid_derivs_scratch_bytes.argtypes = [i32, _lp, i32]
     L.splpak_debug_eval_grid_derivs_tile.restype = i32
     L.splpak_debug_eval_grid_derivs_tile.argtypes = [i32, i32, _ip]
+    L.splpak_integrate_grid_f64.restype = i32
+    L.splpak_integrate_grid_f64.argtypes = [i32, _lp, _ip, _dp, _dp, _dp, _dp, _ip, _dp]
+    L.splpak_integrate_grid_f32.restype = i32
+    L.splpak_integrate_grid_f32.argtypes = [i32, _lp, _ip, _fp, _fp, _fp, _fp, _ip, _fp]
+    L.splpak_integrate_grid_dev_f64.restype = i32
+    L.splpak_integrate_grid_dev_f64.argtypes = [i32, _lp, _ip, vp, vp, _dp, _dp, _ip, vp, vp]
+    L.splpak_integrate_grid_dev_f32.restype = i32
+    L.splpak_integrate_grid_dev_f32.argtypes = [i32, _lp, _ip, vp, vp, _fp, _fp, _ip, vp, vp]
+    L.splpak_debug_integrate_grid_stats.restype = i32
+    L.splpak_debug_integrate_grid_stats.argtypes = [_lp]
     L.splpak_eval_fields_f64.restype = i32
     L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
     L.splpak_eval_fields_f32.restype = i32
@@ -497,6 +509,34 @@ def debug_eval_grid_derivs_tile(ndim, order):
     """Outputs per workgroup tile per dimension (1 beyond ndim) of a grid-derivatives call with this ndim and order."""
     v = np.zeros(4, dtype=np.int32)
     _check(lib().splpak_debug_eval_grid_derivs_tile(int(ndim), int(order), _p(v, _ip)))
+    return tuple(int(t) for t in v)
+
+
+def integrate_grid(ndim, axes, mode, coef, xmin, xmax, nodes, real32=False):
+    """Integrals of the fit over the cells of a tensor grid (splpak_integrate_grid_*).  `axes` is a list of `ndim` 1-D arrays:
+    the n + 1 edges of the n cells of a dimension with mode[d] = 1 (integrated), the n coordinates of one with mode[d] = 0
+    (evaluated); mode None: every dimension is integrated.  Edges may be unsorted, repeated, reversed or outside the grid.
+    -> (values of shape (n_ndim, ..., n_1), C-ordered as evaluate_grid returns its own; ierror)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
+    md = None if mode is None else np.ascontiguousarray(mode, dtype=np.int32)
+    ncell = np.array([a.size - (1 if md is None else int(md[d] == 1)) for d, a in enumerate(axes)], dtype=np.int64)
+    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    coef = np.ascontiguousarray(coef, dtype=dt)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    out = np.zeros(tuple(max(int(n), 0) for n in ncell[::-1]), dtype=dt)
+    fn = lib().splpak_integrate_grid_f32 if real32 else lib().splpak_integrate_grid_f64
+    rc = _check(fn(ndim, _p(ncell, C.POINTER(C.c_int64)), _p(md, _ip), _p(cat, rp), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), _p(out, rp)))
+    return out, rc
+
+
+def debug_integrate_grid_stats():
+    """Host counters of this thread's last integrate_grid call: (slabs, doubles of intermediate held, table entries of the four
+    axes, reduction launches, 0)."""
+    v = np.zeros(8, dtype=np.int64)
+    _check(lib().splpak_debug_integrate_grid_stats(_p(v, C.POINTER(C.c_int64))))
     return tuple(int(t) for t in v)
 
 
@@ -851,6 +891,20 @@ def evaluate_grid_dev(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, st
     return _check(lib().splpak_eval_grid_dev_f64(ndim, _p(npts, lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
                                                  _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), out.data_ptr(),
                                                  C.c_void_p(stream)))
+
+
+def integrate_grid_dev(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out, stream=0):
+    """integrate_grid on torch device tensors: `axes` holds the axes back to back (ncell[d] + 1 edges of an integrated
+    dimension, ncell[d] coordinates of an evaluated one), `out` has prod(ncell) entries, dimension 1 fastest.  `stream` is
+    synchronised once (the piece counts come back to the host); the rest is queued on it.  float32 tensors take the REAL32 entry."""
+    md = None if mode is None else np.ascontiguousarray(mode, dtype=np.int32)
+    ncell = np.ascontiguousarray(ncell, dtype=np.int64)
+    real32 = str(axes.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    fn = lib().splpak_integrate_grid_dev_f32 if real32 else lib().splpak_integrate_grid_dev_f64
+    rp = _fp if real32 else _dp
+    return _check(fn(ndim, _p(ncell, C.POINTER(C.c_int64)), _p(md, _ip), axes.data_ptr(), coef.data_ptr(), _p(xmin, rp), _p(xmax, rp),
+                     _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
 
 
 def evaluate_grid_derivs_dev(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, stream=0):

@@ -2,7 +2,7 @@
 // pointers, the evaluation mode, and the host-only / synthetic-data helpers that need no plan.
 //
 // Every entry family has ONE ladder of argument checks (point_validate for the value and the derivative entries,
-// fields_validate, grid_validate, grid_derivs_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
+// fields_validate, grid_validate, integrate_validate, grid_derivs_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
 // Where two entries of a family have always answered differently, the difference is a named parameter of the ladder.
 #include "plan.hpp"
 #include "basis.hpp"
@@ -431,6 +431,125 @@ int32_t splpak_debug_eval_grid_stats(int64_t out2[2])
     SPLPAK_HIP_TRY(eval_grid_stats(v), SPLPAK_E_NODEVICE);
     out2[0] = v[0];
     out2[1] = v[1];
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- integrals over the cells of a tensor grid (integrategrid.hip) ----
+// The ladder of grid_validate with ncell in place of npts and the mode check beside the count check; no nderiv, hence no 104.
+// nax: the axis entries (ncell[d] + 1 edges of an integrated dimension, ncell[d] coordinates of an evaluated one).
+template <typename T>
+static bool integrate_validate(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes, const T *coef, const T *xmin_t,
+                               const T *xmax_t, const int32_t *nodes, const T *out, Grid &g, long long &nout, long long &nax, int &rc,
+                               long long &zero_n)
+{
+    nout = 0;
+    nax = 0;
+    zero_n = 0;
+    if (!ncell) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    double xmin[MAXD], xmax[MAXD];
+    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, xmin, xmax, rc, zero_n)) return false;
+    long long ntab = 0;
+    bool ok = grid_counts(ndim, ncell, nout, ntab);
+    for (int d = 0; ok && d < ndim; ++d) {
+        const int m = mode ? mode[d] : 1;
+        ok = (m == 0 || m == 1) && !__builtin_add_overflow(ntab, (long long)m, &ntab);
+    }
+    if (!ok) {
+        set_error("negative ncell, a mode outside 0 and 1, or an output count beyond int64");
+        rc = SPLPAK_E_BADARG;
+        return false;
+    }
+    nax = ntab;
+    rc = eval_validate(ndim, nullptr, xmin, xmax, nodes, g);
+    if (rc != 0) {
+        if (rc > 0 && out) zero_n = nout;
+        return false;
+    }
+    if (nout == 0) return false;
+    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
+    if (int r = device_ready()) { rc = r; return false; }
+    return true;
+}
+
+static int32_t integrate_status(hipError_t e)
+{
+    if (e == hipSuccess) return 0;
+    (void)hip_ok(e, "integration on a grid");
+    return e == hipErrorOutOfMemory ? SPLPAK_E_NOMEM : SPLPAK_E_NODEVICE;
+}
+
+template <typename T>
+static int32_t integrate_grid_dev(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes_dev, const T *coef_dev,
+                                  const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, void *stream)
+{
+    Grid g;
+    long long nout = 0, nax = 0, zero_n = 0;
+    int rc = 0;
+    if (!integrate_validate(ndim, ncell, mode, axes_dev, coef_dev, xmin, xmax, nodes, out_dev, g, nout, nax, rc, zero_n)) {
+        if (zero_n > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
+        return rc;
+    }
+    return integrate_status(launch_integrate_grid<T>(g, ncell, mode, axes_dev, coef_dev, out_dev, (hipStream_t)stream));
+}
+
+template <typename T>
+static int32_t integrate_grid_host(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes, const T *coef,
+                                   const T *xmin, const T *xmax, const int32_t *nodes, T *out)
+{
+    Grid g;
+    long long nout = 0, nax = 0, zero_n = 0;
+    int rc = 0;
+    if (!integrate_validate(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out, g, nout, nax, rc, zero_n)) {
+        for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
+        return rc;
+    }
+    bool nomem = false;
+    const int32_t r = staged_call<T>(axes, (size_t)nax, coef, (size_t)g.ncol, out, (size_t)nout, false, "integration on a grid", rc,
+                                     [&](const T *da, const T *dc, T *dout) {
+                                         const hipError_t e = launch_integrate_grid<T>(g, ncell, mode, da, dc, dout, nullptr);
+                                         nomem = e == hipErrorOutOfMemory;
+                                         return e;
+                                     });
+    return nomem ? SPLPAK_E_NOMEM : r;
+}
+
+extern "C" {
+
+int32_t splpak_integrate_grid_f64(int32_t ndim, const int64_t *ncell, const int32_t *mode, const double *axes, const double *coef,
+                                  const double *xmin, const double *xmax, const int32_t *nodes, double *out)
+{
+    return integrate_grid_host<double>(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out);
+}
+
+int32_t splpak_integrate_grid_f32(int32_t ndim, const int64_t *ncell, const int32_t *mode, const float *axes, const float *coef,
+                                  const float *xmin, const float *xmax, const int32_t *nodes, float *out)
+{
+    return integrate_grid_host<float>(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out);
+}
+
+int32_t splpak_integrate_grid_dev_f64(int32_t ndim, const int64_t *ncell, const int32_t *mode, const double *axes_dev,
+                                      const double *coef_dev, const double *xmin, const double *xmax, const int32_t *nodes,
+                                      double *out_dev, void *stream)
+{
+    return integrate_grid_dev<double>(ndim, ncell, mode, axes_dev, coef_dev, xmin, xmax, nodes, out_dev, stream);
+}
+
+int32_t splpak_integrate_grid_dev_f32(int32_t ndim, const int64_t *ncell, const int32_t *mode, const float *axes_dev,
+                                      const float *coef_dev, const float *xmin, const float *xmax, const int32_t *nodes,
+                                      float *out_dev, void *stream)
+{
+    return integrate_grid_dev<float>(ndim, ncell, mode, axes_dev, coef_dev, xmin, xmax, nodes, out_dev, stream);
+}
+
+// host-side counters of the calling thread's last integrate call (no device is asked, nothing is waited for)
+int32_t splpak_debug_integrate_grid_stats(int64_t out8[8])
+{
+    if (!out8) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    long long v[8];
+    integrate_grid_stats(v);
+    for (int j = 0; j < 8; ++j) out8[j] = v[j];
     return 0;
 }
 

@@ -72,7 +72,7 @@ template <int D> constexpr int gtile_outputs() { int s = 1; for (int e = 0; e < 
 // Contraction of dimension DD >= 1.  in[i0 + TX (m + M (j + R h))]: m = the output positions of dimensions 1 .. DD-1
 // (M of them), j = the box row of dimension DD, h = the box rows of the dimensions above (H of them).  Item
 // (m, i, h), i = output position of dimension DD, becomes dst[i0 + TX item] -- or, in the last dimension, the output.
-template <int D, int DD, typename T>
+template <int D, int DD, typename T>          // T: the output type
 __device__ inline void grid_stage(const double *__restrict__ in, double *__restrict__ dst, int R, int H, const int *tw,
                                   const double (*tb)[4], int a, const long long (&o0)[D], const GridShape &gs,
                                   T *__restrict__ out)
@@ -113,10 +113,12 @@ __device__ inline void grid_stage(const double *__restrict__ in, double *__restr
     }
 }
 
-template <int D, typename T>
+// TC: storage type of the coefficients, TO: of the outputs (the grid entries: the same; the integrals of integrategrid.hip:
+// REAL32 coefficients, double piece values)
+template <int D, typename TC, typename TO>
 __global__ void __launch_bounds__(GRID_NT)
 eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int *__restrict__ wst,
-                 const T *__restrict__ coef, T *__restrict__ out, unsigned long long *__restrict__ stats)
+                 const TC *__restrict__ coef, TO *__restrict__ out, unsigned long long *__restrict__ stats)
 {
     using GT = GTile<D>;
     constexpr int TX = GT::T[0], NTAB = gtile_tab<D>(D);
@@ -211,17 +213,17 @@ eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int
             }
             __syncthreads();
             if constexpr (D == 2) {
-                grid_stage<D, 1, T>(bufA, nullptr, R[1], 1, tw, tb, a[1], o0, gs, out);
+                grid_stage<D, 1, TO>(bufA, nullptr, R[1], 1, tw, tb, a[1], o0, gs, out);
             } else if constexpr (D == 3) {
-                grid_stage<D, 1, T>(bufA, bufB, R[1], R[2], tw, tb, a[1], o0, gs, out);
+                grid_stage<D, 1, TO>(bufA, bufB, R[1], R[2], tw, tb, a[1], o0, gs, out);
                 __syncthreads();
-                grid_stage<D, 2, T>(bufB, nullptr, R[2], 1, tw, tb, a[2], o0, gs, out);
+                grid_stage<D, 2, TO>(bufB, nullptr, R[2], 1, tw, tb, a[2], o0, gs, out);
             } else {
-                grid_stage<D, 1, T>(bufA, bufB, R[1], R[2] * R[3], tw, tb, a[1], o0, gs, out);
+                grid_stage<D, 1, TO>(bufA, bufB, R[1], R[2] * R[3], tw, tb, a[1], o0, gs, out);
                 __syncthreads();
-                grid_stage<D, 2, T>(bufB, bufA, R[2], R[3], tw, tb, a[2], o0, gs, out);
+                grid_stage<D, 2, TO>(bufB, bufA, R[2], R[3], tw, tb, a[2], o0, gs, out);
                 __syncthreads();
-                grid_stage<D, 3, T>(bufA, nullptr, R[3], 1, tw, tb, a[3], o0, gs, out);
+                grid_stage<D, 3, TO>(bufA, nullptr, R[3], 1, tw, tb, a[3], o0, gs, out);
             }
         }
         return;
@@ -249,7 +251,7 @@ eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int
         if (!ok) continue;
         const double sum = window_sum<D>(b, [&](int k1, int k2, int k3, double (&c)[4]) {
             const long long ci = base + k1 * s1 + k2 * s2 + k3 * s3;
-            if constexpr (sizeof(T) == 8) {
+            if constexpr (sizeof(TC) == 8) {
                 typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
                 const d2v lo = *reinterpret_cast<const d2v *>(coef + ci);
                 const d2v hi = *reinterpret_cast<const d2v *>(coef + ci + 2);
@@ -260,7 +262,7 @@ eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int
                 c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
             }
         });
-        out[idx] = (T)sum;
+        out[idx] = (TO)sum;
     }
 }
 
@@ -288,11 +290,38 @@ hipError_t eval_grid_stats(long long out2[2])
     return hipSuccess;
 }
 
+int eval_grid_tile(int ndim, int d) { return ndim == 1 ? GTile<1>::T[d] : ndim == 2 ? GTile<2>::T[d] : ndim == 3 ? GTile<3>::T[d] : GTile<4>::T[d]; }
+
+// the tile kernel on prepared tables: gs.npts and gs.off are the caller's, the tile counts are set here
+template <typename TC, typename TO>
+hipError_t launch_eval_grid_tables(const Grid &g, GridShape &gs, const double *fac, const int *wst, const TC *coef, TO *out,
+                                   unsigned long long *stats, hipStream_t st)
+{
+    long long ntiles = 1;
+    for (int d = 0; d < MAXD; ++d) {
+        const int t = eval_grid_tile(g.ndim, d);
+        gs.ntile[d] = (gs.npts[d] + t - 1) / t;
+        if (__builtin_mul_overflow(ntiles, gs.ntile[d], &ntiles)) return hipErrorInvalidValue;
+    }
+    if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
+    dim3 gr((unsigned)ntiles), bl(GRID_NT);
+    switch (g.ndim) {
+    case 1: hipLaunchKernelGGL((eval_grid_kernel<1, TC, TO>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
+    case 2: hipLaunchKernelGGL((eval_grid_kernel<2, TC, TO>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
+    case 3: hipLaunchKernelGGL((eval_grid_kernel<3, TC, TO>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
+    default: hipLaunchKernelGGL((eval_grid_kernel<4, TC, TO>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_eval_grid_tables<double, double>(const Grid &, GridShape &, const double *, const int *, const double *, double *, unsigned long long *, hipStream_t);
+template hipError_t launch_eval_grid_tables<float, float>(const Grid &, GridShape &, const double *, const int *, const float *, float *, unsigned long long *, hipStream_t);
+template hipError_t launch_eval_grid_tables<float, double>(const Grid &, GridShape &, const double *, const int *, const float *, double *, unsigned long long *, hipStream_t);
+
 template <typename T>
 hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, const int *nderiv, const T *coef, T *out, hipStream_t st)
 {
     GridShape gs;
-    long long ntab = 0, ntiles = 1;
+    long long ntab = 0;
     for (int d = 0; d < MAXD; ++d) {
         const long long n = d < g.ndim ? npts[d] : 1;
         if (n <= 0) return hipSuccess;
@@ -303,12 +332,6 @@ hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, c
     gs.off[MAXD] = ntab;
     for (int d = g.ndim; d < MAXD; ++d) gs.off[d] = ntab;
     const NDeriv nd = clamp_nderiv(nderiv, g.ndim);
-    for (int d = 0; d < MAXD; ++d) {
-        const int t = g.ndim == 1 ? GTile<1>::T[d] : g.ndim == 2 ? GTile<2>::T[d] : g.ndim == 3 ? GTile<3>::T[d] : GTile<4>::T[d];
-        gs.ntile[d] = (gs.npts[d] + t - 1) / t;
-        ntiles *= gs.ntile[d];
-    }
-    if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
     DevScratch<1> &s = g_gscratch;
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -323,16 +346,9 @@ hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, c
         dim3 gr((unsigned)((ntab + 255) / 256)), bl(256);
         hipLaunchKernelGGL((value_only(nd) ? grid_table_kernel<T, true> : grid_table_kernel<T, false>), gr, bl, 0, st, g, gs, nd, axes, fac, wst);
     }
-    dim3 gr((unsigned)ntiles), bl(GRID_NT);
-    switch (g.ndim) {
-    case 1: hipLaunchKernelGGL((eval_grid_kernel<1, T>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
-    case 2: hipLaunchKernelGGL((eval_grid_kernel<2, T>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
-    case 3: hipLaunchKernelGGL((eval_grid_kernel<3, T>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
-    default: hipLaunchKernelGGL((eval_grid_kernel<4, T>), gr, bl, 0, st, g, gs, fac, wst, coef, out, stats); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = s.mark_used(st);
-    return e;
+    const hipError_t e = launch_eval_grid_tables<T, T>(g, gs, fac, wst, coef, out, stats, st);
+    const hipError_t m = s.mark_used(st);                   // also after a refused tile count: the table kernel is queued
+    return e != hipSuccess ? e : m;
 }
 template hipError_t launch_eval_grid<double>(const Grid &, const int64_t *, const double *, const int *, const double *, double *, hipStream_t);
 template hipError_t launch_eval_grid<float>(const Grid &, const int64_t *, const float *, const int *, const float *, float *, hipStream_t);

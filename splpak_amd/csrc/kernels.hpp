@@ -61,6 +61,16 @@ long long eval_grid_derivs_scratch_bytes(long long ntab, int order);
 // outputs of a workgroup tile per dimension (1 beyond ndim); false: ndim outside 1 .. MAXD or order outside 1 .. 2
 bool eval_grid_derivs_tile(int ndim, int order, int out4[4]);
 
+// ---- integrategrid.hip
+// out[j0 + ncell[0] (j1 + ...)] = the fit integrated over cell j_d of every dimension with mode[d] = 1 (axis: ncell[d] + 1
+// edges) at coordinate j_d of every dimension with mode[d] = 0 (axis: ncell[d] coordinates); mode null: all integrated.
+// Synchronises st once (the piece counts come back to the host).  hipErrorOutOfMemory: the scratch could not be allocated.
+template <typename T>
+hipError_t launch_integrate_grid(const Grid &g, const int64_t *ncell, const int *mode, const T *axes, const T *coef, T *out, hipStream_t st);
+// host counters of the calling thread's last launch_integrate_grid: slabs [0], doubles of intermediate [1], table entries per
+// axis [2..5], reduction launches [6], 0 [7]
+void integrate_grid_stats(long long out8[8]);
+
 // ---- synth.hip
 hipError_t launch_synth_points(int ndim, long long first, long long n, double *x, double *y,
                                double *w, hipStream_t st);

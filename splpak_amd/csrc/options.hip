@@ -21,6 +21,7 @@ const Known KNOWN[] = {
     {"SPLPAK_DIST_CHUNK", 0},
     {"SPLPAK_GRAM_SCRATCH_MB", 1},
     {"SPLPAK_GRAM_VALU", 0},
+    {"SPLPAK_INTEGRATE_SCRATCH_MB", 1},
     {"SPLPAK_MPLAN_BAND", 0},
     {"SPLPAK_MPLAN_RCCL", 1},
     {"SPLPAK_NARROW_BW", 0},

@@ -25,6 +25,7 @@
 !!    `evaluate_fields` evaluates several coefficient sets (what `refit` returns) at the same batch of points in one call,
 !!    `evaluate_grid` evaluates every point of a tensor-product grid of points from its axes alone,
 !!    `evaluate_grid_derivatives` value + gradient (+ Hessian) on such a grid, one plane per entry, in one pass,
+!!    `integrate_grid` integrates the fit over the cells of a tensor grid (cell integrals, projections), `integrate` over one box,
 !!    `last_fit_info` returns the diagnostics of the last fit (the residual norm `reserr` that the
 !!    reference computes, suprls :1693, and drops, splcw :690; row counts; refinement steps).
 !!
@@ -75,6 +76,8 @@ module splpak_module
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
         procedure,public :: evaluate_grid => splpak_eval_grid       !! every point of a tensor-product grid of points (additive)
         procedure,public :: evaluate_grid_derivatives => splpak_eval_grid_derivs !! value + gradient (+ Hessian) planes on such a grid (additive)
+        procedure,public :: integrate_grid => splpak_integrate_grid !! integrals over the cells of a tensor grid, projections (additive)
+        procedure,public :: integrate     => splpak_integrate       !! the integral over one box (additive)
         procedure,public :: evaluate_fields => splpak_eval_fields   !! several coefficient sets at the same batch of points (additive)
         procedure,public :: refit         => splpak_refit           !! new values on the points of the last `initialize` (additive)
         procedure,public :: destroy       => destroy_splpak
@@ -92,6 +95,8 @@ module splpak_module
         procedure,private :: splpak_eval_grid
         procedure,private :: splpak_eval_grid_derivs
         procedure,private :: splpak_eval_fields
+        procedure,private :: splpak_integrate_grid
+        procedure,private :: splpak_integrate
     end type splpak_type
 
 #ifndef REAL128
@@ -156,6 +161,17 @@ module splpak_module
             integer(c_int64_t),value :: ldout
             type(c_ptr),value :: npts, axes, coef, xmin, xmax, nodes, out
         end function c_eval_grid_derivs
+#ifdef REAL32
+        integer(c_int32_t) function c_integrate_grid(ndim,ncell,mode,axes,coef,xmin,xmax,nodes,out) &
+                                                     bind(C,name='splpak_integrate_grid_f32')
+#else
+        integer(c_int32_t) function c_integrate_grid(ndim,ncell,mode,axes,coef,xmin,xmax,nodes,out) &
+                                                     bind(C,name='splpak_integrate_grid_f64')
+#endif
+            import :: c_int32_t, c_ptr
+            integer(c_int32_t),value :: ndim
+            type(c_ptr),value :: ncell, mode, axes, coef, xmin, xmax, nodes, out
+        end function c_integrate_grid
 #ifdef REAL32
         integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
                                                   bind(C,name='splpak_eval_fields_f32')
@@ -996,6 +1012,198 @@ module splpak_module
             if (ierror < 0) call report_library_failure(ierror,'evaluate_grid_derivatives')
         end select
     end subroutine splpak_eval_grid_derivs
+
+    !> Integrals of a fit over the cells of a tensor grid: dimension idim with mode(idim) = 1 is INTEGRATED -- its axis holds
+    !! ncell(idim)+1 edges and output index j is the cell from e(j) to e(j+1) -- and one with mode(idim) = 0 is EVALUATED at
+    !! its ncell(idim) coordinates, as in `evaluate_grid`.  `axes` holds the axes back to back; `f` has product(ncell)
+    !! entries, dimension 1 fastest.  Edges may be unsorted, repeated (an empty cell is 0), reversed (the negation) and
+    !! outside the grid (the integral of the linear extrapolation).  Exact: every cell is cut at the node lines and each
+    !! piece integrated by two-point Gauss-Legendre.  A mean is the caller's division by the cell volume.
+    !! One call of the HIP library (splpak_integrate_grid_f64); under set_host(.true.), in the -DREAL128 build, for ndim > 4
+    !! or with SPLPAK_HOST_IF_NO_GPU=1 the same pieces and the same rule over the module's scalar evaluation.
+    !! ierror: 101..103 as splfe, -3 for a negative ncell or a mode outside 0 and 1.
+    subroutine splpak_integrate_grid(me,ndim,ncell,mode,axes,coef,xmin,xmax,nodes,f,ierror)
+        class(splpak_type),intent(inout) :: me
+        integer,intent(in) :: ndim
+        integer,intent(in) :: ncell(*), mode(*)
+        real(wp),intent(in),target :: axes(*)
+        real(wp),intent(in),target :: coef(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(out),target :: f(*)
+        integer,intent(out) :: ierror
+        integer(c_int32_t) :: rc
+        integer(c_int64_t),target :: nc64(max(ndim,1))
+        integer(c_int32_t),target :: md32(max(ndim,1))
+        integer(c_int64_t) :: iq, nq
+        integer :: idim, ie, mxq, nder(max(ndim,1)), k(max(ndim,1)), kq(max(ndim,1)), nqd(max(ndim,1)), off(max(ndim,1))
+        real(wp) :: x(max(ndim,1)), acc(max(ndim,1)), v
+        real(wp),allocatable :: xq(:,:), wq(:,:)
+        me%mdim = ndim
+        rc = 0
+        nc64 = 0
+        md32 = 1
+        do idim = 1, ndim
+            nc64(idim) = int(ncell(idim),c_int64_t)
+            md32(idim) = int(mode(idim),c_int32_t)
+        end do
+#ifndef REAL128
+        if (.not. (host_takes(me,ndim) .and. ndim >= 1)) &
+            rc = c_integrate_grid(int(ndim,c_int32_t), c_loc(nc64), c_loc(md32), c_loc(axes), c_loc(coef), c_loc(xmin), &
+                                  c_loc(xmax), c_loc(nodes), c_loc(f))
+#endif
+        if ((host_takes(me,ndim) .or. host_if_no_gpu(int(rc))) .and. ndim >= 1) then   ! host solver: the rule over the scalar evaluation
+            ierror = 0
+            nq = 1
+            ie = 0
+            do idim = 1, ndim
+                if (ncell(idim) < 0 .or. mode(idim) < 0 .or. mode(idim) > 1) then
+                    ierror = -3
+                    call report(ierror,' integrate_grid - NCELL(IDIM) is negative or MODE(IDIM) is not 0 or 1 for some IDIM')
+                    return
+                end if
+                off(idim) = ie
+                ie = ie + ncell(idim) + mode(idim)
+                nq = nq*nc64(idim)
+            end do
+            nder = 0
+            x(1:ndim) = xmin(1:ndim)
+            v = eval_point(me,ndim,x,nder,coef,xmin,xmax,nodes,ie)     ! the checks of the grid (102, 103)
+            if (ie /= 0) then
+                ierror = ie
+                f(1:nq) = 0.0_wp
+                return
+            end if
+            mxq = 2*(maxval(nodes(1:ndim)) + 1)                        ! at most nodes + 1 pieces per cell
+            allocate(xq(mxq,ndim), wq(mxq,ndim))
+            k = 1
+            do iq = 1, nq
+                do idim = 1, ndim
+                    if (mode(idim) == 0) then
+                        nqd(idim) = 1
+                        xq(1,idim) = axes(off(idim) + k(idim))
+                        wq(1,idim) = 1.0_wp
+                    else
+                        call cell_rule(axes(off(idim) + k(idim)), axes(off(idim) + k(idim) + 1), xmin(idim), xmax(idim), &
+                                       nodes(idim), nqd(idim), xq(:,idim), wq(:,idim))
+                    end if
+                end do
+                ! the tensor of the points: dimension 1 innermost, one accumulator per dimension
+                acc = 0.0_wp
+                kq = 1
+                tensor: do
+                    do idim = 1, ndim
+                        x(idim) = xq(kq(idim),idim)
+                    end do
+                    v = eval_point(me,ndim,x,nder,coef,xmin,xmax,nodes,ie)
+                    acc(1) = acc(1) + wq(kq(1),1)*v
+                    idim = 1
+                    do
+                        kq(idim) = kq(idim) + 1
+                        if (kq(idim) <= nqd(idim)) exit
+                        kq(idim) = 1
+                        if (idim == ndim) exit tensor
+                        acc(idim+1) = acc(idim+1) + wq(kq(idim+1),idim+1)*acc(idim)
+                        acc(idim) = 0.0_wp
+                        idim = idim + 1
+                    end do
+                end do tensor
+                f(iq) = acc(ndim)
+                idim = 1                                    ! odometer over the cells, first dimension fastest
+                do while (idim <= ndim)
+                    k(idim) = k(idim) + 1
+                    if (k(idim) <= ncell(idim)) exit
+                    k(idim) = 1
+                    idim = idim + 1
+                end do
+            end do
+            return
+        end if
+#ifdef REAL128
+        rc = -1
+#endif
+        ierror = int(rc)
+        select case (ierror)
+        case (0)
+        case (101); call report(ierror,' splfe or splde - NDIM is less than 1')
+        case (102); call report(ierror,' splfe or splde - NODES(IDIM) is less than  4for some IDIM')
+        case (103); call report(ierror,' splfe or splde - XMIN(IDIM) = XMAX(IDIM) for some IDIM')
+        case default
+            if (ierror < 0) call report_library_failure(ierror,'integrate_grid')
+        end select
+    end subroutine splpak_integrate_grid
+
+    !> The two Gauss-Legendre points and weights of every piece of the cell e0 .. e1 of one dimension: the cell is cut at the
+    !! node lines xmin + k*dx, the region of a coordinate is k = floor((x - xmin)/dx) clamped to -1 .. nodes-1, the weights
+    !! carry the sign of e1 - e0.  The construction of csrc/pieces.hpp, not its arithmetic: the device forms the region
+    !! from dxin*(x - xmin), so for an edge within a rounding of a node line the two may cut one piece more or less -- a
+    !! piece of a few ulps, which changes the integral by less than a rounding.  Everything here is in the working
+    !! precision wp: under -DREAL32 the host form accumulates in single precision, unlike the device.
+    subroutine cell_rule(e0,e1,xmin,xmax,nodes,n,xq,wq)
+        real(wp),intent(in) :: e0, e1, xmin, xmax
+        integer,intent(in) :: nodes
+        integer,intent(out) :: n
+        real(wp),intent(out) :: xq(:), wq(:)
+        real(wp) :: lo, hi, dx, a, b, m, h, sgn
+        integer :: klo, khi, q, r
+        lo = min(e0,e1)
+        hi = max(e0,e1)
+        sgn = merge(1.0_wp, -1.0_wp, e0 <= e1)
+        dx = (xmax - xmin)/real(nodes - 1,wp)
+        klo = region(lo)
+        khi = max(region(hi), klo)
+        n = 0
+        do q = 0, khi - klo
+            r = klo + q
+            a = lo
+            b = hi
+            if (q > 0) a = min(max(xmin + real(r,wp)*dx, lo), hi)
+            if (q < khi - klo) b = min(max(xmin + real(r+1,wp)*dx, lo), hi)
+            m = 0.5_wp*(a + b)
+            h = 0.5_wp*(b - a)
+            xq(n+1) = m - h/sqrt(3.0_wp)
+            xq(n+2) = m + h/sqrt(3.0_wp)
+            wq(n+1) = sgn*h
+            wq(n+2) = sgn*h
+            n = n + 2
+        end do
+    contains
+        integer function region(x)
+            real(wp),intent(in) :: x
+            real(wp) :: t
+            t = (x - xmin)/dx
+            if (.not. (t >= 0.0_wp)) then
+                region = -1
+            else if (t >= real(nodes - 1,wp)) then
+                region = nodes - 1
+            else
+                region = int(t)
+            end if
+        end function region
+    end subroutine cell_rule
+
+    !> The integral of a fit over the box lower(idim) .. upper(idim): `integrate_grid` with one cell in every dimension.
+    subroutine splpak_integrate(me,ndim,lower,upper,coef,xmin,xmax,nodes,value,ierror)
+        class(splpak_type),intent(inout) :: me
+        integer,intent(in) :: ndim
+        real(wp),intent(in) :: lower(*), upper(*)
+        real(wp),intent(in),target :: coef(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(out) :: value
+        integer,intent(out) :: ierror
+        real(wp),target :: ax(2*max(ndim,1)), f1(1)
+        integer :: one(max(ndim,1)), idim
+        one = 1
+        ax = 0.0_wp
+        do idim = 1, ndim
+            ax(2*idim-1) = lower(idim)
+            ax(2*idim) = upper(idim)
+        end do
+        f1 = 0.0_wp
+        call splpak_integrate_grid(me,ndim,one,one,ax,coef,xmin,xmax,nodes,f1,ierror)
+        value = f1(1)
+    end subroutine splpak_integrate
 
     !> Several coefficient sets at the same batch of points -- the evaluation half of `refit`: f(i,k) is the spline of
     !! coef(:,k) (with `nderiv`, that partial derivative) at x(:,i), the very value `evaluate_many` returns for that field.
