@@ -523,6 +523,90 @@ int32_t splpak_integrate_grid_dev_f32(int32_t ndim, const int64_t *ncell /* host
  * intermediate live in the scratch of splpak_eval_grid_*, grown on demand and released by splpak_shutdown. */
 int32_t splpak_debug_integrate_grid_stats(int64_t out8[8]);
 
+/* The fit of samples given on a tensor-product grid of points: an image, a volume, a table -- the opposite direction of
+ * splpak_eval_grid_*.  Returns the coefficients splcw returns for the listed Cartesian product with the weights
+ * w(i0, i1, ..) = prod_d waxes_d[i_d], PROVIDED THAT FIT HAS NO CONSTRAINT ROWS: its rows are then (W_1 A_1) x ... x
+ * (W_D A_D), A_d the npts[d] x nodes[d] matrix of the four window values per axis coordinate, and the solution is
+ * C = (P_1 x ... x P_D) Y with P_d = (A_d^T W_d^2 A_d)^-1 A_d^T W_d^2: one streaming pass over the samples and D 7-band
+ * solves along the axes of the coefficient tensor, instead of 8 (ndim + 1) bytes per sample, a sort and a factorisation.
+ *   npts, axes  as for splpak_eval_grid_*: the axes back to back, in any order, repeats and values outside the box allowed;
+ *   waxes       the same layout, one weight per axis coordinate; NULL: all 1 (there is no negative-first-weight sentinel);
+ *   values      field k's prod npts samples at values + k*ldv, dimension 1 fastest (what splpak_eval_grid_* writes);
+ *   coef        field k's ncol coefficients go to coef + k*ldcoef (the layout of splpak_refit_* and splpak_eval_fields_*).
+ * The words between the fields are neither read nor written.
+ * xtrap.  With xtrap == 0 the reference adds no constraint rows (:862).  With xtrap != 0 it adds them for data-sparse nodes
+ * (:921-1046); this entry then answers only when there are none, which it decides from per-axis nearest-node histograms:
+ * every coordinate must be counted in range -- k = int(dxin_d (x - xmin_d) + 0.5), truncated toward zero, in 0 .. nodes_d - 1
+ * --, every weight non-negative, and with h_d(j) the sum of the weights of the coordinates with k == j and ef = 0.5 at the
+ * two end nodes, 1 elsewhere:   prod_d min_j h_d(j) / ef(j)  >=  0.75 prod_d sum_j h_d(j) / prod_d (nodes_d - 1).
+ * Otherwise SPLPAK_E_UNSUPPORTED with the message "the sample has data-sparse nodes (or coordinates outside the counting
+ * range): constraint rows are not separable; list the points and use the point fit, or pass xtrap = 0" -- never a silent
+ * fallback.  The products of per-axis sums round differently from the reference's running sums over the points: a sample
+ * that sits exactly on the 0.75 threshold may be decided differently.
+ * Summation order.  Per axis the coordinates are ordered by (window start, original index): the TABLE ORDER.  The spread
+ * T = (A_1^T W_1^2 x ... x A_D^T W_D^2) Y is taken one dimension at a time, the last dimension first; the entry of node j
+ * is  acc = 0;  acc = fma(g, y, acc)  over the coordinates whose window holds node j, in table order, with g = waxes^2 *
+ * (general-form window value), rounded once.  The solves are band forward and back substitutions with the Cholesky factors
+ * of N_d = A_d^T W_d^2 A_d (formed on the host, coordinates in their original order; the substitutions multiply by the
+ * reciprocal of the diagonal, rounded once on the host), one line of the coefficient tensor at a time, dimension 1 first.  The bits of a
+ * result therefore depend on the axes, the weights and the field alone: not on the launch shape, the number of fields, the
+ * scratch cap, or the host / _dev entry.  There are no floating-point atomics.
+ * Refinement against the samples, the fit's own rule: R = Y - A C (A C by the tile kernel of splpak_eval_grid_* in double,
+ * into a scratch), spread, solve, add; stop when the estimated remaining error is below 1e-11, go on while the corrections
+ * contract (up to 30 steps), 107 with a message -- the coefficients as they stand -- if that misses 1e-10.  A well-conditioned
+ * sample costs three passes over the data: spread; evaluate and spread; stop.  Options (splpak_set_default_option or the
+ * environment): fit_grid_refine = nominal steps (default 4; 0: none), fit_grid_scratch_mb = cap of the residual scratch in
+ * MB (default 256; larger calls go in slabs of consecutive table positions of the last dimension, whose running sums
+ * continue from slab to slab by plain sequential accumulation; a single position above the cap is allocated whole).
+ * REAL32: storage is float; samples, axes and weights are widened on load, every intermediate is double, and there is one
+ * rounding at the store of coef.
+ * Status, decided on the host before any device work, the first failing check wins:
+ *   SPLPAK_E_BADARG       npts, nodes, xmin or xmax null;
+ *   101; SPLPAK_E_UNSUPPORTED (ndim > 4); 102, 103 as splcw;
+ *   104                   ldcoef < ncol;
+ *   105                   an npts[d] < 1;
+ *   SPLPAK_E_BADARG       a product of npts beyond int64, nfields < 1, ldv < prod npts, axes, values or coef null;
+ *   SPLPAK_E_UNSUPPORTED  the xtrap rule above;
+ *   107                   an axis whose N_d is not numerically positive definite (a non-positive Cholesky pivot or one below
+ *                         nodes_d * eps * the largest diagonal entry: too few distinct coordinates, all weights zero); the
+ *                         coefficients of every field are set to 0.
+ * On 101 .. 105 and the negative codes `coef` is untouched.  Then SPLPAK_E_NODEVICE / SPLPAK_E_NOMEM from the device part.
+ * info (optional, 10 doubles per field): [0] data rows = prod_d (coordinates of axis d with a non-zero weight), [1] 0,
+ * [2] refinement steps taken, [3] |last correction|_inf / |coef|_inf, [4] the smallest Cholesky pivot over the axes (the
+ * diagonal entry before its square root), [5] seconds in the host tables and factors (of the call), [6] 0, [7] seconds on
+ * the device (of the field), [8] ||W (A c - y)||_2 AS MEASURED IN THE LAST RESIDUAL PASS, i.e. for the coefficients before
+ * the last correction was added (0 with refinement off), [9] 0. */
+int32_t splpak_fit_grid_f64(int32_t ndim, const int64_t *npts, const double *axes, const double *waxes /* may be NULL */,
+                            int32_t nfields, const double *values, int64_t ldv, const double *xmin, const double *xmax,
+                            const int32_t *nodes, double xtrap, double *coef, int64_t ldcoef,
+                            double *info /* 10 per field, may be NULL */);
+int32_t splpak_fit_grid_f32(int32_t ndim, const int64_t *npts, const float *axes, const float *waxes /* may be NULL */,
+                            int32_t nfields, const float *values, int64_t ldv, const float *xmin, const float *xmax,
+                            const int32_t *nodes, float xtrap, float *coef, int64_t ldcoef,
+                            double *info /* 10 per field, may be NULL */);
+/* the same on resident data: axes, waxes, values and coef are device arrays; npts, xmin, xmax, nodes and info host arrays.
+ * NOT asynchronous: the sum npts axis coordinates and weights are copied to the host for the tables and the status checks
+ * (`stream` is synchronised once for that), and again after every refinement step and at the end of every field.  Hence
+ * not usable inside a stream capture, like splpak_integrate_grid_dev_*.  On 107 the coefficients are zeroed on `stream`. */
+int32_t splpak_fit_grid_dev_f64(int32_t ndim, const int64_t *npts /* host */, const double *axes_dev, const double *waxes_dev /* may be NULL */,
+                                int32_t nfields, const double *values_dev, int64_t ldv, const double *xmin, const double *xmax,
+                                const int32_t *nodes, double xtrap, double *coef_dev, int64_t ldcoef,
+                                double *info /* host, 10 per field, may be NULL */, void *stream);
+int32_t splpak_fit_grid_dev_f32(int32_t ndim, const int64_t *npts /* host */, const float *axes_dev, const float *waxes_dev /* may be NULL */,
+                                int32_t nfields, const float *values_dev, int64_t ldv, const float *xmin, const float *xmax,
+                                const int32_t *nodes, float xtrap, float *coef_dev, int64_t ldcoef,
+                                double *info /* host, 10 per field, may be NULL */, void *stream);
+/* Diagnostics.  One stage of the device part alone, host arrays, one field, no xtrap rule: stage 0: out[ncol] = T, the
+ * spread of in[prod npts] = the samples; stage 1: out[ncol] = C from in[ncol] = T, the solves alone (no refinement).
+ * Status as splpak_fit_grid_f64 (ldv = prod npts, ldcoef = ncol), then SPLPAK_E_BADARG for another stage. */
+int32_t splpak_debug_fit_grid_stage_f64(int32_t stage, int32_t ndim, const int64_t *npts, const double *axes,
+                                        const double *waxes /* may be NULL */, const double *xmin, const double *xmax,
+                                        const int32_t *nodes, const double *in, double *out);
+/* host counters of the calling thread's last splpak_fit_grid_* / stage call (nothing is waited for): [0] slabs of a residual
+ * pass (0: refinement off), [1] doubles of residual scratch held, [2] spread launches, [3] solve launches, [4] refinement
+ * steps of the last field, [5..7] 0.  The tables and intermediates live in a per-thread scratch released by splpak_shutdown. */
+int32_t splpak_debug_fit_grid_stats(int64_t out8[8]);
+
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
  * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one
  * splpak_eval_* call per field -- each reading the coordinates, building the factor tables and, for a large batch on a

@@ -37,6 +37,8 @@ SYMBOLS = [
     "splpak_eval_grid_derivs_scratch_bytes", "splpak_debug_eval_grid_derivs_tile",
     "splpak_integrate_grid_f64", "splpak_integrate_grid_f32", "splpak_integrate_grid_dev_f64", "splpak_integrate_grid_dev_f32",
     "splpak_debug_integrate_grid_stats",
+    "splpak_fit_grid_f64", "splpak_fit_grid_f32", "splpak_fit_grid_dev_f64", "splpak_fit_grid_dev_f32",
+    "splpak_debug_fit_grid_stage_f64", "splpak_debug_fit_grid_stats",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
     "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
@@ -178,6 +180,18 @@ def lib() -> C.CDLL:
     L.splpak_integrate_grid_dev_f32.argtypes = [i32, _lp, _ip, vp, vp, _fp, _fp, _ip, vp, vp]
     L.splpak_debug_integrate_grid_stats.restype = i32
     L.splpak_debug_integrate_grid_stats.argtypes = [_lp]
+    L.splpak_fit_grid_f64.restype = i32
+    L.splpak_fit_grid_f64.argtypes = [i32, _lp, _dp, _dp, i32, _dp, i64, _dp, _dp, _ip, dbl, _dp, i64, _dp]
+    L.splpak_fit_grid_f32.restype = i32
+    L.splpak_fit_grid_f32.argtypes = [i32, _lp, _fp, _fp, i32, _fp, i64, _fp, _fp, _ip, C.c_float, _fp, i64, _dp]
+    L.splpak_fit_grid_dev_f64.restype = i32
+    L.splpak_fit_grid_dev_f64.argtypes = [i32, _lp, vp, vp, i32, vp, i64, _dp, _dp, _ip, dbl, vp, i64, _dp, vp]
+    L.splpak_fit_grid_dev_f32.restype = i32
+    L.splpak_fit_grid_dev_f32.argtypes = [i32, _lp, vp, vp, i32, vp, i64, _fp, _fp, _ip, C.c_float, vp, i64, _dp, vp]
+    L.splpak_debug_fit_grid_stage_f64.restype = i32
+    L.splpak_debug_fit_grid_stage_f64.argtypes = [i32, i32, _lp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]
+    L.splpak_debug_fit_grid_stats.restype = i32
+    L.splpak_debug_fit_grid_stats.argtypes = [_lp]
     L.splpak_eval_fields_f64.restype = i32
     L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
     L.splpak_eval_fields_f32.restype = i32
@@ -537,6 +551,93 @@ def debug_integrate_grid_stats():
     axes, reduction launches, 0)."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_integrate_grid_stats(_p(v, C.POINTER(C.c_int64))))
+    return tuple(int(t) for t in v)
+
+
+def _grid_axes(axes, waxes, dt):
+    """(npts, the axes back to back, the weights back to back or None) of a list of 1-D arrays."""
+    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
+    npts = np.array([a.size for a in axes], dtype=np.int64)
+    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    wcat = None
+    if waxes is not None:
+        waxes = [np.ascontiguousarray(w, dtype=dt).ravel() for w in waxes]
+        if [w.size for w in waxes] != [a.size for a in axes]:
+            raise SplpakError("fit_grid: waxes must hold one weight per axis coordinate")
+        wcat = np.ascontiguousarray(np.concatenate(waxes)) if waxes else np.zeros(0, dtype=dt)
+    return npts, cat, wcat
+
+
+def fit_grid(ndim, axes, values, xmin, xmax, nodes, xtrap=0.0, waxes=None, real32=False, ldv=None, ldcoef=None, coef=None):
+    """The fit of samples on the tensor-product grid axes[0] x axes[1] x ... (splpak_fit_grid_*): what fit() returns for the
+    listed product with the weights prod_d waxes[d][i_d], provided that fit has no constraint rows (xtrap == 0, or no
+    data-sparse node: otherwise SplpakError from SPLPAK_E_UNSUPPORTED).  `axes` (and `waxes`, or None for all 1) are lists of
+    `ndim` 1-D arrays; `values` has the shape evaluate_grid returns, (n_ndim, ..., n_1), or (nfields,) + that shape, or is
+    flat with the fields `ldv` apart.  `coef`: an array to write into (fields `ldcoef` apart), else a new one.
+    -> (coef of shape (ncol,) or (nfields, ncol) -- flat of nfields*ldcoef when ldcoef is given --, ierror, info (nfields, 10))."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    npts, cat, wcat = _grid_axes(axes, waxes, dt)
+    nsamp = int(np.prod(npts)) if npts.size else 1
+    values = np.ascontiguousarray(values, dtype=dt)
+    if ldv is None:
+        single = values.size == nsamp and values.ndim <= max(len(axes), 1)
+        nfields = 1 if single else (values.size // nsamp if nsamp > 0 else 1)
+        ldv_ = nsamp
+    else:
+        single = False
+        ldv_ = int(ldv)
+        nfields = max((values.size + ldv_ - nsamp) // ldv_, 1) if ldv_ > 0 else 1
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64))) if nodes.size else 0
+    ldc = ncol if ldcoef is None else int(ldcoef)
+    if coef is None:
+        coef = np.zeros(max(nfields * ldc, 1), dtype=dt)
+    info = np.zeros((nfields, 10))
+    fn = lib().splpak_fit_grid_f32 if real32 else lib().splpak_fit_grid_f64
+    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, rp), _p(wcat, rp), nfields, _p(values, rp), ldv_, _p(xmin, rp),
+                   _p(xmax, rp), _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(info, _dp)))
+    if ldcoef is None and coef.size == nfields * ncol:
+        coef = coef[:ncol] if single else coef.reshape(nfields, ncol)
+    return coef, rc, info
+
+
+def fit_grid_dev(ndim, npts, axes, values, xmin, xmax, nodes, coef, xtrap=0.0, waxes=None, nfields=1, ldv=None, ldcoef=None,
+                 stream=0):
+    """fit_grid on torch device tensors: `axes` (and `waxes`, or None) hold the axes back to back, `values` the samples of
+    field k from k*ldv on (default prod npts), `coef` receives its coefficients from k*ldcoef on (default ncol).  `stream`
+    is synchronised (the axes come to the host; every refinement step).  float32 tensors take the REAL32 entry.
+    -> (ierror, info (nfields, 10))."""
+    npts = np.ascontiguousarray(npts, dtype=np.int64)
+    real32 = str(axes.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    info = np.zeros((int(nfields), 10))
+    fn = lib().splpak_fit_grid_dev_f32 if real32 else lib().splpak_fit_grid_dev_f64
+    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), axes.data_ptr(), None if waxes is None else waxes.data_ptr(), int(nfields),
+                   values.data_ptr(), int(np.prod(npts)) if ldv is None else int(ldv), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip),
+                   float(xtrap), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(info, _dp), C.c_void_p(stream)))
+    return rc, info
+
+
+def debug_fit_grid_stage(stage, ndim, axes, data, xmin, xmax, nodes, waxes=None):
+    """One stage of the grid fit alone (splpak_debug_fit_grid_stage_f64): stage 0 -> T[ncol], the spread of the samples
+    `data`; stage 1 -> C[ncol] from `data` = T, the solves alone.  -> (array of ncol, ierror)."""
+    npts, cat, wcat = _grid_axes(axes, waxes, np.float64)
+    data = np.ascontiguousarray(data, dtype=np.float64)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes)
+    out = np.zeros(int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64))))
+    rc = _check(lib().splpak_debug_fit_grid_stage_f64(int(stage), ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, _dp), _p(wcat, _dp),
+                                                      _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), _p(data, _dp), _p(out, _dp)))
+    return out, rc
+
+
+def debug_fit_grid_stats():
+    """Host counters of this thread's last fit_grid call: (slabs of a residual pass, doubles of residual scratch held, spread
+    launches, solve launches, refinement steps of the last field, 0, 0, 0)."""
+    v = np.zeros(8, dtype=np.int64)
+    _check(lib().splpak_debug_fit_grid_stats(_p(v, C.POINTER(C.c_int64))))
     return tuple(int(t) for t in v)
 
 

@@ -266,6 +266,7 @@ void splpak_shutdown(void)
     }
     eval_scratch_shutdown();
     eval_grid_scratch_shutdown();
+    fit_grid_scratch_shutdown();
 }
 
 }  // extern "C"

@@ -71,6 +71,9 @@ hipError_t launch_integrate_grid(const Grid &g, const int64_t *ncell, const int 
 // axis [2..5], reduction launches [6], 0 [7]
 void integrate_grid_stats(long long out8[8]);
 
+// ---- fitgrid.hip (the fit of samples on a tensor-product grid of points: fitgrid.hpp)
+void fit_grid_scratch_shutdown();
+
 // ---- synth.hip
 hipError_t launch_synth_points(int ndim, long long first, long long n, double *x, double *y,
                                double *w, hipStream_t st);

@@ -19,6 +19,9 @@ const Known KNOWN[] = {
     {"SPLPAK_DEBUG_SUMS", 0},
     {"SPLPAK_DEBUG_TWOEND", 0},
     {"SPLPAK_DIST_CHUNK", 0},
+    {"SPLPAK_FIT_GRID_NODE_BLOCK", 0},
+    {"SPLPAK_FIT_GRID_REFINE", 1},
+    {"SPLPAK_FIT_GRID_SCRATCH_MB", 1},
     {"SPLPAK_GRAM_SCRATCH_MB", 1},
     {"SPLPAK_GRAM_VALU", 0},
     {"SPLPAK_INTEGRATE_SCRATCH_MB", 1},

@@ -71,6 +71,7 @@ module splpak_module
     contains
         private
         generic,public   :: initialize    => splcc, splcw        !! fit
+        procedure,public :: initialize_grid => splpak_fit_grid      !! fit of samples on a tensor-product grid of points (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
@@ -172,6 +173,19 @@ module splpak_module
             integer(c_int32_t),value :: ndim
             type(c_ptr),value :: ncell, mode, axes, coef, xmin, xmax, nodes, out
         end function c_integrate_grid
+#ifdef REAL32
+        integer(c_int32_t) function c_fit_grid(ndim,npts,axes,waxes,nfields,values,ldv,xmin,xmax,nodes,xtrap,coef,ldcoef,info) &
+                                               bind(C,name='splpak_fit_grid_f32')
+#else
+        integer(c_int32_t) function c_fit_grid(ndim,npts,axes,waxes,nfields,values,ldv,xmin,xmax,nodes,xtrap,coef,ldcoef,info) &
+                                               bind(C,name='splpak_fit_grid_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr, wp
+            integer(c_int32_t),value :: ndim, nfields
+            integer(c_int64_t),value :: ldv, ldcoef
+            type(c_ptr),value :: npts, axes, waxes, values, xmin, xmax, nodes, coef, info
+            real(wp),value :: xtrap
+        end function c_fit_grid
 #ifdef REAL32
         integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
                                                   bind(C,name='splpak_eval_fields_f32')
@@ -478,6 +492,108 @@ module splpak_module
         end if
 #endif
     end subroutine fit_common
+
+    !> The fit of samples given on a tensor-product grid of points -- an image, a volume, a table: `values` holds one sample
+    !! per point of axes_1 x axes_2 x ..., dimension 1 fastest (what `evaluate_grid` writes), `axes` the npts(idim) coordinates
+    !! of every dimension back to back (any order, repeats and points outside the box allowed), the optional `waxes` one weight
+    !! per axis coordinate in the same layout (the weight of a sample is the product of its coordinates' weights; absent: 1).
+    !! Returns what `initialize` returns for the listed product, provided that fit has no constraint rows: xtrap = 0, or
+    !! xtrap /= 0 and no data-sparse node (include/splpak_hip.h, splpak_fit_grid_f64; otherwise ierror = -4 with the library's
+    !! message: list the points and call `initialize`).  One call of the HIP library: one streaming pass over the samples per
+    !! refinement step and ndim small band solves, no sort and no factorisation of the full normal equations.  Under
+    !! set_host(.true.), for ndim > 4, in the -DREAL128 build and with SPLPAK_HOST_IF_NO_GPU=1 the product is listed and the
+    !! module's host solver fits it (constraint rows included, as `initialize`).  Leaves the object as `initialize` does --
+    !! `evaluate*` follow --, except that there is nothing to `refit`.
+    !! ierror: 0; 101 .. 105 and 107 as `initialize` (104: ncf smaller than the number of coefficients; 105: an npts(idim) < 1).
+    subroutine splpak_fit_grid(me,ndim,npts,axes,values,xmin,xmax,nodes,xtrap,coef,ncf,ierror,waxes)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, ncf
+        integer,intent(in) :: npts(*)
+        real(wp),intent(in),target :: axes(*)
+        real(wp),intent(in),target :: values(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(in) :: xtrap
+        real(wp),intent(out),target :: coef(*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: waxes(*)
+        integer(c_int32_t) :: rc
+        integer(c_int64_t),target :: np64(max(ndim,1))
+        integer(c_int64_t) :: nsamp, ip
+        integer :: idim, ntab, k(max(ndim,1)), off(max(ndim,1))
+        logical :: listed
+        real(wp),allocatable,target :: xl(:,:), wl(:)
+        real(wp),target :: wk(1)
+        type(c_ptr) :: pw
+        me%mdim = ndim
+        me%token = 0                          ! (whatever this object could refit is being replaced)
+        me%fit_fell_to_host = .false.
+        np64 = 0
+        nsamp = 1
+        ntab = 0
+        do idim = 1, ndim
+            np64(idim) = int(npts(idim),c_int64_t)
+            off(idim) = ntab
+            ntab = ntab + max(npts(idim),0)
+            nsamp = nsamp*max(np64(idim),0_c_int64_t)
+        end do
+        rc = -1
+        listed = host_takes(me,ndim)
+#ifndef REAL128
+        if (.not. listed) then
+            pw = c_null_ptr
+            if (present(waxes)) pw = c_loc(waxes)
+            rc = c_fit_grid(int(ndim,c_int32_t), c_loc(np64), c_loc(axes), pw, 1_c_int32_t, c_loc(values), nsamp, c_loc(xmin), &
+                            c_loc(xmax), c_loc(nodes), xtrap, c_loc(coef), int(ncf,c_int64_t), c_loc(me%info))
+            if (host_if_no_gpu(int(rc))) then
+                listed = .true.
+                me%fit_fell_to_host = .true.
+            end if
+        end if
+#endif
+        if (listed) then                      ! the host solver on the listed product, first dimension fastest
+            ierror = 0
+            do idim = 1, ndim
+                if (npts(idim) < 1) nsamp = 0
+            end do
+            allocate(xl(max(ndim,1),max(nsamp,1_c_int64_t)), wl(max(nsamp,1_c_int64_t)))
+            k = 1
+            do ip = 1, nsamp
+                wl(ip) = 1.0_wp
+                do idim = 1, ndim
+                    xl(idim,ip) = axes(off(idim) + k(idim))
+                    if (present(waxes)) wl(ip) = wl(ip)*waxes(off(idim) + k(idim))
+                end do
+                idim = 1
+                do while (idim <= ndim)
+                    k(idim) = k(idim) + 1
+                    if (k(idim) <= npts(idim)) exit
+                    k(idim) = 1
+                    idim = idim + 1
+                end do
+            end do
+            ! (a weight list whose first entry is negative would read as "no weights": the grid entry has no such sentinel)
+            pw = c_null_ptr
+            if (present(waxes) .and. nsamp >= 1) then
+                if (wl(1) >= 0.0_wp) then
+                    pw = c_loc(wl)
+                else
+                    ierror = -4
+                    call report(ierror,' initialize_grid - a negative weight cannot be listed for the host solver')
+                    return
+                end if
+            end if
+            call fit_on_host(me,ndim,c_loc(xl),max(ndim,1),c_loc(values),pw,int(nsamp),c_loc(xmin),c_loc(xmax),nodes,xtrap, &
+                             coef,ncf,wk,1,ierror)
+            return
+        end if
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'initialize_grid')
+        end if
+    end subroutine splpak_fit_grid
 
     !> New values on the points of this object's last `initialize`: several fields sampled at the same points (the
     !! components of a velocity, a time series on a fixed sensor layout, bootstrap replicas) cost one `initialize` and one
