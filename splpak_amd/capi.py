@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("SPLPAK_LIB") or os.path.join(_HERE, "libsplpak_hip.so
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -94,7 +95,7 @@ def lib() -> C.CDLL:
     L.splpak_plan_refit_dev.restype = i32
     L.splpak_plan_refit_dev.argtypes = [vp, i32, vp, i64, vp, i64, vp, _dp]
     L.splpak_debug_plan_refit_stats.restype = i32
-    L.splpak_debug_plan_refit_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.splpak_debug_plan_refit_stats.argtypes = [vp, _lp]
     L.splpak_eval_f64.restype = i32
     L.splpak_eval_f64.argtypes = [i32, i64, _dp, i32, _ip, _dp, _dp, _dp, _ip, _dp]
     L.splpak_eval_f32.restype = i32
@@ -145,7 +146,6 @@ def lib() -> C.CDLL:
     L.splpak_eval_derivs_f32.argtypes = [i32, i64, _fp, i32, i32, _fp, _fp, _fp, _ip, _fp, i32]
     L.splpak_eval_derivs_dev_f64.restype = i32
     L.splpak_eval_derivs_dev_f64.argtypes = [i32, i64, vp, i32, i32, vp, _dp, _dp, _ip, vp, i32, vp]
-    _lp = C.POINTER(C.c_int64)
     L.splpak_eval_grid_f64.restype = i32
     L.splpak_eval_grid_f64.argtypes = [i32, _lp, _dp, _ip, _dp, _dp, _dp, _ip, _dp]
     L.splpak_eval_grid_f32.restype = i32
@@ -463,21 +463,26 @@ def evaluate(ndim, xq, nderiv, coef, xmin, xmax, nodes, real32=False):
     return out, rc
 
 
+def _axes_cat(axes, dt):
+    """(entries per axis as int64, the axes back to back) of a list of 1-D arrays."""
+    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
+    sizes = np.array([a.size for a in axes], dtype=np.int64)
+    return sizes, (np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt))
+
+
 def evaluate_grid(ndim, axes, nderiv, coef, xmin, xmax, nodes, real32=False):
     """splde (nderiv given) / splfe (nderiv None) at every point of the tensor-product grid axes[0] x axes[1] x ...
     `axes` is a list of `ndim` 1-D arrays (any order, repeats and points outside the grid allowed).
     -> (values of shape (len(axes[ndim-1]), ..., len(axes[0])), C-ordered: the LAST index runs along dimension 1; ierror)."""
     dt = np.float32 if real32 else np.float64
     rp = _fp if real32 else _dp
-    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
-    npts = np.array([a.size for a in axes], dtype=np.int64)
-    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    npts, cat = _axes_cat(axes, dt)
     coef = np.ascontiguousarray(coef, dtype=dt)
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
     nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
     out = np.zeros(tuple(int(n) for n in npts[::-1]), dtype=dt)
     fn = lib().splpak_eval_grid_f32 if real32 else lib().splpak_eval_grid_f64
-    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, rp), _p(nd, _ip), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
+    rc = _check(fn(ndim, _p(npts, _lp), _p(cat, rp), _p(nd, _ip), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
                    _p(nodes, _ip), _p(out, rp)))
     return out, rc
 
@@ -485,13 +490,13 @@ def evaluate_grid(ndim, axes, nderiv, coef, xmin, xmax, nodes, real32=False):
 def eval_grid_scratch_bytes(npts) -> int:
     """Bytes of per-thread device scratch a grid call of this shape keeps until shutdown()."""
     npts = np.ascontiguousarray(npts, dtype=np.int64)
-    return _check(lib().splpak_eval_grid_scratch_bytes(int(npts.size), _p(npts, C.POINTER(C.c_int64))))
+    return _check(lib().splpak_eval_grid_scratch_bytes(int(npts.size), _p(npts, _lp)))
 
 
 def debug_eval_grid_stats():
     """(tiles that took the LDS form, tiles that took the general form) in this thread's last grid call; waits for it."""
     v = np.zeros(2, dtype=np.int64)
-    _check(lib().splpak_debug_eval_grid_stats(_p(v, C.POINTER(C.c_int64))))
+    _check(lib().splpak_debug_eval_grid_stats(_p(v, _lp)))
     return int(v[0]), int(v[1])
 
 
@@ -501,14 +506,12 @@ def evaluate_grid_derivs(ndim, axes, order, coef, xmin, xmax, nodes, real32=Fals
     evaluate_derivs, each plane a volume as evaluate_grid returns it; ierror)."""
     dt = np.float32 if real32 else np.float64
     rp = _fp if real32 else _dp
-    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
-    npts = np.array([a.size for a in axes], dtype=np.int64)
-    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    npts, cat = _axes_cat(axes, dt)
     coef = np.ascontiguousarray(coef, dtype=dt)
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
     out = np.zeros((derivs_nout(max(int(ndim), 0), order),) + tuple(int(n) for n in npts[::-1]), dtype=dt)
     fn = lib().splpak_eval_grid_derivs_f32 if real32 else lib().splpak_eval_grid_derivs_f64
-    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, rp), int(order), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
+    rc = _check(fn(ndim, _p(npts, _lp), _p(cat, rp), int(order), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
                    _p(nodes, _ip), _p(out, rp), int(np.prod(npts)) if npts.size else 1))
     return out, rc
 
@@ -516,7 +519,7 @@ def evaluate_grid_derivs(ndim, axes, order, coef, xmin, xmax, nodes, real32=Fals
 def eval_grid_derivs_scratch_bytes(npts, order) -> int:
     """Bytes of per-thread device scratch a grid-derivatives call of this shape keeps until shutdown()."""
     npts = np.ascontiguousarray(npts, dtype=np.int64)
-    return _check(lib().splpak_eval_grid_derivs_scratch_bytes(int(npts.size), _p(npts, C.POINTER(C.c_int64)), int(order)))
+    return _check(lib().splpak_eval_grid_derivs_scratch_bytes(int(npts.size), _p(npts, _lp), int(order)))
 
 
 def debug_eval_grid_derivs_tile(ndim, order):
@@ -533,15 +536,14 @@ def integrate_grid(ndim, axes, mode, coef, xmin, xmax, nodes, real32=False):
     -> (values of shape (n_ndim, ..., n_1), C-ordered as evaluate_grid returns its own; ierror)."""
     dt = np.float32 if real32 else np.float64
     rp = _fp if real32 else _dp
-    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
+    sizes, cat = _axes_cat(axes, dt)
     md = None if mode is None else np.ascontiguousarray(mode, dtype=np.int32)
-    ncell = np.array([a.size - (1 if md is None else int(md[d] == 1)) for d, a in enumerate(axes)], dtype=np.int64)
-    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    ncell = np.array([n - (1 if md is None else int(md[d] == 1)) for d, n in enumerate(sizes)], dtype=np.int64)
     coef = np.ascontiguousarray(coef, dtype=dt)
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
     out = np.zeros(tuple(max(int(n), 0) for n in ncell[::-1]), dtype=dt)
     fn = lib().splpak_integrate_grid_f32 if real32 else lib().splpak_integrate_grid_f64
-    rc = _check(fn(ndim, _p(ncell, C.POINTER(C.c_int64)), _p(md, _ip), _p(cat, rp), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
+    rc = _check(fn(ndim, _p(ncell, _lp), _p(md, _ip), _p(cat, rp), _p(coef, rp), _p(xmin, rp), _p(xmax, rp),
                    _p(nodes, _ip), _p(out, rp)))
     return out, rc
 
@@ -550,21 +552,18 @@ def debug_integrate_grid_stats():
     """Host counters of this thread's last integrate_grid call: (slabs, doubles of intermediate held, table entries of the four
     axes, reduction launches, 0)."""
     v = np.zeros(8, dtype=np.int64)
-    _check(lib().splpak_debug_integrate_grid_stats(_p(v, C.POINTER(C.c_int64))))
+    _check(lib().splpak_debug_integrate_grid_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)
 
 
 def _grid_axes(axes, waxes, dt):
     """(npts, the axes back to back, the weights back to back or None) of a list of 1-D arrays."""
-    axes = [np.ascontiguousarray(a, dtype=dt).ravel() for a in axes]
-    npts = np.array([a.size for a in axes], dtype=np.int64)
-    cat = np.ascontiguousarray(np.concatenate(axes)) if axes else np.zeros(0, dtype=dt)
+    npts, cat = _axes_cat(axes, dt)
     wcat = None
     if waxes is not None:
-        waxes = [np.ascontiguousarray(w, dtype=dt).ravel() for w in waxes]
-        if [w.size for w in waxes] != [a.size for a in axes]:
+        wsizes, wcat = _axes_cat(waxes, dt)
+        if wsizes.tolist() != npts.tolist():
             raise SplpakError("fit_grid: waxes must hold one weight per axis coordinate")
-        wcat = np.ascontiguousarray(np.concatenate(waxes)) if waxes else np.zeros(0, dtype=dt)
     return npts, cat, wcat
 
 
@@ -595,7 +594,7 @@ def fit_grid(ndim, axes, values, xmin, xmax, nodes, xtrap=0.0, waxes=None, real3
         coef = np.zeros(max(nfields * ldc, 1), dtype=dt)
     info = np.zeros((nfields, 10))
     fn = lib().splpak_fit_grid_f32 if real32 else lib().splpak_fit_grid_f64
-    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, rp), _p(wcat, rp), nfields, _p(values, rp), ldv_, _p(xmin, rp),
+    rc = _check(fn(ndim, _p(npts, _lp), _p(cat, rp), _p(wcat, rp), nfields, _p(values, rp), ldv_, _p(xmin, rp),
                    _p(xmax, rp), _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(info, _dp)))
     if ldcoef is None and coef.size == nfields * ncol:
         coef = coef[:ncol] if single else coef.reshape(nfields, ncol)
@@ -615,7 +614,7 @@ def fit_grid_dev(ndim, npts, axes, values, xmin, xmax, nodes, coef, xtrap=0.0, w
     ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
     info = np.zeros((int(nfields), 10))
     fn = lib().splpak_fit_grid_dev_f32 if real32 else lib().splpak_fit_grid_dev_f64
-    rc = _check(fn(ndim, _p(npts, C.POINTER(C.c_int64)), axes.data_ptr(), None if waxes is None else waxes.data_ptr(), int(nfields),
+    rc = _check(fn(ndim, _p(npts, _lp), axes.data_ptr(), None if waxes is None else waxes.data_ptr(), int(nfields),
                    values.data_ptr(), int(np.prod(npts)) if ldv is None else int(ldv), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip),
                    float(xtrap), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(info, _dp), C.c_void_p(stream)))
     return rc, info
@@ -628,7 +627,7 @@ def debug_fit_grid_stage(stage, ndim, axes, data, xmin, xmax, nodes, waxes=None)
     data = np.ascontiguousarray(data, dtype=np.float64)
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes)
     out = np.zeros(int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64))))
-    rc = _check(lib().splpak_debug_fit_grid_stage_f64(int(stage), ndim, _p(npts, C.POINTER(C.c_int64)), _p(cat, _dp), _p(wcat, _dp),
+    rc = _check(lib().splpak_debug_fit_grid_stage_f64(int(stage), ndim, _p(npts, _lp), _p(cat, _dp), _p(wcat, _dp),
                                                       _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), _p(data, _dp), _p(out, _dp)))
     return out, rc
 
@@ -637,7 +636,7 @@ def debug_fit_grid_stats():
     """Host counters of this thread's last fit_grid call: (slabs of a residual pass, doubles of residual scratch held, spread
     launches, solve launches, refinement steps of the last field, 0, 0, 0)."""
     v = np.zeros(8, dtype=np.int64)
-    _check(lib().splpak_debug_fit_grid_stats(_p(v, C.POINTER(C.c_int64))))
+    _check(lib().splpak_debug_fit_grid_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)
 
 
@@ -670,7 +669,7 @@ def debug_eval_fields_stats():
     """(route, place passes, evaluation kernels) of this thread's last fields call -- route: 0 none yet, 1 the direct fields
     kernel, 2 the shared sort, 3 one single-field evaluation per field.  Host-side counters: nothing is waited for."""
     v = np.zeros(3, dtype=np.int64)
-    _check(lib().splpak_debug_eval_fields_stats(_p(v, C.POINTER(C.c_int64))))
+    _check(lib().splpak_debug_eval_fields_stats(_p(v, _lp)))
     return int(v[0]), int(v[1]), int(v[2])
 
 
@@ -982,14 +981,13 @@ def evaluate_grid_dev(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, st
     npts[::-1]).  float32 tensors take the REAL32 entry."""
     nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
     npts = np.ascontiguousarray(npts, dtype=np.int64)
-    lp = C.POINTER(C.c_int64)
     if str(axes.dtype).endswith("float32"):
         xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32)
-        return _check(lib().splpak_eval_grid_dev_f32(ndim, _p(npts, lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
+        return _check(lib().splpak_eval_grid_dev_f32(ndim, _p(npts, _lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
                                                      _p(xmin, _fp), _p(xmax, _fp), _p(nodes, _ip), out.data_ptr(),
                                                      C.c_void_p(stream)))
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes)
-    return _check(lib().splpak_eval_grid_dev_f64(ndim, _p(npts, lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
+    return _check(lib().splpak_eval_grid_dev_f64(ndim, _p(npts, _lp), axes.data_ptr(), _p(nd, _ip), coef.data_ptr(),
                                                  _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), out.data_ptr(),
                                                  C.c_void_p(stream)))
 
@@ -1004,7 +1002,7 @@ def integrate_grid_dev(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out, st
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
     fn = lib().splpak_integrate_grid_dev_f32 if real32 else lib().splpak_integrate_grid_dev_f64
     rp = _fp if real32 else _dp
-    return _check(fn(ndim, _p(ncell, C.POINTER(C.c_int64)), _p(md, _ip), axes.data_ptr(), coef.data_ptr(), _p(xmin, rp), _p(xmax, rp),
+    return _check(fn(ndim, _p(ncell, _lp), _p(md, _ip), axes.data_ptr(), coef.data_ptr(), _p(xmin, rp), _p(xmax, rp),
                      _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
 
 
@@ -1013,7 +1011,6 @@ def evaluate_grid_derivs_dev(ndim, npts, axes, order, coef, xmin, xmax, nodes, o
     evaluate_grid_dev; `out` is a 2-D tensor (nplanes, >= prod(npts)) with unit stride inside a row, its row stride is passed
     as ldout.  float32 tensors take the REAL32 entry."""
     npts = np.ascontiguousarray(npts, dtype=np.int64)
-    lp = C.POINTER(C.c_int64)
     if out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
         raise SplpakError("evaluate_grid_derivs_dev: out must be 2-D (planes, points) with contiguous planes")
     if order in (1, 2) and int(out.shape[0]) < derivs_nout(max(int(ndim), 0), order):
@@ -1023,7 +1020,7 @@ def evaluate_grid_derivs_dev(ndim, npts, axes, order, coef, xmin, xmax, nodes, o
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
     fn = lib().splpak_eval_grid_derivs_dev_f32 if real32 else lib().splpak_eval_grid_derivs_dev_f64
     rp = _fp if real32 else _dp
-    return _check(fn(ndim, _p(npts, lp), axes.data_ptr(), int(order), coef.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip),
+    return _check(fn(ndim, _p(npts, _lp), axes.data_ptr(), int(order), coef.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip),
                      out.data_ptr(), ldo, C.c_void_p(stream)))
 
 

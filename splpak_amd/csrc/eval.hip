@@ -33,21 +33,10 @@ eval_kernel(Grid g, long long nq, const T *__restrict__ xq, int ldxq, NDeriv nd,
             const int ws = eval_table<VAL>(g, d, x, nd.v[d], b[d]);
             base += ws * g.colstride[d];
         }
-        // The 4 coefficients of a window row are contiguous: two 16-byte loads instead of four
-        // 8-byte ones (the kernel is bound by gather instructions / L2 lines, not bytes).
         const int s1 = D > 1 ? g.colstride[1] : 0, s2 = D > 2 ? g.colstride[2] : 0, s3 = D > 3 ? g.colstride[3] : 0;
         const double sum = window_sum<D>(b, [&](int k1, int k2, int k3, double (&c)[4]) {
             const long long idx = base + k1 * s1 + k2 * s2 + k3 * s3;
-            if constexpr (sizeof(T) == 8) {
-                typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
-                const d2v lo = *reinterpret_cast<const d2v *>(coef + idx);
-                const d2v hi = *reinterpret_cast<const d2v *>(coef + idx + 2);
-                c[0] = lo[0]; c[1] = lo[1]; c[2] = hi[0]; c[3] = hi[1];
-            } else {
-                typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
-                const f4v v = *reinterpret_cast<const f4v *>(coef + idx);
-                c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
-            }
+            load_window_row(coef + idx, c);
         });
         out[i] = (T)sum;
     }
@@ -78,16 +67,7 @@ eval_fields_kernel(Grid g, long long nq, const T *__restrict__ xq, int ldxq, NDe
         auto field = [&](const T *__restrict__ cf) {
             return window_sum<D>(b, [&](int k1, int k2, int k3, double (&c)[4]) {
                 const long long idx = base + k1 * s1 + k2 * s2 + k3 * s3;
-                if constexpr (sizeof(T) == 8) {
-                    typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
-                    const d2v lo = *reinterpret_cast<const d2v *>(cf + idx);
-                    const d2v hi = *reinterpret_cast<const d2v *>(cf + idx + 2);
-                    c[0] = lo[0]; c[1] = lo[1]; c[2] = hi[0]; c[3] = hi[1];
-                } else {
-                    typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
-                    const f4v v = *reinterpret_cast<const f4v *>(cf + idx);
-                    c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
-                }
+                load_window_row(cf + idx, c);
             });
         };
         int k = 0;

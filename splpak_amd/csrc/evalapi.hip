@@ -2,7 +2,10 @@
 // pointers, the evaluation mode, and the host-only / synthetic-data helpers that need no plan.
 //
 // Every entry family has ONE ladder of argument checks (point_validate for the value and the derivative entries,
-// fields_validate, grid_validate, integrate_validate, grid_derivs_validate), one device form and one host form that stages its arrays through the device; the extern "C" functions forward to them.
+// fields_validate, grid_validate, integrate_validate, grid_derivs_validate), one device form and one host form that stages its
+// arrays through the device (staged_call: one block of results or several, a stride apart); the extern "C" functions forward
+// to them.  The three grid ladders share their opening and close (grid_open, grid_close: GridCheck) and differ in the middle;
+// what a failed ladder zeroes is zeroed by zero_results.
 // Where two entries of a family have always answered differently, the difference is a named parameter of the ladder.
 #include "plan.hpp"
 #include "basis.hpp"
@@ -46,21 +49,42 @@ struct DevStage {
     }
 };
 
-// A host entry after its checks: in (n_in) and coef (ncol) go to the device, launch(in, coef, out) runs on the null stream,
-// out (n_out; cleared first when `clear`) comes back.  rc = the status to return when all of that went well.
-template <typename T, typename F>
-static int32_t staged_call(const T *in, size_t n_in, const T *coef, size_t ncol, T *out, size_t n_out, bool clear, const char *what,
-                           int rc, F &&launch)
+// A host entry after its checks: in (n_in) and coef (ncol) go to the device, launch(in, coef, out) runs on the null stream and
+// leaves nplanes blocks of n results back to back (cleared first when `clear`); block k comes back to out + k * ldout, so that
+// the caller's words between the blocks keep their contents.  status(e) turns what the copies and the launch returned into
+// the entry's status (staged_status: rc when all went well); a staging buffer that cannot be had is SPLPAK_E_NOMEM.
+template <typename T, typename F, typename S>
+static int32_t staged_call(const T *in, size_t n_in, const T *coef, size_t ncol, T *out, size_t n, int nplanes, long long ldout, bool clear,
+                           F &&launch, S &&status)
 {
     DevStage stage;
     T *din = nullptr, *dc = nullptr, *dout = nullptr;
-    if (!stage.alloc(&din, n_in) || !stage.alloc(&dc, ncol) || !stage.alloc(&dout, n_out)) return SPLPAK_E_NOMEM;
+    if (!stage.alloc(&din, n_in) || !stage.alloc(&dc, ncol) || !stage.alloc(&dout, n * (size_t)nplanes)) return SPLPAK_E_NOMEM;
     hipError_t e = hipMemcpy(din, in, sizeof(T) * n_in, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * ncol, hipMemcpyHostToDevice);
-    if (e == hipSuccess && clear) e = hipMemset(dout, 0, sizeof(T) * n_out);
+    if (e == hipSuccess && clear) e = hipMemset(dout, 0, sizeof(T) * n * (size_t)nplanes);
     if (e == hipSuccess) e = launch((const T *)din, (const T *)dc, dout);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(T) * n_out, hipMemcpyDeviceToHost);
-    return hip_ok(e, what) ? rc : SPLPAK_E_NODEVICE;
+    for (int k = 0; k < nplanes && e == hipSuccess; ++k)
+        e = hipMemcpy(out + (long long)k * ldout, dout + (size_t)k * n, sizeof(T) * n, hipMemcpyDeviceToHost);
+    return status(e);
+}
+
+static auto staged_status(const char *what, int rc)
+{
+    return [=](hipError_t e) -> int32_t { return hip_ok(e, what) ? rc : SPLPAK_E_NODEVICE; };
+}
+
+// The results a failed ladder zeroes (101 / 102 / 103) before its entry returns: n in each of nplanes blocks ld apart, on the
+// host or, `dev`, by memsets queued on st.
+template <typename T>
+static void zero_results(T *out, long long n, int nplanes, long long ld, bool dev, hipStream_t st)
+{
+    if (!out || n <= 0) return;
+    for (int k = 0; k < nplanes; ++k) {
+        T *p = out + (long long)k * ld;
+        if (dev) (void)hipMemsetAsync(p, 0, sizeof(T) * (size_t)n, st);
+        else for (long long i = 0; i < n; ++i) p[i] = (T)0;
+    }
 }
 
 // the grid arguments every ladder starts with: the null checks, ndim in 1 .. MAXD, the limits widened to double.
@@ -139,11 +163,12 @@ static int32_t eval_host(bool derivs, int32_t ndim, int64_t nq, const T *xq, int
         if (out) for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
         return rc;
     }
-    return staged_call<T>(xq, (size_t)nq * ldxq, coef, (size_t)g.ncol, out, (size_t)nq * ldout, derivs, "evaluation", rc,
+    return staged_call<T>(xq, (size_t)nq * ldxq, coef, (size_t)g.ncol, out, (size_t)nq * ldout, 1, 0, derivs,
                           [&](const T *dq, const T *dc, T *dout) {
                               return !derivs ? launch_eval<T>(g, nq, dq, ldxq, nderiv, dc, dout, nullptr)
                                                 : launch_eval_derivs<T>(g, nq, dq, ldxq, order, dc, dout, ldout, nullptr);
-                          });
+                          },
+                          staged_status("evaluation", rc));
 }
 
 extern "C" {
@@ -229,8 +254,7 @@ static int32_t eval_fields_dev(int32_t ndim, int64_t nq, const T *xq_dev, int32_
     int rc = 0;
     bool zero = false;
     if (!fields_validate(ndim, nq, xq_dev, ldxq, nderiv, nfields, coef_dev, ldcoef, xmin, xmax, nodes, out_dev, ldout, g, rc, zero)) {
-        if (zero && out_dev && nq > 0)
-            for (int32_t k = 0; k < nfields; ++k) (void)hipMemsetAsync(out_dev + (long long)k * ldout, 0, sizeof(T) * (size_t)nq, (hipStream_t)stream);
+        if (zero) zero_results(out_dev, nq, nfields, ldout, true, (hipStream_t)stream);
         return rc;
     }
     SPLPAK_HIP_TRY(launch_eval_fields<T>(g, nq, xq_dev, ldxq, nderiv, nfields, coef_dev, ldcoef, out_dev, ldout, (hipStream_t)stream),
@@ -238,8 +262,8 @@ static int32_t eval_fields_dev(int32_t ndim, int64_t nq, const T *xq_dev, int32_
     return rc;
 }
 
-// the host form stages through the device as staged_call does: the coefficients of all fields with the caller's ldcoef in one
-// copy, the results packed (nq apart) and copied back field by field, so that the caller's words between the fields keep their contents
+// the host form: the coefficients of all fields go to the device with the caller's ldcoef in one copy, the results are packed
+// there (nq apart) and come back field by field
 template <typename T>
 static int32_t eval_fields_host(int32_t ndim, int64_t nq, const T *xq, int32_t ldxq, const int32_t *nderiv, int32_t nfields, const T *coef,
                                 int64_t ldcoef, const T *xmin, const T *xmax, const int32_t *nodes, T *out, int64_t ldout)
@@ -248,21 +272,15 @@ static int32_t eval_fields_host(int32_t ndim, int64_t nq, const T *xq, int32_t l
     int rc = 0;
     bool zero = false;
     if (!fields_validate(ndim, nq, xq, ldxq, nderiv, nfields, coef, ldcoef, xmin, xmax, nodes, out, ldout, g, rc, zero)) {
-        if (zero && out)
-            for (int32_t k = 0; k < nfields; ++k)
-                for (int64_t i = 0; i < nq; ++i) out[(long long)k * ldout + i] = (T)0;
+        if (zero) zero_results(out, nq, nfields, ldout, false, nullptr);
         return rc;
     }
-    const size_t n_in = (size_t)nq * ldxq, n_coef = (size_t)(nfields - 1) * (size_t)ldcoef + (size_t)g.ncol, n_out = (size_t)nfields * (size_t)nq;
-    DevStage stage;
-    T *din = nullptr, *dc = nullptr, *dout = nullptr;
-    if (!stage.alloc(&din, n_in) || !stage.alloc(&dc, n_coef) || !stage.alloc(&dout, n_out)) return SPLPAK_E_NOMEM;
-    hipError_t e = hipMemcpy(din, xq, sizeof(T) * n_in, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * n_coef, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_eval_fields<T>(g, nq, din, ldxq, nderiv, nfields, dc, ldcoef, dout, nq, nullptr);
-    for (int32_t k = 0; k < nfields && e == hipSuccess; ++k)
-        e = hipMemcpy(out + (long long)k * ldout, dout + (long long)k * nq, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost);
-    return hip_ok(e, "evaluation of several fields") ? rc : SPLPAK_E_NODEVICE;
+    const size_t n_coef = (size_t)(nfields - 1) * (size_t)ldcoef + (size_t)g.ncol;
+    return staged_call<T>(xq, (size_t)nq * ldxq, coef, n_coef, out, (size_t)nq, nfields, ldout, false,
+                          [&](const T *dq, const T *dc, T *dout) {
+                              return launch_eval_fields<T>(g, nq, dq, ldxq, nderiv, nfields, dc, ldcoef, dout, nq, nullptr);
+                          },
+                          staged_status("evaluation of several fields", rc));
 }
 
 extern "C" {
@@ -325,66 +343,80 @@ static bool grid_counts(int32_t ndim, const int64_t *npts, long long &nout, long
     return true;
 }
 
-// The checks every grid entry makes before it touches a device, in the order of eval_host / splpak_eval_dev_f64.
-// Returns true when the caller goes on to compute (rc = 0 or 104); otherwise rc is the status to return and
-// zero_n the outputs to zero first (101: the empty product, one output; 102 / 103: all of them).
+// What the ladder of a grid family (grid_validate, integrate_validate, grid_derivs_validate) leaves to its entries.  Every
+// ladder is grid_open, the family's own checks, grid_close, in the order of eval_host / splpak_eval_dev_f64.
+struct GridCheck {
+    Grid g;
+    double xmin[MAXD], xmax[MAXD];
+    long long nout = 0;         // results (of one plane)
+    long long ntab = 0;         // axis entries
+    int rc = 0;                 // the status to return when the ladder ends the call; 0 or 104 when the entry goes on to compute
+    long long zero_n = 0;       // results to zero first (101: the empty product, one output; 102 / 103: all of them) ..
+    int zero_planes = 1;        // .. in that many planes
+};
+
+// The opening: the null checks, ndim, the limits widened, the counts.  bad_counts: the family's text for a negative count
+// or a product beyond int64.
+template <typename T>
+static bool grid_open(int32_t ndim, const int64_t *counts, const T *xmin_t, const T *xmax_t, const int32_t *nodes, const T *out,
+                      const char *bad_counts, GridCheck &c)
+{
+    if (!counts) { set_error("null argument"); c.rc = SPLPAK_E_BADARG; return false; }
+    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, c.xmin, c.xmax, c.rc, c.zero_n)) return false;
+    if (!grid_counts(ndim, counts, c.nout, c.ntab)) { set_error(bad_counts); c.rc = SPLPAK_E_BADARG; return false; }
+    return true;
+}
+
+// The close: 102 / 103 (the results of all `planes` planes are zeroed) and 104 (which does not end the ladder), the empty
+// product, the data pointers, the device.  True: the entry goes on to compute.
+template <typename T>
+static bool grid_close(int32_t ndim, const int32_t *nderiv, const int32_t *nodes, const T *axes, const T *coef, const T *out, int planes,
+                       GridCheck &c)
+{
+    c.rc = eval_validate(ndim, nderiv, c.xmin, c.xmax, nodes, c.g);
+    if (c.rc != 0 && c.rc != 104) {
+        if (c.rc > 0 && out) { c.zero_n = c.nout; c.zero_planes = planes; }
+        return false;
+    }
+    if (c.nout == 0) return false;
+    if (!axes || !coef || !out) { set_error("null argument"); c.rc = SPLPAK_E_BADARG; return false; }
+    if (int r = device_ready()) { c.rc = r; return false; }
+    return true;
+}
+
 template <typename T>
 static bool grid_validate(int32_t ndim, const int64_t *npts, const T *axes, const int32_t *nderiv, const T *coef,
-                          const T *xmin_t, const T *xmax_t, const int32_t *nodes, const T *out, Grid &g, long long &nout,
-                          int &rc, long long &zero_n)
+                          const T *xmin, const T *xmax, const int32_t *nodes, const T *out, GridCheck &c)
 {
-    nout = 0;
-    zero_n = 0;
-    if (!npts) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    double xmin[MAXD], xmax[MAXD];
-    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, xmin, xmax, rc, zero_n)) return false;
-    long long ntab = 0;
-    if (!grid_counts(ndim, npts, nout, ntab)) {
-        set_error("negative npts, or an output count beyond int64");
-        rc = SPLPAK_E_BADARG;
-        return false;
-    }
-    rc = eval_validate(ndim, nderiv, xmin, xmax, nodes, g);
-    if (rc != 0 && rc != 104) {
-        if (rc > 0 && out) zero_n = nout;
-        return false;
-    }
-    if (nout == 0) return false;
-    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    if (int r = device_ready()) { rc = r; return false; }
-    return true;
+    return grid_open(ndim, npts, xmin, xmax, nodes, out, "negative npts, or an output count beyond int64", c) &&
+           grid_close(ndim, nderiv, nodes, axes, coef, out, 1, c);
 }
 
 template <typename T>
 static int32_t eval_grid_dev(int32_t ndim, const int64_t *npts, const T *axes_dev, const int32_t *nderiv, const T *coef_dev,
                              const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, void *stream)
 {
-    Grid g;
-    long long nout = 0, zero_n = 0;
-    int rc = 0;
-    if (!grid_validate(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, g, nout, rc, zero_n)) {
-        if (zero_n > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
-        return rc;
+    GridCheck c;
+    if (!grid_validate(ndim, npts, axes_dev, nderiv, coef_dev, xmin, xmax, nodes, out_dev, c)) {
+        zero_results(out_dev, c.zero_n, 1, 0, true, (hipStream_t)stream);
+        return c.rc;
     }
-    SPLPAK_HIP_TRY(launch_eval_grid<T>(g, npts, axes_dev, nderiv, coef_dev, out_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return rc;
+    SPLPAK_HIP_TRY(launch_eval_grid<T>(c.g, npts, axes_dev, nderiv, coef_dev, out_dev, (hipStream_t)stream), SPLPAK_E_NODEVICE);
+    return c.rc;
 }
 
 template <typename T>
 static int32_t eval_grid_host(int32_t ndim, const int64_t *npts, const T *axes, const int32_t *nderiv, const T *coef,
                               const T *xmin, const T *xmax, const int32_t *nodes, T *out)
 {
-    Grid g;
-    long long nout = 0, zero_n = 0;
-    int rc = 0;
-    if (!grid_validate(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, g, nout, rc, zero_n)) {
-        for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
-        return rc;
+    GridCheck c;
+    if (!grid_validate(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, c)) {
+        zero_results(out, c.zero_n, 1, 0, false, nullptr);
+        return c.rc;
     }
-    long long ntab = 0;
-    for (int d = 0; d < ndim; ++d) ntab += npts[d];
-    return staged_call<T>(axes, (size_t)ntab, coef, (size_t)g.ncol, out, (size_t)nout, false, "grid evaluation", rc,
-                          [&](const T *da, const T *dc, T *dout) { return launch_eval_grid<T>(g, npts, da, nderiv, dc, dout, nullptr); });
+    return staged_call<T>(axes, (size_t)c.ntab, coef, (size_t)c.g.ncol, out, (size_t)c.nout, 1, 0, false,
+                          [&](const T *da, const T *dc, T *dout) { return launch_eval_grid<T>(c.g, npts, da, nderiv, dc, dout, nullptr); },
+                          staged_status("grid evaluation", c.rc));
 }
 
 extern "C" {
@@ -438,39 +470,18 @@ int32_t splpak_debug_eval_grid_stats(int64_t out2[2])
 
 // ---- integrals over the cells of a tensor grid (integrategrid.hip) ----
 // The ladder of grid_validate with ncell in place of npts and the mode check beside the count check; no nderiv, hence no 104.
-// nax: the axis entries (ncell[d] + 1 edges of an integrated dimension, ncell[d] coordinates of an evaluated one).
+// c.ntab: the axis entries (ncell[d] + 1 edges of an integrated dimension, ncell[d] coordinates of an evaluated one).
 template <typename T>
-static bool integrate_validate(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes, const T *coef, const T *xmin_t,
-                               const T *xmax_t, const int32_t *nodes, const T *out, Grid &g, long long &nout, long long &nax, int &rc,
-                               long long &zero_n)
+static bool integrate_validate(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes, const T *coef, const T *xmin,
+                               const T *xmax, const int32_t *nodes, const T *out, GridCheck &c)
 {
-    nout = 0;
-    nax = 0;
-    zero_n = 0;
-    if (!ncell) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    double xmin[MAXD], xmax[MAXD];
-    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, xmin, xmax, rc, zero_n)) return false;
-    long long ntab = 0;
-    bool ok = grid_counts(ndim, ncell, nout, ntab);
-    for (int d = 0; ok && d < ndim; ++d) {
+    const char *bad = "negative ncell, a mode outside 0 and 1, or an output count beyond int64";
+    if (!grid_open(ndim, ncell, xmin, xmax, nodes, out, bad, c)) return false;
+    for (int d = 0; d < ndim; ++d) {
         const int m = mode ? mode[d] : 1;
-        ok = (m == 0 || m == 1) && !__builtin_add_overflow(ntab, (long long)m, &ntab);
+        if ((m != 0 && m != 1) || __builtin_add_overflow(c.ntab, (long long)m, &c.ntab)) { set_error(bad); c.rc = SPLPAK_E_BADARG; return false; }
     }
-    if (!ok) {
-        set_error("negative ncell, a mode outside 0 and 1, or an output count beyond int64");
-        rc = SPLPAK_E_BADARG;
-        return false;
-    }
-    nax = ntab;
-    rc = eval_validate(ndim, nullptr, xmin, xmax, nodes, g);
-    if (rc != 0) {
-        if (rc > 0 && out) zero_n = nout;
-        return false;
-    }
-    if (nout == 0) return false;
-    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    if (int r = device_ready()) { rc = r; return false; }
-    return true;
+    return grid_close(ndim, nullptr, nodes, axes, coef, out, 1, c);
 }
 
 static int32_t integrate_status(hipError_t e)
@@ -484,35 +495,26 @@ template <typename T>
 static int32_t integrate_grid_dev(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes_dev, const T *coef_dev,
                                   const T *xmin, const T *xmax, const int32_t *nodes, T *out_dev, void *stream)
 {
-    Grid g;
-    long long nout = 0, nax = 0, zero_n = 0;
-    int rc = 0;
-    if (!integrate_validate(ndim, ncell, mode, axes_dev, coef_dev, xmin, xmax, nodes, out_dev, g, nout, nax, rc, zero_n)) {
-        if (zero_n > 0) (void)hipMemsetAsync(out_dev, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
-        return rc;
+    GridCheck c;
+    if (!integrate_validate(ndim, ncell, mode, axes_dev, coef_dev, xmin, xmax, nodes, out_dev, c)) {
+        zero_results(out_dev, c.zero_n, 1, 0, true, (hipStream_t)stream);
+        return c.rc;
     }
-    return integrate_status(launch_integrate_grid<T>(g, ncell, mode, axes_dev, coef_dev, out_dev, (hipStream_t)stream));
+    return integrate_status(launch_integrate_grid<T>(c.g, ncell, mode, axes_dev, coef_dev, out_dev, (hipStream_t)stream));
 }
 
 template <typename T>
 static int32_t integrate_grid_host(int32_t ndim, const int64_t *ncell, const int32_t *mode, const T *axes, const T *coef,
                                    const T *xmin, const T *xmax, const int32_t *nodes, T *out)
 {
-    Grid g;
-    long long nout = 0, nax = 0, zero_n = 0;
-    int rc = 0;
-    if (!integrate_validate(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out, g, nout, nax, rc, zero_n)) {
-        for (long long i = 0; i < zero_n; ++i) out[i] = (T)0;
-        return rc;
+    GridCheck c;
+    if (!integrate_validate(ndim, ncell, mode, axes, coef, xmin, xmax, nodes, out, c)) {
+        zero_results(out, c.zero_n, 1, 0, false, nullptr);
+        return c.rc;
     }
-    bool nomem = false;
-    const int32_t r = staged_call<T>(axes, (size_t)nax, coef, (size_t)g.ncol, out, (size_t)nout, false, "integration on a grid", rc,
-                                     [&](const T *da, const T *dc, T *dout) {
-                                         const hipError_t e = launch_integrate_grid<T>(g, ncell, mode, da, dc, dout, nullptr);
-                                         nomem = e == hipErrorOutOfMemory;
-                                         return e;
-                                     });
-    return nomem ? SPLPAK_E_NOMEM : r;
+    return staged_call<T>(axes, (size_t)c.ntab, coef, (size_t)c.g.ncol, out, (size_t)c.nout, 1, 0, false,
+                          [&](const T *da, const T *dc, T *dout) { return launch_integrate_grid<T>(c.g, ncell, mode, da, dc, dout, nullptr); },
+                          integrate_status);
 }
 
 extern "C" {
@@ -557,88 +559,49 @@ int32_t splpak_debug_integrate_grid_stats(int64_t out8[8])
 
 // ---- value, gradient and Hessian planes on a tensor-product grid of points (evalgridderivs.hip) ----
 // The checks of a grid-derivatives entry before it touches a device: the ladder of grid_validate with the order and ldout
-// checks between the shape and the 102 / 103 checks.  True: the caller goes on to compute; false: rc is the status to
-// return, and zero_n results are zeroed first -- of out[0] alone (101) or, `planes`, of every plane (102 / 103).
+// checks between the shape and the 102 / 103 checks.  True: the caller goes on to compute; false: c.rc is the status to
+// return, and c.zero_n results are zeroed first -- of out[0] alone (101) or of every plane (102 / 103).
 template <typename T>
-static bool grid_derivs_validate(int32_t ndim, const int64_t *npts, const T *axes, int32_t order, const T *coef, const T *xmin_t,
-                                 const T *xmax_t, const int32_t *nodes, const T *out, int64_t ldout, Grid &g, long long &nout,
-                                 int &rc, long long &zero_n, bool &planes)
+static bool grid_derivs_validate(int32_t ndim, const int64_t *npts, const T *axes, int32_t order, const T *coef, const T *xmin,
+                                 const T *xmax, const int32_t *nodes, const T *out, int64_t ldout, GridCheck &c)
 {
-    nout = 0;
-    zero_n = 0;
-    planes = false;
-    if (!npts) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    double xmin[MAXD], xmax[MAXD];
-    if (!grid_args(ndim, xmin_t, xmax_t, nodes, out ? 1 : 0, xmin, xmax, rc, zero_n)) return false;
-    long long ntab = 0, total = 0;
-    if (!grid_counts(ndim, npts, nout, ntab)) {
-        set_error("negative npts, or an output count beyond int64");
-        rc = SPLPAK_E_BADARG;
-        return false;
-    }
-    if (order < 1 || order > 2) { set_error("order must be 1 (gradient) or 2 (gradient and Hessian)"); rc = SPLPAK_E_BADARG; return false; }
-    if (ldout < nout || __builtin_mul_overflow((long long)derivs_nout(ndim, order), (long long)ldout, &total)) {
+    if (!grid_open(ndim, npts, xmin, xmax, nodes, out, "negative npts, or an output count beyond int64", c)) return false;
+    if (order < 1 || order > 2) { set_error("order must be 1 (gradient) or 2 (gradient and Hessian)"); c.rc = SPLPAK_E_BADARG; return false; }
+    long long total = 0;
+    if (ldout < c.nout || __builtin_mul_overflow((long long)derivs_nout(ndim, order), (long long)ldout, &total)) {
         set_error("ldout smaller than the number of grid points, or the planes beyond int64");
-        rc = SPLPAK_E_BADARG;
+        c.rc = SPLPAK_E_BADARG;
         return false;
     }
-    rc = eval_validate(ndim, nullptr, xmin, xmax, nodes, g);
-    if (rc != 0) {
-        if (rc > 0 && out) { zero_n = nout; planes = true; }
-        return false;
-    }
-    if (nout == 0) return false;
-    if (!axes || !coef || !out) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
-    if (int r = device_ready()) { rc = r; return false; }
-    return true;
+    return grid_close(ndim, nullptr, nodes, axes, coef, out, derivs_nout(ndim, order), c);
 }
 
 template <typename T>
 static int32_t eval_grid_derivs_dev(int32_t ndim, const int64_t *npts, const T *axes_dev, int32_t order, const T *coef_dev, const T *xmin,
                                     const T *xmax, const int32_t *nodes, T *out_dev, int64_t ldout, void *stream)
 {
-    Grid g;
-    long long nout = 0, zero_n = 0;
-    int rc = 0;
-    bool planes = false;
-    if (!grid_derivs_validate(ndim, npts, axes_dev, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, g, nout, rc, zero_n, planes)) {
-        const int np = planes ? derivs_nout(ndim, order) : 1;
-        if (zero_n > 0)
-            for (int e = 0; e < np; ++e) (void)hipMemsetAsync(out_dev + (long long)e * ldout, 0, sizeof(T) * (size_t)zero_n, (hipStream_t)stream);
-        return rc;
+    GridCheck c;
+    if (!grid_derivs_validate(ndim, npts, axes_dev, order, coef_dev, xmin, xmax, nodes, out_dev, ldout, c)) {
+        zero_results(out_dev, c.zero_n, c.zero_planes, ldout, true, (hipStream_t)stream);
+        return c.rc;
     }
-    SPLPAK_HIP_TRY(launch_eval_grid_derivs<T>(g, npts, axes_dev, order, coef_dev, out_dev, ldout, (hipStream_t)stream), SPLPAK_E_NODEVICE);
-    return rc;
+    SPLPAK_HIP_TRY(launch_eval_grid_derivs<T>(c.g, npts, axes_dev, order, coef_dev, out_dev, ldout, (hipStream_t)stream), SPLPAK_E_NODEVICE);
+    return c.rc;
 }
 
-// the host form stages through the device as staged_call does; the planes are packed there (prod npts apart) and copied
-// back one by one, so that the caller's words between the planes keep their contents
+// the host form: the planes are packed on the device (prod npts apart) and come back one by one
 template <typename T>
 static int32_t eval_grid_derivs_host(int32_t ndim, const int64_t *npts, const T *axes, int32_t order, const T *coef, const T *xmin,
                                      const T *xmax, const int32_t *nodes, T *out, int64_t ldout)
 {
-    Grid g;
-    long long nout = 0, zero_n = 0;
-    int rc = 0;
-    bool planes = false;
-    if (!grid_derivs_validate(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, ldout, g, nout, rc, zero_n, planes)) {
-        const int np = planes ? derivs_nout(ndim, order) : 1;
-        for (int e = 0; e < np; ++e)
-            for (long long i = 0; i < zero_n; ++i) out[(long long)e * ldout + i] = (T)0;
-        return rc;
+    GridCheck c;
+    if (!grid_derivs_validate(ndim, npts, axes, order, coef, xmin, xmax, nodes, out, ldout, c)) {
+        zero_results(out, c.zero_n, c.zero_planes, ldout, false, nullptr);
+        return c.rc;
     }
-    const int np = derivs_nout(ndim, order);
-    size_t ntab = 0;
-    for (int d = 0; d < ndim; ++d) ntab += (size_t)npts[d];
-    DevStage stage;
-    T *da = nullptr, *dc = nullptr, *dout = nullptr;
-    if (!stage.alloc(&da, ntab) || !stage.alloc(&dc, (size_t)g.ncol) || !stage.alloc(&dout, (size_t)np * (size_t)nout)) return SPLPAK_E_NOMEM;
-    hipError_t e = hipMemcpy(da, axes, sizeof(T) * ntab, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * (size_t)g.ncol, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_eval_grid_derivs<T>(g, npts, da, order, dc, dout, nout, nullptr);
-    for (int k = 0; k < np && e == hipSuccess; ++k)
-        e = hipMemcpy(out + (long long)k * ldout, dout + (long long)k * nout, sizeof(T) * (size_t)nout, hipMemcpyDeviceToHost);
-    return hip_ok(e, "grid evaluation of derivatives") ? rc : SPLPAK_E_NODEVICE;
+    return staged_call<T>(axes, (size_t)c.ntab, coef, (size_t)c.g.ncol, out, (size_t)c.nout, derivs_nout(ndim, order), ldout, false,
+                          [&](const T *da, const T *dc, T *dout) { return launch_eval_grid_derivs<T>(c.g, npts, da, order, dc, dout, c.nout, nullptr); },
+                          staged_status("grid evaluation of derivatives", c.rc));
 }
 
 extern "C" {

@@ -25,6 +25,24 @@ inline bool value_only(const NDeriv &nd)
     return v;
 }
 
+// The 4 coefficients of a window row (k0 = 0..3 from p on), widened to double.  They are contiguous: two 16-byte loads
+// (REAL32: one) instead of four 8-byte ones (the gathering kernels are bound by gather instructions / L2 lines, not bytes).
+// The load4 of window_sum in the direct, the fields and the grid kernels' general form.
+template <typename T>
+__device__ inline void load_window_row(const T *p, double (&c)[4])
+{
+    if constexpr (sizeof(T) == 8) {
+        typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
+        const d2v lo = *reinterpret_cast<const d2v *>(p);
+        const d2v hi = *reinterpret_cast<const d2v *>(p + 2);
+        c[0] = lo[0]; c[1] = lo[1]; c[2] = hi[0]; c[3] = hi[1];
+    } else {
+        typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
+        const f4v v = *reinterpret_cast<const f4v *>(p);
+        c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
+    }
+}
+
 // Sum of the 4^D window products, factorised: the innermost dimension is contracted with its four
 // factors first, then the partial sums with the factors of the next dimension, and so on -- 64 + 16 + 4
 // fused multiply-adds in 3-D instead of the 64 * 3 multiplications of the plain triple product (the

@@ -251,16 +251,7 @@ eval_grid_kernel(Grid g, GridShape gs, const double *__restrict__ fac, const int
         if (!ok) continue;
         const double sum = window_sum<D>(b, [&](int k1, int k2, int k3, double (&c)[4]) {
             const long long ci = base + k1 * s1 + k2 * s2 + k3 * s3;
-            if constexpr (sizeof(TC) == 8) {
-                typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
-                const d2v lo = *reinterpret_cast<const d2v *>(coef + ci);
-                const d2v hi = *reinterpret_cast<const d2v *>(coef + ci + 2);
-                c[0] = lo[0]; c[1] = lo[1]; c[2] = hi[0]; c[3] = hi[1];
-            } else {
-                typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
-                const f4v v = *reinterpret_cast<const f4v *>(coef + ci);
-                c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
-            }
+            load_window_row(coef + ci, c);
         });
         out[idx] = (TO)sum;
     }
@@ -292,6 +283,21 @@ hipError_t eval_grid_stats(long long out2[2])
 
 int eval_grid_tile(int ndim, int d) { return ndim == 1 ? GTile<1>::T[d] : ndim == 2 ? GTile<2>::T[d] : ndim == 3 ? GTile<3>::T[d] : GTile<4>::T[d]; }
 
+bool eval_grid_slab(int ndim, const long long *npts, long long row, long long cap, long long &qmax)
+{
+    const int last = ndim - 1;
+    long long row_tiles = 1;      // tiles of one tile layer of the last dimension
+    for (int d = 0; d < last; ++d) {
+        const long long t = eval_grid_tile(ndim, d);
+        if (__builtin_mul_overflow(row_tiles, (npts[d] + t - 1) / t, &row_tiles)) return false;
+    }
+    if (row_tiles > 0x7fffffffLL) return false;
+    const long long qtiles = (0x7fffffffLL / row_tiles) * eval_grid_tile(ndim, last);
+    qmax = cap / row;
+    qmax = qmax < qtiles ? qmax : qtiles;
+    return true;
+}
+
 // the tile kernel on prepared tables: gs.npts and gs.off are the caller's, the tile counts are set here
 template <typename TC, typename TO>
 hipError_t launch_eval_grid_tables(const Grid &g, GridShape &gs, const double *fac, const int *wst, const TC *coef, TO *out,
@@ -321,16 +327,8 @@ template <typename T>
 hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, const int *nderiv, const T *coef, T *out, hipStream_t st)
 {
     GridShape gs;
-    long long ntab = 0;
-    for (int d = 0; d < MAXD; ++d) {
-        const long long n = d < g.ndim ? npts[d] : 1;
-        if (n <= 0) return hipSuccess;
-        gs.npts[d] = n;
-        gs.off[d] = ntab;
-        if (d < g.ndim) ntab += n;
-    }
-    gs.off[MAXD] = ntab;
-    for (int d = g.ndim; d < MAXD; ++d) gs.off[d] = ntab;
+    if (!grid_shape(g.ndim, npts, gs)) return hipSuccess;
+    const long long ntab = gs.off[MAXD];
     const NDeriv nd = clamp_nderiv(nderiv, g.ndim);
     DevScratch<1> &s = g_gscratch;
     int dev = 0;
@@ -338,6 +336,7 @@ hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, c
     const size_t need[1] = {(size_t)eval_grid_scratch_bytes(ntab)};
     if (hipError_t e = s.ensure(dev, need, /*may_release_plan=*/true); e != hipSuccess) return e;
     if (hipError_t e = s.wait_on(st); e != hipSuccess) return e;
+    const ScratchUse<1> use{s, st};                         // (also after a refused tile count: the table kernel is queued)
     unsigned long long *stats = s.as<unsigned long long>(0);
     double *fac = reinterpret_cast<double *>(stats + 2);
     int *wst = reinterpret_cast<int *>(fac + 4 * ntab);
@@ -346,9 +345,7 @@ hipError_t launch_eval_grid(const Grid &g, const int64_t *npts, const T *axes, c
         dim3 gr((unsigned)((ntab + 255) / 256)), bl(256);
         hipLaunchKernelGGL((value_only(nd) ? grid_table_kernel<T, true> : grid_table_kernel<T, false>), gr, bl, 0, st, g, gs, nd, axes, fac, wst);
     }
-    const hipError_t e = launch_eval_grid_tables<T, T>(g, gs, fac, wst, coef, out, stats, st);
-    const hipError_t m = s.mark_used(st);                   // also after a refused tile count: the table kernel is queued
-    return e != hipSuccess ? e : m;
+    return launch_eval_grid_tables<T, T>(g, gs, fac, wst, coef, out, stats, st);
 }
 template hipError_t launch_eval_grid<double>(const Grid &, const int64_t *, const double *, const int *, const double *, double *, hipStream_t);
 template hipError_t launch_eval_grid<float>(const Grid &, const int64_t *, const float *, const int *, const float *, float *, hipStream_t);

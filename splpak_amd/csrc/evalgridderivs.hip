@@ -347,16 +347,7 @@ eval_grid_derivs_kernel(Grid g, GridShape gs, const double *__restrict__ fac, co
             [&](int o_, int d, int kk) { return tb[o_ * NTAB + te[d]][kk]; },
             [&](int k1, int k2, int k3, double (&c)[4]) {
                 const long long ci = base + k1 * s1 + k2 * s2 + k3 * s3;
-                if constexpr (sizeof(T) == 8) {
-                    typedef double d2v __attribute__((ext_vector_type(2), aligned(8)));
-                    const d2v lo = *reinterpret_cast<const d2v *>(coef + ci);
-                    const d2v hi = *reinterpret_cast<const d2v *>(coef + ci + 2);
-                    c[0] = lo[0]; c[1] = lo[1]; c[2] = hi[0]; c[3] = hi[1];
-                } else {
-                    typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));
-                    const f4v v = *reinterpret_cast<const f4v *>(coef + ci);
-                    c[0] = v[0]; c[1] = v[1]; c[2] = v[2]; c[3] = v[3];
-                }
+                load_window_row(coef + ci, c);
             },
             k, acc);
 #pragma unroll
@@ -401,16 +392,9 @@ hipError_t launch_eval_grid_derivs(const Grid &g, const int64_t *npts, const T *
     GridShape gs;
     int tile[4];
     if (!eval_grid_derivs_tile(g.ndim, order, tile)) return hipErrorInvalidValue;
-    long long ntab = 0, ntiles = 1;
-    for (int d = 0; d < MAXD; ++d) {
-        const long long n = d < g.ndim ? npts[d] : 1;
-        if (n <= 0) return hipSuccess;
-        gs.npts[d] = n;
-        gs.off[d] = ntab;
-        if (d < g.ndim) ntab += n;
-    }
-    gs.off[MAXD] = ntab;
-    for (int d = g.ndim; d < MAXD; ++d) gs.off[d] = ntab;
+    if (!grid_shape(g.ndim, npts, gs)) return hipSuccess;
+    const long long ntab = gs.off[MAXD];
+    long long ntiles = 1;
     for (int d = 0; d < MAXD; ++d) {
         gs.ntile[d] = (gs.npts[d] + tile[d] - 1) / tile[d];
         ntiles *= gs.ntile[d];
@@ -422,12 +406,11 @@ hipError_t launch_eval_grid_derivs(const Grid &g, const int64_t *npts, const T *
     const size_t need[1] = {(size_t)eval_grid_derivs_scratch_bytes(ntab, order)};
     if (hipError_t e = s.ensure(dev, need, /*may_release_plan=*/true); e != hipSuccess) return e;
     if (hipError_t e = s.wait_on(st); e != hipSuccess) return e;
+    const ScratchUse<1> use{s, st};
     unsigned long long *stats = s.as<unsigned long long>(0);
     if (hipError_t e = hipMemsetAsync(stats, 0, 16, st); e != hipSuccess) return e;
-    hipError_t e = order == 1 ? launch_order<1, T>(g, gs, ntab, ntiles, axes, coef, out, ldout, stats, st)
-                              : launch_order<2, T>(g, gs, ntab, ntiles, axes, coef, out, ldout, stats, st);
-    if (e == hipSuccess) e = s.mark_used(st);
-    return e;
+    return order == 1 ? launch_order<1, T>(g, gs, ntab, ntiles, axes, coef, out, ldout, stats, st)
+                      : launch_order<2, T>(g, gs, ntab, ntiles, axes, coef, out, ldout, stats, st);
 }
 template hipError_t launch_eval_grid_derivs<double>(const Grid &, const int64_t *, const double *, int, const double *, double *, long long, hipStream_t);
 template hipError_t launch_eval_grid_derivs<float>(const Grid &, const int64_t *, const float *, int, const float *, float *, long long, hipStream_t);

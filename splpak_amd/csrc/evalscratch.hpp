@@ -2,7 +2,7 @@
 // sort, the run path, the persistent path and the grid route each keep a thread_local instance (regrowing one leaves the others alone):
 //   ensure     the buffers hold at least the asked sizes on this device (regrown together, never shrunk)
 //   wait_on    a stream about to use them waits for the previous use (which may have been on another stream)
-//   mark_used  records the end of this use
+//   mark_used  records the end of this use (ScratchUse below: on every exit of a scope)
 //   release    frees everything (splpak_shutdown, a failed ensure)
 #pragma once
 #include "kernels.hpp"
@@ -63,6 +63,16 @@ struct DevScratch {
         used = used || e == hipSuccess;
         return e;
     }
+};
+
+// Held from wait_on to the end of a call (the grid routes, the grid fit): records the end of this use of the scratch on
+// every exit, the error returns included: what was queued before them still reads and writes the buffers, and a later call
+// on another stream has to wait for it.  (Nothing to record while the scratch holds nothing: before or after a failed ensure.)
+template <int N>
+struct ScratchUse {
+    DevScratch<N> &s;
+    hipStream_t st;
+    ~ScratchUse() { if (s.last) (void)s.mark_used(st); }
 };
 
 }  // namespace splpak

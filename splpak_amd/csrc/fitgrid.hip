@@ -152,6 +152,10 @@ static int fit_grid_host_run(const Grid &g, const int64_t *npts, const double *a
     return 0;
 }
 
+// (Placed on a 64-byte boundary: the per-coordinate loop of fit_grid_host_run, inlined here, takes 15 ns an iteration, and the
+// same instructions starting 48 bytes into a line, where a change elsewhere in the library had moved them, took 4 % longer
+// over the two 4096-point axes of an image.)
+__attribute__((aligned(64)))
 int fit_grid_host(const Grid &g, const int64_t *npts, const double *axes, const double *waxes, double xtrap, FitGridHost &h)
 {
     try {
@@ -303,17 +307,6 @@ static hipError_t launch_spread(const SpreadArgs &a, const TI *in, const double 
     return hipGetLastError();
 }
 
-// an integer option, clamped to lo .. hi; dflt when it is not set or not a number
-static long long option_ll(const char *name, long long dflt, long long lo, long long hi)
-{
-    if (const char *e = splpak::opt_get(name)) {
-        char *end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end != e && !*end) return v < lo ? lo : (v > hi ? hi : v);
-    }
-    return dflt;
-}
-
 // Nodes per block: the largest of 64, 32, .. that still gives the pass 8192 waves (32 per CU: a wave's walk is a chain of
 // memory waits, so what hides them is waves); a pass that misses that even with one node per block takes 1, and one of fewer
 // than 2048 waves in all, where nothing matters, 4.  No bit of the result depends on it, which the diagnostic option
@@ -335,6 +328,17 @@ static int node_block(long long inner, long long outer, int nod)
 // chunk and not once per entry.
 constexpr int SOLVE_CH = 8;
 
+// One step of L z = t at row j: l = the row's four entries (the reciprocal of the diagonal first), s = t[j], z1 .. z3 the
+// three results before it.  Returns z[j].  (The step of the backward sweep stays written out in both kernels: as a function
+// of this kind the chunked kernel compiled its row tests to other branches.)
+__device__ inline double band_forward(const double *l, double s, double z1, double z2, double z3)
+{
+    s = fma(-l[1], z1, s);
+    s = fma(-l[2], z2, s);
+    s = fma(-l[3], z3, s);
+    return s * l[0];
+}
+
 __global__ void __launch_bounds__(256)
 fit_solve_kernel(const double *__restrict__ chol, int nod, long long inner, long long lines, double *__restrict__ x)
 {
@@ -350,12 +354,7 @@ fit_solve_kernel(const double *__restrict__ chol, int nod, long long inner, long
 #pragma unroll
         for (int k = 0; k < SOLVE_CH; ++k) {
             if (j0 + k < nod) {
-                const double *l = chol + 4 * (long long)(j0 + k);
-                double s = r[k];
-                s = fma(-l[1], z1, s);
-                s = fma(-l[2], z2, s);
-                s = fma(-l[3], z3, s);
-                s *= l[0];
+                const double s = band_forward(chol + 4 * (long long)(j0 + k), r[k], z1, z2, z3);
                 r[k] = s;
                 z3 = z2; z2 = z1; z1 = s;
             }
@@ -412,12 +411,7 @@ fit_solve_reg_kernel(const double *__restrict__ chol, int nod, long long inner, 
 #pragma unroll
     for (int k = 0; k < NR; ++k) {
         if (k < nod) {
-            const double *l = sl + 4 * k;
-            double s = r[k];
-            s = fma(-l[1], z1, s);
-            s = fma(-l[2], z2, s);
-            s = fma(-l[3], z3, s);
-            s *= l[0];
+            const double s = band_forward(sl + 4 * k, r[k], z1, z2, z3);
             r[k] = s;
             z3 = z2; z2 = z1; z1 = s;
         }
@@ -514,12 +508,6 @@ struct Device {
     double *at(long long o) const { return base + o; }
 };
 
-struct UseGuard {
-    DevScratch<1> &s;
-    hipStream_t st;
-    ~UseGuard() { if (s.last) (void)s.mark_used(st); }
-};
-
 }  // namespace
 
 // sizes; false: beyond what can be addressed
@@ -556,17 +544,10 @@ static bool plan_layout(const FitGridHost &h, bool refine, long long stage_value
     if (refine) {
         long long row = 1;      // samples per position of the last dimension
         for (int e = 0; e < last; ++e) row *= h.npts[e];      // (prod npts fits int64: the entry checked it)
-        long long sq = 0, row_tiles = 1;
+        long long sq = 0, q = 0;
         if (__builtin_mul_overflow(row, (long long)h.ax[last].nod, &sq) || sq > (1LL << 58)) return false;
-        for (int e = 0; e < last; ++e) {
-            const long long t = eval_grid_tile(D, e);
-            if (__builtin_mul_overflow(row_tiles, (h.npts[e] + t - 1) / t, &row_tiles)) return false;
-        }
-        if (row_tiles > 0x7fffffffLL) return false;
         const long long cap = option_ll("SPLPAK_FIT_GRID_SCRATCH_MB", 256, 1, 1LL << 40) * (1LL << 17);
-        const long long tl = eval_grid_tile(D, last), qtiles = (0x7fffffffLL / row_tiles) * tl;
-        long long q = cap / row;
-        q = q < qtiles ? q : qtiles;
+        if (!eval_grid_slab(D, h.npts, row, cap, q)) return false;
         q = q < 1 ? 1 : q;      // a single position above the cap goes whole
         q = q > h.npts[last] ? h.npts[last] : q;
         long long ac = 0;
@@ -675,13 +656,8 @@ static hipError_t spread_residual(const Device &dv, const TI *values, const doub
     double *out = last == 0 ? dst : dv.at(L.A);
     SpreadArgs a = spread_args(dv, last);
     if (hipError_t e = hipMemsetAsync(dv.at(L.sq), 0, sizeof(double) * (size_t)(a.inner * a.nod), dv.st); e != hipSuccess) return e;
-    GridShape gs;
-    for (int d = 0; d < MAXD; ++d) {
-        gs.npts[d] = d < dv.D ? h.npts[d] : 1;
-        gs.off[d] = L.off[d < dv.D ? d : dv.D];
-        gs.ntile[d] = 1;
-    }
-    gs.off[MAXD] = L.off[dv.D];
+    GridShape gs;      // (its table offsets are Layout::off: the prefix of npts)
+    if (!grid_shape(dv.D, h.npts, gs)) return hipErrorInvalidValue;
     const int *wst = reinterpret_cast<const int *>(dv.at(L.wstE));
     for (long long pa = 0, k = 0; pa < a.np; pa += L.q, ++k) {
         const long long pb = pa + L.q < a.np ? pa + L.q : a.np;
@@ -767,7 +743,7 @@ static int fit_grid_device_run(const FitGridHost &h, int nfields, const T *value
     const double tol = 1e-11;
     const int ncol = h.g.ncol;
     Device dv(h, st);
-    const UseGuard guard{g_fscratch, st};
+    const ScratchUse<1> use{g_fscratch, st};
     if (int r = device_begin(dv, hard > 0, on_host ? (long long)sizeof(T) * h.nsamp : 0, on_host ? (long long)sizeof(T) * ncol : 0)) return r;
     const Layout &L = dv.L;
     double *X = dv.at(L.X), *R = dv.at(L.R), *small = dv.at(L.small);
@@ -864,7 +840,7 @@ int fit_grid_stage(const FitGridHost &h, int stage, const double *in, double *ou
         const int ncol = h.g.ncol;
         const long long nin = stage == 0 ? h.nsamp : ncol;
         Device dv(h, nullptr);
-        const UseGuard guard{g_fscratch, nullptr};
+        const ScratchUse<1> use{g_fscratch, nullptr};
         if (int r = device_begin(dv, false, 8 * nin, 0)) return r;
         double *X = dv.at(dv.L.X), *sv = dv.at(dv.L.stageV);
         if (stage == 0) {

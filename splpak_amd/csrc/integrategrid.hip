@@ -27,7 +27,6 @@
 #include "pieces.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <new>
 #include <vector>
 
@@ -158,17 +157,6 @@ void integrate_grid_stats(long long out8[8])
     for (int k = 0; k < 8; ++k) out8[k] = t_stats[k];
 }
 
-static long long scratch_cap_doubles()
-{
-    long long mb = 256;
-    if (const char *e = splpak::opt_get("SPLPAK_INTEGRATE_SCRATCH_MB")) {
-        char *end = nullptr;
-        const long long v = strtoll(e, &end, 10);
-        if (end != e && !*end) mb = v < 1 ? 1 : (v > (1LL << 40) ? (1LL << 40) : v);
-    }
-    return mb * (1LL << 17);                                // 2^20 / 8
-}
-
 template <typename TO>
 static hipError_t launch_piece_sum(const double *in, TO *out, const long long *s, long long pbase, long long inner, long long ncell,
                                    long long np, long long outer, hipStream_t st)
@@ -178,14 +166,6 @@ static hipError_t launch_piece_sum(const double *in, TO *out, const long long *s
     hipLaunchKernelGGL((piece_sum_kernel<TO>), dim3((unsigned)blocks), dim3(256), 0, st, in, out, s, pbase, inner, ncell, np, total);
     return hipGetLastError();
 }
-
-// records the end of this use of the scratch on every exit, the error returns included: what was queued before them still
-// reads and writes the buffers, and a later call on another stream has to wait for it
-struct UseGuard {
-    DevScratch<1> &s;
-    hipStream_t st;
-    ~UseGuard() { if (s.last) (void)s.mark_used(st); }
-};
 
 template <typename T>
 static hipError_t integrate_grid_run(const Grid &g, const int64_t *ncell, const int *mode, const T *axes, const T *coef, T *out, hipStream_t st)
@@ -221,7 +201,7 @@ static hipError_t integrate_grid_run(const Grid &g, const int64_t *ncell, const 
     const size_t need1[1] = {(size_t)(16 + 8 * nst)};
     if (hipError_t e = s.ensure(dev, need1, /*may_release_plan=*/true); e != hipSuccess) return e;
     if (hipError_t e = s.wait_on(st); e != hipSuccess) return e;
-    const UseGuard guard{s, st};
+    const ScratchUse<1> use{s, st};
     auto count_pass = [&]() {
         long long *starts = reinterpret_cast<long long *>(s.as<unsigned long long>(0) + 2);
         hipLaunchKernelGGL((piece_count_kernel<T>), dim3((unsigned)((nst + 255) / 256)), dim3(256), 0, st, g, is, nst, axes, starts);
@@ -234,38 +214,29 @@ static hipError_t integrate_grid_run(const Grid &g, const int64_t *ncell, const 
     if (hipError_t e = hipMemcpyAsync(hs.data(), s.as<unsigned long long>(0) + 2, 8 * (size_t)nst, hipMemcpyDeviceToHost, st); e != hipSuccess) return e;
     if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return e;      // the one wait: the piece counts size the launches
 
-    long long P[MAXD] = {1, 1, 1, 1}, ntab = 0;
-    GridShape full;
-    for (int d = 0; d < MAXD; ++d) {
-        full.off[d] = ntab;
-        full.npts[d] = 1;
-        full.ntile[d] = 1;
-        if (d < D) {
-            P[d] = hs[(size_t)(is.soff[d] + is.ncell[d])];
-            full.npts[d] = P[d];
-            ntab += P[d];
-            t_stats[2 + d] = P[d];
-        }
+    long long P[MAXD] = {1, 1, 1, 1};                       // pieces per dimension (every cell has at least one)
+    for (int d = 0; d < D; ++d) {
+        P[d] = hs[(size_t)(is.soff[d] + is.ncell[d])];
+        t_stats[2 + d] = P[d];
     }
-    full.off[MAXD] = ntab;
+    GridShape full;
+    if (!grid_shape(D, P, full)) return hipErrorInvalidValue;      // (a scan that lost its counts: P >= ncell >= 1)
+    const long long ntab = full.off[MAXD];
     // doubles per piece of the last dimension: the piece products (A) and, with two or more integrated dimensions, the result
     // of the first reduction (B); later results fit the buffer two steps back
-    long long rowA = 1, rowB = 0, row_out = 1, row_tiles = 1;
+    long long rowA = 1, rowB = 0, row_out = 1;
     bool big = false;
     for (int d = 0; d < L; ++d) {
         big = big || __builtin_mul_overflow(rowA, P[d], &rowA);
         row_out *= is.ncell[d];                             // (the product of all ncell fits int64: the entry checked it)
-        const long long t = eval_grid_tile(D, d);
-        big = big || __builtin_mul_overflow(row_tiles, (P[d] + t - 1) / t, &row_tiles);
     }
     if (!big && nint >= 2) rowB = rowA / P[first] * is.ncell[first];
     long long row = 0;
-    big = big || __builtin_add_overflow(rowA, rowB, &row) || row > (1LL << 59) || row_tiles > 0x7fffffffLL;
+    big = big || __builtin_add_overflow(rowA, rowB, &row) || row > (1LL << 59);
     if (big) return hipErrorOutOfMemory;
-    const long long cap = scratch_cap_doubles();
-    long long qmax = cap / row;                             // pieces of the last dimension per slab
-    const long long tl = eval_grid_tile(D, L), qtiles = (0x7fffffffLL / row_tiles) * tl;
-    qmax = qmax < qtiles ? qmax : qtiles;
+    const long long cap = option_ll("SPLPAK_INTEGRATE_SCRATCH_MB", 256, 1, 1LL << 40) * (1LL << 17);      // 2^20 / 8
+    long long qmax = 0;                                     // pieces of the last dimension per slab
+    if (!eval_grid_slab(D, P, row, cap, qmax)) return hipErrorOutOfMemory;
     // slabs of consecutive cells of the last dimension; a single cell above the cap goes whole
     const long long *SL = hs.data() + is.soff[L];
     const long long nl = is.ncell[L];
@@ -282,7 +253,8 @@ static hipError_t integrate_grid_run(const Grid &g, const int64_t *ncell, const 
     if (__builtin_mul_overflow(rowA, qbig, &na) || __builtin_mul_overflow(rowB, qbig, &nb) || na > (1LL << 59) || nb > (1LL << 59) ||
         ntab > (1LL << 55))
         return hipErrorOutOfMemory;
-    if (qbig > (0x7fffffffLL / row_tiles) * tl) return hipErrorInvalidValue;
+    long long qfit = 0;                                     // a single cell above the cap: does its slab still fit a launch?
+    if (!eval_grid_slab(D, P, 1, qbig, qfit) || qfit < qbig) return hipErrorInvalidValue;
     words = 2 + nst + 4 * ntab + na + nb + (ntab + 1) / 2;
     const size_t need2[1] = {(size_t)words * 8};
     const bool regrow = need2[0] > s.bytes[0];

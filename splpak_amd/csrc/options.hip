@@ -142,6 +142,16 @@ const char *opt_get(const char *canon)
     return std::getenv(canon);
 }
 
+long long option_ll(const char *name, long long dflt, long long lo, long long hi)
+{
+    if (const char *e = opt_get(name)) {
+        char *end = nullptr;
+        const long long v = strtoll(e, &end, 10);
+        if (end != e && !*end) return v < lo ? lo : (v > hi ? hi : v);
+    }
+    return dflt;
+}
+
 OptionsScope::OptionsScope(const Options *o) : prev(t_current) { t_current = o; }
 OptionsScope::~OptionsScope() { t_current = prev; }
 

@@ -26,6 +26,8 @@ Options options_snapshot();
 int options_set_default(const char *name, const char *value);      // value NULL: back to the environment's
 // the calling thread's current options, else the process snapshot
 const char *opt_get(const char *canon);
+// an integer option, clamped to lo .. hi; dflt when it is not set or not a number (the whole string must be a decimal integer)
+long long option_ll(const char *name, long long dflt, long long lo, long long hi);
 struct OptionsScope {
     const Options *prev;
     explicit OptionsScope(const Options *o);

@@ -330,6 +330,30 @@ def test_grid_derivs_host_entry_equals_device_entry():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("real32", [False, True], ids=["real64", "real32"])
+def test_grid_derivs_host_entry_with_padded_ldout_leaves_the_gaps_alone(real32):
+    """The host entries themselves (capi.evaluate_grid_derivs always passes a tight ldout): six planes ldout = points + 5 apart
+    into a NaN-filled buffer equal the device entry's bit for bit; the words between and behind the planes stay NaN."""
+    nodes, npts, order, pad, guard = (6, 5), (5, 3), 2, 5, 16
+    axes = _axes("awkward", nodes, npts, real32)
+    dt, rp = (np.float32, capi._fp) if real32 else (np.float64, capi._dp)
+    nout, npl = int(np.prod(npts)), _nplanes(2, order)
+    assert npl == 6
+    n64 = np.asarray(npts, dtype=np.int64)
+    cat, coef = np.concatenate(axes).astype(dt), _coef(nodes, real32)
+    lo, hi, nod = np.asarray(LO[:2], dtype=dt), np.asarray(HI[:2], dtype=dt), np.asarray(nodes, dtype=np.int32)
+    whole = np.full(npl * (nout + pad) + guard, np.nan, dtype=dt)
+    fn = capi.lib().splpak_eval_grid_derivs_f32 if real32 else capi.lib().splpak_eval_grid_derivs_f64
+    rc = fn(2, capi._p(n64, LP), capi._p(cat, rp), order, capi._p(coef, rp), capi._p(lo, rp), capi._p(hi, rp), capi._p(nod, capi._ip),
+            capi._p(whole, rp), nout + pad)
+    assert rc == 0
+    planes = whole[:npl * (nout + pad)].reshape(npl, nout + pad)
+    assert np.array_equal(planes[:, :nout], _fused_cached(nodes, npts, "awkward", order, real32)[0])
+    assert np.all(np.isnan(planes[:, nout:]))
+    assert np.all(np.isnan(whole[npl * (nout + pad):])) and whole.size == npl * (nout + pad) + guard
+
+
+@pytest.mark.gpu
 def test_grid_derivs_on_a_side_stream():
     """Asynchronous on the caller's stream: synchronising THAT stream alone is enough."""
     import torch
