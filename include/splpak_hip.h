@@ -607,6 +607,75 @@ int32_t splpak_debug_fit_grid_stage_f64(int32_t stage, int32_t ndim, const int64
  * steps of the last field, [5..7] 0.  The tables and intermediates live in a per-thread scratch released by splpak_shutdown. */
 int32_t splpak_debug_fit_grid_stats(int64_t out8[8]);
 
+/* The grid fit with a weight per sample: dead pixels, masked regions, NaN holes, a variance map -- weights that do not
+ * factor over the axes (those that do belong to splpak_fit_grid_*, which needs no iteration).  Returns the coefficients
+ * splcw returns for the listed samples OF NON-ZERO WEIGHT, provided that fit has no constraint rows: the contract of
+ * splpak_fit_grid_*.
+ *   weights  one per sample in the layout of `values`, a row weight as wdata of splcw is: the normal equations see its
+ *            square.  Field k's weights at weights + k*ldw; ldw == 0: one array for all fields, analysed once per call;
+ *            otherwise ldw >= prod npts.  A sample whose weight is exactly 0 is selected out, never multiplied: its value
+ *            may be NaN or Inf.
+ * Algorithm.  N = A^T diag(w^2) A with A = A_D x ... x A_1 is no Kronecker product.  N x = b is solved by preconditioned
+ * conjugate gradients from a zero start: applying N is one tile pass of splpak_eval_grid_* into the slab scratch and the
+ * spread passes of splpak_fit_grid_*, the first of which loads the sample's weight; the preconditioner is the separable
+ * solve of splpak_fit_grid_* on M = N^_D x ... x N^_1, N^_d = A_d^T diag(m_d / S^((D-1)/D)) A_d, with m_d the marginals of
+ * w^2 over the other dimensions and S their total (one pass over the weights).  For separable weights M = N and the
+ * iteration ends in one or two steps.  The first solve goes to a relative preconditioned residual of 1e-11; then the
+ * refinement rule of splpak_fit_grid_* unchanged, its residual A^T (w^2 o (y - A x)) taken from the samples and its
+ * corrections solved to 1e-3.  The scalars of the iteration stay on the device and are read back every 5 iterations.
+ * Options: fit_grid_refine, fit_grid_scratch_mb as for splpak_fit_grid_*; fit_grid_weighted_maxit = the cap of one solve's
+ * iterations (default 1000): a solve that reaches it hands its iterate to the refinement rule, which decides.
+ * xtrap != 0: answered only when no node is data sparse by the reference's rule node by node (:879-907): with h(j) the sum of
+ * the weights of the samples whose nearest node is j (every coordinate counted in range as for splpak_fit_grid_*) and
+ * ef(j) = 0.5 per dimension in which j is an end node, every h(j) / ef(j) >= 0.75 sum h / prod_d (nodes_d - 1).
+ * Determinism.  The bits of a field's coefficients depend on the axes, the weights and the field alone: not on the node
+ * block, the scratch cap (slabs), the number of fields, shared or per-field weights, or the host / _dev entry.  Every sum
+ * has one owner and a fixed order (csrc/fitgridw.hip gives it); there are no floating-point atomics.
+ * Status, the first failing check wins: the ladder of splpak_fit_grid_* with `weights` among its null checks, and
+ * SPLPAK_E_BADARG also for an ldw that is neither 0 nor >= prod npts; 107 where an axis is rank deficient whatever the
+ * weights.  Then, AFTER the pass over the weights (of every weight set of the call, before any coefficient is written):
+ *   SPLPAK_E_BADARG       a weight that is negative or not finite ("a weight is negative or not finite");
+ *   SPLPAK_E_UNSUPPORTED  the xtrap rule, with the message of splpak_fit_grid_*.
+ * On these `coef` is untouched.  107 with THAT FIELD's coefficients zeroed, each with a message of its own -- the reference
+ * says 107 for the same samples --: an N^_d that fails the pivot test of splpak_fit_grid_* (a singular M implies a singular
+ * N); an entry of diag(N) that is not positive (a coefficient without a sample of non-zero weight in its support); a
+ * breakdown of the iteration (p^T N p <= 0 or a scalar that is not finite).  107 with the coefficients as they stand where
+ * the refinement rule misses 1e-10.
+ * info as for splpak_fit_grid_*, except [0] = the count of non-zero weights, [4] = the smallest pivot of the
+ * preconditioner's factors, [6] = [9] = 0. */
+int32_t splpak_fit_grid_weighted_f64(int32_t ndim, const int64_t *npts, const double *axes, int32_t nfields, const double *values,
+                                     int64_t ldv, const double *weights, int64_t ldw, const double *xmin, const double *xmax,
+                                     const int32_t *nodes, double xtrap, double *coef, int64_t ldcoef,
+                                     double *info /* 10 per field, may be NULL */);
+int32_t splpak_fit_grid_weighted_f32(int32_t ndim, const int64_t *npts, const float *axes, int32_t nfields, const float *values,
+                                     int64_t ldv, const float *weights, int64_t ldw, const float *xmin, const float *xmax,
+                                     const int32_t *nodes, float xtrap, float *coef, int64_t ldcoef,
+                                     double *info /* 10 per field, may be NULL */);
+/* the same on resident data: axes, values, weights and coef are device arrays.  Not asynchronous, like splpak_fit_grid_dev_*:
+ * `stream` is synchronised for the axes, after the pass over the weights, every 5 iterations and after every refinement step. */
+int32_t splpak_fit_grid_weighted_dev_f64(int32_t ndim, const int64_t *npts /* host */, const double *axes_dev, int32_t nfields,
+                                         const double *values_dev, int64_t ldv, const double *weights_dev, int64_t ldw,
+                                         const double *xmin, const double *xmax, const int32_t *nodes, double xtrap, double *coef_dev,
+                                         int64_t ldcoef, double *info /* host, 10 per field, may be NULL */, void *stream);
+int32_t splpak_fit_grid_weighted_dev_f32(int32_t ndim, const int64_t *npts /* host */, const float *axes_dev, int32_t nfields,
+                                         const float *values_dev, int64_t ldv, const float *weights_dev, int64_t ldw,
+                                         const float *xmin, const float *xmax, const int32_t *nodes, float xtrap, float *coef_dev,
+                                         int64_t ldcoef, double *info /* host, 10 per field, may be NULL */, void *stream);
+/* Diagnostics.  One stage alone, host arrays, one field, no xtrap rule: stage 0: out[ncol] = A^T (w^2 o in[prod npts]), the
+ * right-hand side; 1: out[ncol] = N in[ncol], the operator; 2: out[ncol] = M^-1 in[ncol], the preconditioner; 3:
+ * out[sum npts + ncol] = the D marginals of w^2 (the axes back to back), then diag(N) (`in` is not read).  Status as
+ * splpak_fit_grid_weighted_f64 (ldv = prod npts, ldw = 0, ldcoef = ncol; `out` is never zeroed), then SPLPAK_E_BADARG for
+ * another stage; stages 2 and 3 also refuse a bad weight and return 107 as the fit does. */
+int32_t splpak_debug_fit_grid_weighted_stage_f64(int32_t stage, int32_t ndim, const int64_t *npts, const double *axes,
+                                                 const double *weights, const double *xmin, const double *xmax, const int32_t *nodes,
+                                                 const double *in, double *out);
+/* host counters of the calling thread's last splpak_fit_grid_weighted_* / stage call (nothing is waited for): [0] slabs of an
+ * operator pass, [1] doubles of slab scratch held, [2] spread launches, [3] axis-solve launches, [4] refinement steps of the
+ * last field, [5] conjugate-gradient iterations of the last field over all its solves (per solve: up to the first iterate
+ * within the tolerance; up to 4 more have run when the read-back sees it), [6] solves of the last field, [7] weight analyses of
+ * the call (1 with ldw == 0, nfields otherwise). */
+int32_t splpak_debug_fit_grid_weighted_stats(int64_t out8[8]);
+
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
  * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one
  * splpak_eval_* call per field -- each reading the coordinates, building the factor tables and, for a large batch on a

@@ -40,6 +40,8 @@ SYMBOLS = [
     "splpak_debug_integrate_grid_stats",
     "splpak_fit_grid_f64", "splpak_fit_grid_f32", "splpak_fit_grid_dev_f64", "splpak_fit_grid_dev_f32",
     "splpak_debug_fit_grid_stage_f64", "splpak_debug_fit_grid_stats",
+    "splpak_fit_grid_weighted_f64", "splpak_fit_grid_weighted_f32", "splpak_fit_grid_weighted_dev_f64",
+    "splpak_fit_grid_weighted_dev_f32", "splpak_debug_fit_grid_weighted_stage_f64", "splpak_debug_fit_grid_weighted_stats",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
     "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
@@ -192,6 +194,18 @@ def lib() -> C.CDLL:
     L.splpak_debug_fit_grid_stage_f64.argtypes = [i32, i32, _lp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]
     L.splpak_debug_fit_grid_stats.restype = i32
     L.splpak_debug_fit_grid_stats.argtypes = [_lp]
+    L.splpak_fit_grid_weighted_f64.restype = i32
+    L.splpak_fit_grid_weighted_f64.argtypes = [i32, _lp, _dp, i32, _dp, i64, _dp, i64, _dp, _dp, _ip, dbl, _dp, i64, _dp]
+    L.splpak_fit_grid_weighted_f32.restype = i32
+    L.splpak_fit_grid_weighted_f32.argtypes = [i32, _lp, _fp, i32, _fp, i64, _fp, i64, _fp, _fp, _ip, C.c_float, _fp, i64, _dp]
+    L.splpak_fit_grid_weighted_dev_f64.restype = i32
+    L.splpak_fit_grid_weighted_dev_f64.argtypes = [i32, _lp, vp, i32, vp, i64, vp, i64, _dp, _dp, _ip, dbl, vp, i64, _dp, vp]
+    L.splpak_fit_grid_weighted_dev_f32.restype = i32
+    L.splpak_fit_grid_weighted_dev_f32.argtypes = [i32, _lp, vp, i32, vp, i64, vp, i64, _fp, _fp, _ip, C.c_float, vp, i64, _dp, vp]
+    L.splpak_debug_fit_grid_weighted_stage_f64.restype = i32
+    L.splpak_debug_fit_grid_weighted_stage_f64.argtypes = [i32, i32, _lp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]
+    L.splpak_debug_fit_grid_weighted_stats.restype = i32
+    L.splpak_debug_fit_grid_weighted_stats.argtypes = [_lp]
     L.splpak_eval_fields_f64.restype = i32
     L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
     L.splpak_eval_fields_f32.restype = i32
@@ -637,6 +651,87 @@ def debug_fit_grid_stats():
     launches, solve launches, refinement steps of the last field, 0, 0, 0)."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_fit_grid_stats(_p(v, _lp)))
+    return tuple(int(t) for t in v)
+
+
+def fit_grid_weighted(ndim, axes, values, weights, xmin, xmax, nodes, xtrap=0.0, real32=False, ldv=None, ldw=None, ldcoef=None,
+                      coef=None):
+    """fit_grid with a weight per sample (splpak_fit_grid_weighted_*): what fit() returns for the listed samples of non-zero
+    weight, provided that fit has no constraint rows.  `values` as for fit_grid; `weights` has the shape of one field's values
+    (one array for all fields, ldw = 0) or that of `values` (a weight array per field, `ldw` apart when flat; default prod
+    npts).  A sample of weight 0 may hold NaN.  SplpakError from SPLPAK_E_BADARG for a negative or non-finite weight.
+    -> (coef, ierror, info (nfields, 10)) as fit_grid."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    npts, cat = _axes_cat(axes, dt)
+    nsamp = int(np.prod(npts)) if npts.size else 1
+    values = np.ascontiguousarray(values, dtype=dt)
+    weights = np.ascontiguousarray(weights, dtype=dt)
+    if ldv is None:
+        single = values.size == nsamp and values.ndim <= max(len(axes), 1)
+        nfields = 1 if single else (values.size // nsamp if nsamp > 0 else 1)
+        ldv_ = nsamp
+    else:
+        single = False
+        ldv_ = int(ldv)
+        nfields = max((values.size + ldv_ - nsamp) // ldv_, 1) if ldv_ > 0 else 1
+    if ldw is None:
+        if weights.size not in (nsamp, nfields * nsamp):
+            raise SplpakError("fit_grid_weighted: weights must hold one weight per sample, for one field or for every field")
+        ldw = 0 if weights.size == nsamp else nsamp
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64))) if nodes.size else 0
+    ldc = ncol if ldcoef is None else int(ldcoef)
+    if coef is None:
+        coef = np.zeros(max(nfields * ldc, 1), dtype=dt)
+    info = np.zeros((nfields, 10))
+    fn = lib().splpak_fit_grid_weighted_f32 if real32 else lib().splpak_fit_grid_weighted_f64
+    rc = _check(fn(ndim, _p(npts, _lp), _p(cat, rp), nfields, _p(values, rp), ldv_, _p(weights, rp), int(ldw), _p(xmin, rp),
+                   _p(xmax, rp), _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(info, _dp)))
+    if ldcoef is None and coef.size == nfields * ncol:
+        coef = coef[:ncol] if single else coef.reshape(nfields, ncol)
+    return coef, rc, info
+
+
+def fit_grid_weighted_dev(ndim, npts, axes, values, weights, xmin, xmax, nodes, coef, xtrap=0.0, nfields=1, ldv=None, ldw=0,
+                          ldcoef=None, stream=0):
+    """fit_grid_weighted on torch device tensors, as fit_grid_dev: `weights` in the layout of `values`, field k's from k*ldw
+    on (0: one array for all fields).  -> (ierror, info (nfields, 10))."""
+    npts = np.ascontiguousarray(npts, dtype=np.int64)
+    real32 = str(axes.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    info = np.zeros((int(nfields), 10))
+    fn = lib().splpak_fit_grid_weighted_dev_f32 if real32 else lib().splpak_fit_grid_weighted_dev_f64
+    rc = _check(fn(ndim, _p(npts, _lp), axes.data_ptr(), int(nfields), values.data_ptr(),
+                   int(np.prod(npts)) if ldv is None else int(ldv), weights.data_ptr(), int(ldw), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), float(xtrap), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(info, _dp),
+                   C.c_void_p(stream)))
+    return rc, info
+
+
+def debug_fit_grid_weighted_stage(stage, ndim, axes, weights, data, xmin, xmax, nodes):
+    """One stage of the weighted grid fit alone (splpak_debug_fit_grid_weighted_stage_f64): 0 -> A^T (w^2 o data), 1 -> N data,
+    2 -> M^-1 data (arrays of ncol); 3 -> the D marginals of w^2, then diag(N) (sum npts + ncol; `data` is not read).
+    -> (array, ierror)."""
+    npts, cat = _axes_cat(axes, np.float64)
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    data = None if data is None else np.ascontiguousarray(data, dtype=np.float64)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes)
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    out = np.zeros(ncol + (int(np.sum(npts)) if int(stage) == 3 else 0))
+    rc = _check(lib().splpak_debug_fit_grid_weighted_stage_f64(int(stage), ndim, _p(npts, _lp), _p(cat, _dp), _p(weights, _dp),
+                                                               _p(xmin, _dp), _p(xmax, _dp), _p(nodes, _ip), _p(data, _dp), _p(out, _dp)))
+    return out, rc
+
+
+def debug_fit_grid_weighted_stats():
+    """Host counters of this thread's last fit_grid_weighted call: (slabs of an operator pass, doubles of slab scratch held,
+    spread launches, axis-solve launches, refinement steps of the last field, its CG iterations over all solves, its CG
+    solves, weight analyses of the call)."""
+    v = np.zeros(8, dtype=np.int64)
+    _check(lib().splpak_debug_fit_grid_weighted_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)
 
 

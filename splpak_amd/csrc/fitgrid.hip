@@ -30,8 +30,7 @@
 // one loads them: plain sequential accumulation) and the entry form change no bit.  No floating-point atomics; every sum has
 // one owner.  The residual norm follows the same rule: per (lane position, window start s) the terms w^2 r^2 of the
 // coordinates with that window start in table order, then fixed-order sums over s, over blocks of 4096 lanes and over the blocks.
-#include "fitgrid.hpp"
-#include "evalgrid.hpp"
+#include "fitgriddev.hpp"
 #include "../../include/splpak_hip.h"
 
 #include <algorithm>
@@ -48,6 +47,46 @@ namespace splpak {
 static const char *XTRAP_MESSAGE =
     "the sample has data-sparse nodes (or coordinates outside the counting range): constraint rows are not separable; "
     "list the points and use the point fit, or pass xtrap = 0";
+
+const char *fit_grid_xtrap_message() { return XTRAP_MESSAGE; }
+
+// a.nrm -> a.chol, a.minpiv, a.spd: band Cholesky, half-width 3; the rank test on the pivot before its square root
+static void band_cholesky(FitGridAxis &a)
+{
+    const int nod = a.nod;
+    double maxdiag = 0.0;
+    for (int j = 0; j < nod; ++j) maxdiag = std::max(maxdiag, a.nrm[(size_t)j * 4]);
+    const double floor_piv = (double)nod * std::numeric_limits<double>::epsilon() * maxdiag;
+    a.minpiv = std::numeric_limits<double>::infinity();
+    a.spd = true;
+    auto L = [&](int r, int c) -> double & { return a.chol[(size_t)r * 4 + (r - c)]; };
+    for (int j = 0; j < nod && a.spd; ++j) {
+        const int lo = j - 3 > 0 ? j - 3 : 0;
+        for (int m = lo; m < j; ++m) {
+            double v = a.nrm[(size_t)j * 4 + (j - m)];
+            for (int q = lo; q < m; ++q) v -= L(j, q) * L(m, q);
+            L(j, m) = v / L(m, m);
+        }
+        double piv = a.nrm[(size_t)j * 4];
+        for (int q = lo; q < j; ++q) piv -= L(j, q) * L(j, q);
+        a.spd = piv > 0.0 && piv >= floor_piv;      // (false for a NaN)
+        if (!(a.minpiv <= piv)) a.minpiv = piv;
+        L(j, j) = a.spd ? std::sqrt(piv) : 1.0;
+    }
+}
+
+// 0, or 107 with the message that names the first axis whose normal matrix failed the pivot test
+static int axes_spd(const FitGridHost &h)
+{
+    for (int d = 0; d < h.g.ndim; ++d)
+        if (!h.ax[d].spd) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "the normal matrix of axis %d is not positive definite (too few distinct coordinates with a non-zero weight?)", d + 1);
+            set_error(buf);
+            return 107;
+        }
+    return 0;
+}
 
 static int fit_grid_host_run(const Grid &g, const int64_t *npts, const double *axes, const double *waxes, double xtrap, FitGridHost &h)
 {
@@ -106,26 +145,7 @@ static int fit_grid_host_run(const Grid &g, const int64_t *npts, const double *a
             std::vector<long long> cur(a.start);
             for (long long i = 0; i < n; ++i) a.order[(size_t)cur[(size_t)a.ws[(size_t)i]]++] = i;
         }
-        // band Cholesky, half-width 3; the rank test on the pivot before its square root
-        double maxdiag = 0.0;
-        for (int j = 0; j < nod; ++j) maxdiag = std::max(maxdiag, a.nrm[(size_t)j * 4]);
-        const double floor_piv = (double)nod * std::numeric_limits<double>::epsilon() * maxdiag;
-        a.minpiv = std::numeric_limits<double>::infinity();
-        a.spd = true;
-        auto L = [&](int r, int c) -> double & { return a.chol[(size_t)r * 4 + (r - c)]; };
-        for (int j = 0; j < nod && a.spd; ++j) {
-            const int lo = j - 3 > 0 ? j - 3 : 0;
-            for (int m = lo; m < j; ++m) {
-                double v = a.nrm[(size_t)j * 4 + (j - m)];
-                for (int q = lo; q < m; ++q) v -= L(j, q) * L(m, q);
-                L(j, m) = v / L(m, m);
-            }
-            double piv = a.nrm[(size_t)j * 4];
-            for (int q = lo; q < j; ++q) piv -= L(j, q) * L(j, q);
-            a.spd = piv > 0.0 && piv >= floor_piv;      // (false for a NaN)
-            if (!(a.minpiv <= piv)) a.minpiv = piv;
-            L(j, j) = a.spd ? std::sqrt(piv) : 1.0;
-        }
+        band_cholesky(a);
         if (xtrap != 0.0 && separable) {
             double sum = 0.0, least = std::numeric_limits<double>::infinity();
             for (int j = 0; j < nod; ++j) {
@@ -142,14 +162,7 @@ static int fit_grid_host_run(const Grid &g, const int64_t *npts, const double *a
         set_error(XTRAP_MESSAGE);
         return SPLPAK_E_UNSUPPORTED;
     }
-    for (int d = 0; d < D; ++d)
-        if (!h.ax[d].spd) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "the normal matrix of axis %d is not positive definite (too few distinct coordinates with a non-zero weight?)", d + 1);
-            set_error(buf);
-            return 107;
-        }
-    return 0;
+    return axes_spd(h);
 }
 
 // (Placed on a 64-byte boundary: the per-coordinate loop of fit_grid_host_run, inlined here, takes 15 ns an iteration, and the
@@ -166,26 +179,34 @@ int fit_grid_host(const Grid &g, const int64_t *npts, const double *axes, const 
     }
 }
 
+// The factors again for other axis weights, given SQUARED (fitgridw.hip: the scaled marginals of a weight map); the window
+// values and the table order stay.  N_d is summed in the order fit_grid_host_run sums it.
+int fit_grid_host_reweight(FitGridHost &h, const double *w2axes)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    long long off = 0;
+    for (int d = 0; d < h.g.ndim; ++d) {
+        FitGridAxis &a = h.ax[d];
+        a.nrm.assign((size_t)a.nod * 4, 0.0);
+        a.chol.assign((size_t)a.nod * 4, 0.0);
+        a.nonzero = 0;
+        for (long long i = 0; i < a.n; ++i) {
+            const double *b = &a.b[(size_t)i * 4];
+            const double w2 = w2axes[off + i];
+            const int ws = a.ws[(size_t)i];
+            a.w2[(size_t)i] = w2;
+            a.nonzero += w2 != 0.0 ? 1 : 0;
+            for (int r = 0; r < 4; ++r)
+                for (int c = 0; c <= r; ++c) a.nrm[(size_t)(ws + r) * 4 + (r - c)] += w2 * b[r] * b[c];
+        }
+        off += a.n;
+        band_cholesky(a);
+    }
+    h.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return axes_spd(h);
+}
+
 // ---- spread ----------------------------------------------------------------------------------------------------------
-struct SpreadArgs {
-    long long inner, np, outer;      // in[i + inner (c + np o)], c = a coordinate of this axis; out[i + inner (j + nod o)]
-    long long pa, pb;                // the table positions of this launch
-    int nod, nbk, nblk;              // nodes, nodes per block, blocks
-    int cont;                        // the running sums continue from `out` (a later slab)
-    const double *G;                 // [np][4] w^2 * window values, table order
-    const int *ws;                   // [np] window starts, table order
-    const long long *idx;            // [np] original index of a table position
-    const long long *start;          // [nod - 2]
-    // the residual pass alone: in = the samples, indexed by original index; sub = A C of the slab, indexed by p - pa
-    const double *w2s;               // [np] squared weights of this axis, table order
-    const double *w2lo[MAXD];        // squared weights of the dimensions below, original order
-    long long nlo[MAXD];
-    int nlow;
-};
-
-constexpr long long SPREAD_WAVE_FORM = 128;      // lane positions from which a pass takes the wave form
-constexpr int SPREAD_BATCH = 8;                  // samples a thread asks for at a time, one batch ahead of their use
-
 // The lane positions of a pass are its (i, o) pairs, i fastest: inner * outer of them.  UNI (from SPREAD_WAVE_FORM lane
 // positions on): a wave owns 64 consecutive ones and ONE node block, so the walk over the table is the same in every lane
 // (scalar loads of the table entries, no divergence); where `inner` is short the lanes run on into o (the pass of dimension 1:
@@ -307,11 +328,16 @@ static hipError_t launch_spread(const SpreadArgs &a, const TI *in, const double 
     return hipGetLastError();
 }
 
+hipError_t launch_spread_plain(const SpreadArgs &a, const double *in, double *out, hipStream_t st)
+{
+    return launch_spread<double, false>(a, in, nullptr, out, nullptr, st);
+}
+
 // Nodes per block: the largest of 64, 32, .. that still gives the pass 8192 waves (32 per CU: a wave's walk is a chain of
 // memory waits, so what hides them is waves); a pass that misses that even with one node per block takes 1, and one of fewer
 // than 2048 waves in all, where nothing matters, 4.  No bit of the result depends on it, which the diagnostic option
 // fit_grid_node_block (1 .. 64) lets a test show.
-static int node_block(long long inner, long long outer, int nod)
+int fit_grid_node_block(long long inner, long long outer, int nod)
 {
     const long long forced = option_ll("SPLPAK_FIT_GRID_NODE_BLOCK", 0, 0, 64);
     if (forced > 0) return (int)forced;
@@ -474,44 +500,30 @@ fit_store_kernel(const double *__restrict__ x, T *__restrict__ coef, int n)
     if (i < n) coef[i] = (T)x[i];      // REAL32: the one rounding
 }
 
+template <typename T>
+hipError_t launch_fit_store(const double *x, T *coef, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL((fit_store_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, coef, n);
+    return hipGetLastError();
+}
+template hipError_t launch_fit_store<double>(const double *, double *, int, hipStream_t);
+template hipError_t launch_fit_store<float>(const double *, float *, int, hipStream_t);
+
 // ---- device side of a call -------------------------------------------------------------------------------------------
 static thread_local DevScratch<1> g_fscratch;
-static thread_local long long t_stats[8];
+
+DevScratch<1> &fit_grid_scratch() { return g_fscratch; }
+thread_local long long t_fit_grid_stats[8];
 
 void fit_grid_stats(long long out8[8])
 {
-    for (int k = 0; k < 8; ++k) out8[k] = t_stats[k];
+    for (int k = 0; k < 8; ++k) out8[k] = t_fit_grid_stats[k];
 }
 
 void fit_grid_scratch_shutdown() { g_fscratch.release(); }
 
-namespace {
-
-// Everything a call keeps on the device, carved out of one buffer (offsets in doubles).
-struct Layout {
-    long long off[MAXD + 1];      // table entries of every axis (prefix of npts)
-    long long offn[MAXD + 1];     // prefix of nodes
-    long long offs[MAXD + 1];     // prefix of nodes - 2
-    long long G, fac, w2o, w2s, idx, start, chol, wsS, wstE;      // tables
-    long long tables;                                             // doubles of tables (uploaded in one copy)
-    long long small, X, R, A, B, sq, rows, part, AC, stageV, stageC, total;
-    long long szA, szB, q, nslab;  // table positions of the last dimension per slab; slabs
-};
-
-struct Device {
-    const FitGridHost &h;
-    Layout L;
-    double *base = nullptr;
-    hipStream_t st;
-    int D, last;
-    Device(const FitGridHost &hh, hipStream_t s) : h(hh), st(s), D(hh.g.ndim), last(hh.g.ndim - 1) {}
-    double *at(long long o) const { return base + o; }
-};
-
-}  // namespace
-
 // sizes; false: beyond what can be addressed
-static bool plan_layout(const FitGridHost &h, bool refine, long long stage_values_bytes, long long stage_coef_bytes, Layout &L)
+static bool plan_layout(const FitGridHost &h, bool refine, long long stage_values_bytes, long long stage_coef_bytes, long long extra, Layout &L)
 {
     const int D = h.g.ndim, last = D - 1;
     long long ntab = 0, nn = 0, ns = 0;
@@ -558,6 +570,8 @@ static bool plan_layout(const FitGridHost &h, bool refine, long long stage_value
     }
     L.stageV = take((stage_values_bytes + 7) / 8);
     L.stageC = take((stage_coef_bytes + 7) / 8);
+    if (extra < 0 || extra > (1LL << 58)) return false;
+    L.extra = take(extra);
     L.total = o;
     return o < (1LL << 59);
 }
@@ -592,7 +606,7 @@ static void fill_tables(const FitGridHost &h, const Layout &L, std::vector<doubl
     }
 }
 
-static SpreadArgs spread_args(const Device &dv, int d)
+SpreadArgs spread_args(const Device &dv, int d)
 {
     const FitGridHost &h = dv.h;
     const Layout &L = dv.L;
@@ -605,7 +619,7 @@ static SpreadArgs spread_args(const Device &dv, int d)
     a.pa = 0;
     a.pb = a.np;
     a.nod = h.ax[d].nod;
-    a.nbk = node_block(a.inner, a.outer, a.nod);
+    a.nbk = fit_grid_node_block(a.inner, a.outer, a.nod);
     a.nblk = (a.nod + a.nbk - 1) / a.nbk;
     a.G = dv.at(L.G) + 4 * L.off[d];
     a.ws = reinterpret_cast<const int *>(dv.at(L.wsS)) + L.off[d];
@@ -621,15 +635,16 @@ static SpreadArgs spread_args(const Device &dv, int d)
 }
 
 // the passes below the last dimension: cur (the last dimension's result) -> dst[ncol]
-static hipError_t spread_rest(const Device &dv, const double *cur, double *dst)
+hipError_t spread_rest(const Device &dv, const double *cur, double *dst, const double *tables)
 {
     const Layout &L = dv.L;
     int k = 1;
     for (int d = dv.last - 1; d >= 0; --d, ++k) {
         double *out = d == 0 ? dst : dv.at(k % 2 == 0 ? L.A : L.B);
-        const SpreadArgs a = spread_args(dv, d);
+        SpreadArgs a = spread_args(dv, d);
+        if (tables) a.G = tables + 4 * L.off[d];
         if (hipError_t e = launch_spread<double, false>(a, cur, nullptr, out, nullptr, dv.st); e != hipSuccess) return e;
-        ++t_stats[2];
+        ++t_fit_grid_stats[2];
         cur = out;
     }
     return hipSuccess;
@@ -642,48 +657,59 @@ static hipError_t spread_values(const Device &dv, const TI *values, double *dst)
     double *out = dv.last == 0 ? dst : dv.at(dv.L.A);
     const SpreadArgs a = spread_args(dv, dv.last);
     if (hipError_t e = launch_spread<TI, false>(a, values, nullptr, out, nullptr, dv.st); e != hipSuccess) return e;
-    ++t_stats[2];
-    return spread_rest(dv, out, dst);
+    ++t_fit_grid_stats[2];
+    return spread_rest(dv, out, dst, nullptr);
+}
+
+// small[2] = the sum of sq[inner][nod], the per-(lane position, window start) sums of a residual pass, in the header's order
+hipError_t residual_norm(const Device &dv, long long inner, int nod)
+{
+    const Layout &L = dv.L;
+    const long long nb = (inner + 255) / 256, np = (inner + 4095) / 4096;
+    if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fit_ssq_rows_kernel, dim3((unsigned)nb), dim3(256), 0, dv.st, dv.at(L.sq), inner, nod, dv.at(L.rows));
+    hipLaunchKernelGGL(fit_block_sum_kernel, dim3((unsigned)np), dim3(256), 0, dv.st, dv.at(L.rows), inner, dv.at(L.part));
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return launch_sum_fixed(dv.at(L.part), np, dv.at(L.small) + 2, dv.st);
+}
+
+// Layout::AC = A x at the table positions pa .. pb - 1 of the last dimension (a slab: at most Layout::q of them)
+hipError_t eval_slab(const Device &dv, const double *x, long long pa, long long pb)
+{
+    const FitGridHost &h = dv.h;
+    const Layout &L = dv.L;
+    GridShape s;      // (its table offsets are Layout::off: the prefix of npts)
+    if (!grid_shape(dv.D, h.npts, s)) return hipErrorInvalidValue;
+    s.npts[dv.last] = pb - pa;
+    s.off[dv.last] += pa;
+    const int *wst = reinterpret_cast<const int *>(dv.at(L.wstE));
+    return launch_eval_grid_tables<double, double>(h.g, s, dv.at(L.fac), wst, x, dv.at(L.AC), nullptr, dv.st);
 }
 
 // dst[ncol] = the spread of values - A x, slab by slab; small[2] = the sum of the squared weighted residuals
 template <typename TI>
 static hipError_t spread_residual(const Device &dv, const TI *values, const double *x, double *dst)
 {
-    const FitGridHost &h = dv.h;
     const Layout &L = dv.L;
     const int last = dv.last;
     double *out = last == 0 ? dst : dv.at(L.A);
     SpreadArgs a = spread_args(dv, last);
     if (hipError_t e = hipMemsetAsync(dv.at(L.sq), 0, sizeof(double) * (size_t)(a.inner * a.nod), dv.st); e != hipSuccess) return e;
-    GridShape gs;      // (its table offsets are Layout::off: the prefix of npts)
-    if (!grid_shape(dv.D, h.npts, gs)) return hipErrorInvalidValue;
-    const int *wst = reinterpret_cast<const int *>(dv.at(L.wstE));
     for (long long pa = 0, k = 0; pa < a.np; pa += L.q, ++k) {
         const long long pb = pa + L.q < a.np ? pa + L.q : a.np;
-        GridShape s = gs;
-        s.npts[last] = pb - pa;
-        s.off[last] = gs.off[last] + pa;
-        if (hipError_t e = launch_eval_grid_tables<double, double>(h.g, s, dv.at(L.fac), wst, x, dv.at(L.AC), nullptr, dv.st); e != hipSuccess) return e;
+        if (hipError_t e = eval_slab(dv, x, pa, pb); e != hipSuccess) return e;
         a.pa = pa;
         a.pb = pb;
         a.cont = k > 0;
         if (hipError_t e = launch_spread<TI, true>(a, values, dv.at(L.AC), out, dv.at(L.sq), dv.st); e != hipSuccess) return e;
-        ++t_stats[2];
+        ++t_fit_grid_stats[2];
     }
-    {
-        const long long nb = (a.inner + 255) / 256, np = (a.inner + 4095) / 4096;
-        if (nb > 0x7fffffffLL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(fit_ssq_rows_kernel, dim3((unsigned)nb), dim3(256), 0, dv.st, dv.at(L.sq), a.inner, a.nod, dv.at(L.rows));
-        hipLaunchKernelGGL(fit_block_sum_kernel, dim3((unsigned)np), dim3(256), 0, dv.st, dv.at(L.rows), a.inner, dv.at(L.part));
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        if (hipError_t e = launch_sum_fixed(dv.at(L.part), np, dv.at(L.small) + 2, dv.st); e != hipSuccess) return e;
-    }
-    return spread_rest(dv, out, dst);
+    if (hipError_t e = residual_norm(dv, a.inner, a.nod); e != hipSuccess) return e;
+    return spread_rest(dv, out, dst, nullptr);
 }
 
 // x[ncol] <- (N_1^-1 x ... x N_D^-1) x
-static hipError_t solve_all(const Device &dv, double *x)
+hipError_t solve_all(const Device &dv, double *x)
 {
     const FitGridHost &h = dv.h;
     long long inner = 1;
@@ -696,17 +722,17 @@ static hipError_t solve_all(const Device &dv, double *x)
         else if (nod <= 64) hipLaunchKernelGGL(fit_solve_reg_kernel<64>, gr, bl, 0, dv.st, chol, nod, inner, lines, x);
         else hipLaunchKernelGGL(fit_solve_kernel, gr, bl, 0, dv.st, chol, nod, inner, lines, x);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        ++t_stats[3];
+        ++t_fit_grid_stats[3];
         inner *= nod;
     }
     return hipSuccess;
 }
 
 // the scratch of the call and its tables on the device; 0 or a status
-static int device_begin(Device &dv, bool refine, long long stage_values_bytes, long long stage_coef_bytes)
+int device_begin(Device &dv, bool refine, long long stage_values_bytes, long long stage_coef_bytes, long long extra)
 {
-    for (int k = 0; k < 8; ++k) t_stats[k] = 0;
-    if (!plan_layout(dv.h, refine, stage_values_bytes, stage_coef_bytes, dv.L)) {
+    for (int k = 0; k < 8; ++k) t_fit_grid_stats[k] = 0;
+    if (!plan_layout(dv.h, refine, stage_values_bytes, stage_coef_bytes, extra, dv.L)) {
         set_error("the grid fit's intermediates are beyond what can be addressed");
         return SPLPAK_E_NOMEM;
     }
@@ -728,8 +754,8 @@ static int device_begin(Device &dv, bool refine, long long stage_values_bytes, l
     SPLPAK_HIP_TRY(hipMemcpyAsync(dv.base, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice, dv.st), SPLPAK_E_NODEVICE);
     SPLPAK_HIP_TRY(hipStreamSynchronize(dv.st), SPLPAK_E_NODEVICE);
     if (refine) {
-        t_stats[0] = dv.L.nslab;
-        t_stats[1] = dv.L.stageV - dv.L.AC;      // the doubles of A C
+        t_fit_grid_stats[0] = dv.L.nslab;
+        t_fit_grid_stats[1] = dv.L.stageV - dv.L.AC;      // the doubles of A C
     }
     return 0;
 }
@@ -740,11 +766,10 @@ static int fit_grid_device_run(const FitGridHost &h, int nfields, const T *value
 {
     const int nominal = (int)option_ll("SPLPAK_FIT_GRID_REFINE", 4, 0, 1000000);
     const int hard = nominal == 0 ? 0 : (nominal > 30 ? nominal : 30);
-    const double tol = 1e-11;
     const int ncol = h.g.ncol;
     Device dv(h, st);
     const ScratchUse<1> use{g_fscratch, st};
-    if (int r = device_begin(dv, hard > 0, on_host ? (long long)sizeof(T) * h.nsamp : 0, on_host ? (long long)sizeof(T) * ncol : 0)) return r;
+    if (int r = device_begin(dv, hard > 0, on_host ? (long long)sizeof(T) * h.nsamp : 0, on_host ? (long long)sizeof(T) * ncol : 0, 0)) return r;
     const Layout &L = dv.L;
     double *X = dv.at(L.X), *R = dv.at(L.R), *small = dv.at(L.small);
     int status = 0;
@@ -761,31 +786,23 @@ static int fit_grid_device_run(const FitGridHost &h, int nfields, const T *value
         SPLPAK_HIP_TRY(solve_all(dv, X), SPLPAK_E_NODEVICE);
         // the fit's own rule (planfit.hip refinement_advance): stop when the estimated remaining error is below tol, go on
         // while the corrections contract, fail (107) when that leaves an estimate above the parity bar
-        int steps = 0;
-        double last_rel = 0.0, prev_rel = std::numeric_limits<double>::infinity(), ratio = 0.0, ssq = 0.0;
-        bool converged = hard == 0;
-        for (int it = 0; it < hard && !converged; ++it) {
+        RefineRule rule;
+        double ssq = 0.0;
+        rule.converged = hard == 0;
+        for (int it = 0; it < hard && !rule.converged; ++it) {
             SPLPAK_HIP_TRY(spread_residual<T>(dv, vk, X, R), SPLPAK_E_NODEVICE);
             SPLPAK_HIP_TRY(solve_all(dv, R), SPLPAK_E_NODEVICE);
             SPLPAK_HIP_TRY(launch_axpy_absmax(ncol, X, R, small, st), SPLPAK_E_NODEVICE);
             double am[3];
             SPLPAK_HIP_TRY(hipMemcpyAsync(am, small, sizeof am, hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
             SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
-            ++steps;
             ssq = am[2];
-            last_rel = am[1] > 0.0 ? am[0] / am[1] : 0.0;
-            if (am[0] != am[0] || am[1] != am[1]) last_rel = std::numeric_limits<double>::quiet_NaN();
-            if (!(last_rel == last_rel)) break;
-            if (last_rel <= tol) { converged = true; break; }
-            if (it >= 1) {
-                ratio = last_rel / prev_rel;
-                if (ratio < 0.9 && last_rel * ratio / (1.0 - ratio) <= tol) { converged = true; break; }
-                if (ratio >= 0.9) { converged = last_rel <= 1e-10; break; }
-            }
-            prev_rel = last_rel;
+            if (rule.advance(it, am)) break;
         }
-        if (!converged) {
-            const double est = steps >= 2 && ratio > 0.0 && ratio < 1.0 ? last_rel * ratio / (1.0 - ratio) : last_rel;
+        const int steps = rule.steps;
+        const double last_rel = rule.last_rel;
+        if (!rule.converged) {
+            const double est = rule.estimate();
             if (!(est <= 1e-10)) {
                 char buf[200];
                 snprintf(buf, sizeof buf, "grid fit: the refinement of field %d left an estimated error of %.2e after %d steps", k, est, steps);
@@ -803,7 +820,7 @@ static int fit_grid_device_run(const FitGridHost &h, int nfields, const T *value
             SPLPAK_HIP_TRY(hipGetLastError(), SPLPAK_E_NODEVICE);
         }
         SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
-        t_stats[4] = steps;
+        t_fit_grid_stats[4] = steps;
         if (info) {
             double *f = info + 10 * (long long)k;
             double rows = 1.0, minpiv = std::numeric_limits<double>::infinity();
@@ -841,7 +858,7 @@ int fit_grid_stage(const FitGridHost &h, int stage, const double *in, double *ou
         const long long nin = stage == 0 ? h.nsamp : ncol;
         Device dv(h, nullptr);
         const ScratchUse<1> use{g_fscratch, nullptr};
-        if (int r = device_begin(dv, false, 8 * nin, 0)) return r;
+        if (int r = device_begin(dv, false, 8 * nin, 0, 0)) return r;
         double *X = dv.at(dv.L.X), *sv = dv.at(dv.L.stageV);
         if (stage == 0) {
             SPLPAK_HIP_TRY(hipMemcpy(sv, in, sizeof(double) * (size_t)nin, hipMemcpyHostToDevice), SPLPAK_E_NODEVICE);

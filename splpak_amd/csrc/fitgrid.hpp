@@ -37,6 +37,10 @@ struct FitGridHost {
 // 107 (an axis whose normal matrix is not numerically positive definite); SPLPAK_E_NOMEM.  Touches no device.
 int fit_grid_host(const Grid &g, const int64_t *npts, const double *axes, const double *waxes, double xtrap, FitGridHost &h);
 
+// The normal matrices and factors of h again for other axis weights, given SQUARED, one per axis coordinate (the axes back
+// to back); the window values and the table order stay.  0; 107 as fit_grid_host.
+int fit_grid_host_reweight(FitGridHost &h, const double *w2axes);
+
 // The device part.  Field k's samples at values + k*ldv, its coefficients to coef + k*ldcoef; `on_host`: both are host
 // arrays and are staged field by field (the words between the fields are neither read nor written), else device arrays.
 // info: 10 per field or null.  0; 107 (the refinement missed 1e-10); SPLPAK_E_NOMEM; SPLPAK_E_NODEVICE.
@@ -51,5 +55,17 @@ int fit_grid_stage(const FitGridHost &h, int stage, const double *in, double *ou
 // host counters of the calling thread's last fit_grid_device / fit_grid_stage: slabs of a residual pass [0], doubles of
 // residual scratch held [1], spread launches [2], solve launches [3], refinement steps of the last field [4], 0 [5..7]
 void fit_grid_stats(long long out8[8]);
+
+// ---- fitgridw.hip: a weight per sample (splpak_fit_grid_weighted_*)
+// h: the tables of fit_grid_host WITHOUT axis weights and with xtrap = 0 (changed: the factors become those of the
+// preconditioner of the last weight set); axes: the host copy the tables were made from (the xtrap rule counts from it).
+// Field k's weights at weights + k*ldw in the layout of its samples, ldw = 0: one set for all fields.  Status as the header
+// gives it; synchronises st.
+template <typename T>
+int fit_grid_weighted_device(FitGridHost &h, const double *axes, double xtrap, int nfields, const T *values, long long ldv,
+                             const T *weights, long long ldw, T *coef, long long ldcoef, double *info, bool on_host, hipStream_t st);
+// One stage alone, host arrays, one field (the header: right-hand side, operator, preconditioner, marginals and diagonal)
+int fit_grid_weighted_stage(FitGridHost &h, const double *axes, int stage, const double *weights, const double *in, double *out);
+void fit_grid_weighted_stats(long long out8[8]);
 
 }  // namespace splpak

@@ -22,6 +22,7 @@ const Known KNOWN[] = {
     {"SPLPAK_FIT_GRID_NODE_BLOCK", 0},
     {"SPLPAK_FIT_GRID_REFINE", 1},
     {"SPLPAK_FIT_GRID_SCRATCH_MB", 1},
+    {"SPLPAK_FIT_GRID_WEIGHTED_MAXIT", 1},
     {"SPLPAK_GRAM_SCRATCH_MB", 1},
     {"SPLPAK_GRAM_VALU", 0},
     {"SPLPAK_INTEGRATE_SCRATCH_MB", 1},

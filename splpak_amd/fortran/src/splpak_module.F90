@@ -72,6 +72,7 @@ module splpak_module
         private
         generic,public   :: initialize    => splcc, splcw        !! fit
         procedure,public :: initialize_grid => splpak_fit_grid      !! fit of samples on a tensor-product grid of points (additive)
+        procedure,public :: initialize_grid_weighted => splpak_fit_grid_weighted   !! the same with a weight per sample (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
@@ -186,6 +187,19 @@ module splpak_module
             type(c_ptr),value :: npts, axes, waxes, values, xmin, xmax, nodes, coef, info
             real(wp),value :: xtrap
         end function c_fit_grid
+#ifdef REAL32
+        integer(c_int32_t) function c_fit_grid_weighted(ndim,npts,axes,nfields,values,ldv,weights,ldw,xmin,xmax,nodes,xtrap,coef, &
+                                                        ldcoef,info) bind(C,name='splpak_fit_grid_weighted_f32')
+#else
+        integer(c_int32_t) function c_fit_grid_weighted(ndim,npts,axes,nfields,values,ldv,weights,ldw,xmin,xmax,nodes,xtrap,coef, &
+                                                        ldcoef,info) bind(C,name='splpak_fit_grid_weighted_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr, wp
+            integer(c_int32_t),value :: ndim, nfields
+            integer(c_int64_t),value :: ldv, ldw, ldcoef
+            type(c_ptr),value :: npts, axes, values, weights, xmin, xmax, nodes, coef, info
+            real(wp),value :: xtrap
+        end function c_fit_grid_weighted
 #ifdef REAL32
         integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
                                                   bind(C,name='splpak_eval_fields_f32')
@@ -594,6 +608,98 @@ module splpak_module
             call report_library_failure(ierror,'initialize_grid')
         end if
     end subroutine splpak_fit_grid
+
+    !> `initialize_grid` with a weight per sample -- a mask, dead pixels, a variance map: `weights` holds one row weight per
+    !! sample in the layout of `values` (the normal equations see its square); a sample whose weight is exactly 0 is left out
+    !! and may hold NaN.  Returns what `initialize` returns for the listed samples of non-zero weight, provided that fit has no
+    !! constraint rows (include/splpak_hip.h, splpak_fit_grid_weighted_f64: a conjugate-gradient iteration whose operator is
+    !! one evaluation and one spread pass over the samples; ierror = -3 for a negative or non-finite weight, -4 where xtrap /= 0
+    !! meets data-sparse nodes).  Under set_host(.true.), for ndim > 4, in the -DREAL128 build and with SPLPAK_HOST_IF_NO_GPU=1
+    !! the samples of non-zero weight are listed and the module's host solver fits them, as `initialize_grid` does.
+    subroutine splpak_fit_grid_weighted(me,ndim,npts,axes,values,weights,xmin,xmax,nodes,xtrap,coef,ncf,ierror)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, ncf
+        integer,intent(in) :: npts(*)
+        real(wp),intent(in),target :: axes(*)
+        real(wp),intent(in),target :: values(*), weights(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(in) :: xtrap
+        real(wp),intent(out),target :: coef(*)
+        integer,intent(out) :: ierror
+        integer(c_int32_t) :: rc
+        integer(c_int64_t),target :: np64(max(ndim,1))
+        integer(c_int64_t) :: nsamp, ip, nl
+        integer :: idim, ntab, k(max(ndim,1)), off(max(ndim,1))
+        logical :: listed
+        real(wp),allocatable,target :: xl(:,:), wl(:), yl(:)
+        real(wp),target :: wk(1)
+        me%mdim = ndim
+        me%token = 0                          ! (whatever this object could refit is being replaced)
+        me%fit_fell_to_host = .false.
+        np64 = 0
+        nsamp = 1
+        ntab = 0
+        do idim = 1, ndim
+            np64(idim) = int(npts(idim),c_int64_t)
+            off(idim) = ntab
+            ntab = ntab + max(npts(idim),0)
+            nsamp = nsamp*max(np64(idim),0_c_int64_t)
+        end do
+        rc = -1
+        listed = host_takes(me,ndim)
+#ifndef REAL128
+        if (.not. listed) then
+            rc = c_fit_grid_weighted(int(ndim,c_int32_t), c_loc(np64), c_loc(axes), 1_c_int32_t, c_loc(values), nsamp, &
+                                     c_loc(weights), 0_c_int64_t, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, c_loc(coef), &
+                                     int(ncf,c_int64_t), c_loc(me%info))
+            if (host_if_no_gpu(int(rc))) then
+                listed = .true.
+                me%fit_fell_to_host = .true.
+            end if
+        end if
+#endif
+        if (listed) then                      ! the host solver on the listed samples of non-zero weight, first dimension fastest
+            ierror = 0
+            do idim = 1, ndim
+                if (npts(idim) < 1) nsamp = 0
+            end do
+            allocate(xl(max(ndim,1),max(nsamp,1_c_int64_t)), wl(max(nsamp,1_c_int64_t)), yl(max(nsamp,1_c_int64_t)))
+            k = 1
+            nl = 0
+            do ip = 1, nsamp
+                if (weights(ip) < 0.0_wp .or. weights(ip) /= weights(ip) .or. abs(weights(ip)) > huge(1.0_wp)) then
+                    ierror = -3
+                    call report(ierror,' initialize_grid_weighted - a weight is negative or not finite')
+                    return
+                end if
+                if (weights(ip) /= 0.0_wp) then
+                    nl = nl + 1
+                    do idim = 1, ndim
+                        xl(idim,nl) = axes(off(idim) + k(idim))
+                    end do
+                    wl(nl) = weights(ip)
+                    yl(nl) = values(ip)
+                end if
+                idim = 1
+                do while (idim <= ndim)
+                    k(idim) = k(idim) + 1
+                    if (k(idim) <= npts(idim)) exit
+                    k(idim) = 1
+                    idim = idim + 1
+                end do
+            end do
+            call fit_on_host(me,ndim,c_loc(xl),max(ndim,1),c_loc(yl),c_loc(wl),int(nl),c_loc(xmin),c_loc(xmax),nodes,xtrap, &
+                             coef,ncf,wk,1,ierror)
+            return
+        end if
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'initialize_grid_weighted')
+        end if
+    end subroutine splpak_fit_grid_weighted
 
     !> New values on the points of this object's last `initialize`: several fields sampled at the same points (the
     !! components of a velocity, a time series on a fixed sensor layout, bootstrap replicas) cost one `initialize` and one
