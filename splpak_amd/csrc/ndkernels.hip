@@ -148,6 +148,11 @@ nd_whoami_kernel(unsigned *__restrict__ map)
 // it each, or one 16 x 16 tile each) -- for launches of a few hundred items, which otherwise leave most of the chip's 1 024
 // SIMDs idle while one wave per item works through its 1 024 MFMAs of 64 cycles each (27 us per K = 256, measured 30-57 us
 // per launch at BASELINE config 2).  Every element sees the same sequence of operations: bitwise the same result.
+// A front's LAST Schur pass (job.pm != NULL) does not store its tile: it adds it into the parent through the child -> parent
+// map (extend-add).  That tail fetches the map first and then the parent's entries in batches of 4 N or 8 N per lane -- loads,
+// ONE wait, adds, stores, global addressing -- because a wave issues no MFMA while it waits: with one read-modify-write at a
+// time (64 per lane, each a full round trip to cold lines) the final passes of the deep stages, which nothing overlaps, ran
+// a third longer (DESIGN 4a "The serialised tail").
 template <int SD, int WPS, bool SCHUR, int SPLIT = 1, int WGW = 1>
 __global__ void __launch_bounds__(64 * WGW, WPS)
 nd_syrk_kernel(const SyrkJob *__restrict__ jobs, int njobs, int nitems, int margin, const unsigned *__restrict__ resmap,
@@ -293,28 +298,62 @@ nd_syrk_kernel(const SyrkJob *__restrict__ jobs, int njobs, int nitems, int marg
         // the front's last pass: its Schur complement goes straight into the parent (extend-add), every entry once --
         // the parent's entries of THIS child are touched by no other wave of the launch (the map is injective, the
         // launch holds children of one slot only), so plain read-modify-writes are safe and the order of the sums is
-        // fixed: child of slot 0, then child of slot 1
-        int prow[N];
+        // fixed: child of slot 0, then child of slot 1.  For the same reason no two of a wave's targets coincide, so the
+        // parent's entries are fetched in BATCHES (the 4 N entries of one m, or of two): all map lookups first, then per batch
+        // every load, one wait, the adds, every store -- a handful of memory round trips per item instead of one per entry,
+        // which the wave would sit through without issuing an MFMA.  The operand queue is dead here: its registers hold the
+        // batch.  Targets are addressed as global memory (one 64-bit address per column, panel or Schur buffer), and an
+        // entry without a target (padding: -1; above the diagonal of a diagonal item) is neither loaded nor stored.
+        typedef __attribute__((address_space(1))) double gdouble;
+        typedef __attribute__((address_space(1))) const int gint;
+        constexpr int BM = M < 2 ? M : 2;            // m's per batch
+        gint *pm = (gint *)j.pm;
+        const int hl = j.h - 1;
+        int prow[N], pcol[M][4];
 #pragma unroll
         for (int n = 0; n < N; ++n) {
-            const int r = ti * 64 + (n0 + n) * 16 + l15;
-            prow[n] = r < j.h ? j.pm[r] : -1;
+            const int r = ti * 64 + (n0 + n) * 16 + l15, t = pm[r < hl ? r : hl];
+            prow[n] = r < j.h ? t : -1;
         }
 #pragma unroll
         for (int m = 0; m < M; ++m)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-                const int cc = (m0 + m) * 16 + q + 4 * v, c = tj * 64 + cc;
-                const int pcol = c < j.h ? j.pm[c] : -1;
-                if (pcol < 0) continue;
-                double *__restrict__ colp = pcol < j.wpp ? j.Pp + (long long)pcol * j.ldpp : schur_col(j.Sp, j.ldsp, pcol - j.wpp) - j.wpp;
-#pragma unroll
-                for (int n = 0; n < N; ++n) {
-                    const int rr = (n0 + n) * 16 + l15;
-                    if (prow[n] < 0 || (diag && rr < cc)) continue;
-                    colp[prow[n]] += acc[m][n][v];
-                }
+                const int c = tj * 64 + (m0 + m) * 16 + q + 4 * v, t = pm[c < hl ? c : hl];
+                pcol[m][v] = c < j.h ? t : -1;
             }
+#pragma unroll
+        for (int mb = 0; mb < M; mb += BM) {
+            gdouble *colp[BM][4];
+            double t[BM][4][N];
+            auto live = [&](int m, int v, int n) {
+                return pcol[m][v] >= 0 && prow[n] >= 0 && !(diag && (n0 + n) * 16 + l15 < (m0 + m) * 16 + q + 4 * v);
+            };
+#pragma unroll
+            for (int e = 0; e < BM; ++e)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int pc = pcol[mb + e][v];
+                    colp[e][v] = (gdouble *)(pc < j.wpp ? j.Pp + (long long)pc * j.ldpp : schur_col(j.Sp, j.ldsp, pc - j.wpp) - j.wpp);
+                }
+#pragma unroll
+            for (int e = 0; e < BM; ++e)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+#pragma unroll
+                    for (int n = 0; n < N; ++n)
+                        if (live(mb + e, v, n)) t[e][v][n] = colp[e][v][prow[n]];
+            // the batch's one wait, stated: left to the compiler every guarded add gets a vmcnt(0) of its own (a lane that skips
+            // one must not skip the wait of the next), which also waits for the store issued just before it
+            __builtin_amdgcn_s_waitcnt(0x0f70);      // gfx9 encoding of vmcnt(0) alone
+#pragma unroll
+            for (int e = 0; e < BM; ++e)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+#pragma unroll
+                    for (int n = 0; n < N; ++n)
+                        if (live(mb + e, v, n)) colp[e][v][prow[n]] = t[e][v][n] + acc[mb + e][n][v];
+        }
         return;
     }
 #pragma unroll
