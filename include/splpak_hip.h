@@ -676,6 +676,73 @@ int32_t splpak_debug_fit_grid_weighted_stage_f64(int32_t stage, int32_t ndim, co
  * the call (1 with ldw == 0, nfields otherwise). */
 int32_t splpak_debug_fit_grid_weighted_stats(int64_t out8[8]);
 
+/* Many small independent fits on one node grid in one launch: a spline per spectrum, per detector row, per station time series,
+ * per tile of an image, per bootstrap resample of the points.  Every problem has its own points, its own number of them, its
+ * own values and weights; only ndim, nodes, xmin, xmax and xtrap are shared.  (splpak_refit_* is the route for many VALUE sets
+ * on the SAME points.)
+ *   offsets  nbatch + 1 of them: problem k owns the points offsets[k] .. offsets[k+1]-1 of xdata(l1xdat, *), ydata and wdata;
+ *   coef     problem k's ncol coefficients go to coef + k*ldcoef, ldcoef >= ncol: the layout of splpak_refit_* and
+ *            splpak_eval_fields_*.
+ * Per problem: what splcw does for its points, or splcc when wdata == NULL.  A negative FIRST weight of a problem means "no
+ * weights" for that problem (:581-588); a point of weight 0 contributes no row and no histogram bump (:891); the nearest-node
+ * histogram, the 0.75 rule, dcwght and the derivative-constraint rows are the reference's (:862-1046), the first-derivative
+ * rows at boundary nodes and the doubled mixed row in 2-D included; every problem has its own totlwt and its own sparse set.
+ * There is no hist_out.
+ * Algorithm.  One workgroup works on one problem from its points to its coefficients, all in its own LDS: the banded normal
+ * equations A^T W^2 A + C^T C and A^T W^2 y (2-D: the smaller dimension fastest, whatever the caller's order), a Cholesky on the
+ * band with the pivot test of splpak_fit_f64 (a pivot that is not positive fails), the solve, and the
+ * refinement of splpak_fit_grid_* against the data and constraint rows: it stops at an estimated 1e-11, goes on for up to 30
+ * steps while the corrections contract, and says 107 when that misses 1e-10.  The rows come from the window tables of the
+ * single fit.  The batch is ONE launch whatever nbatch is; its workgroups stride over the problems when there are more
+ * problems than workgroups.  A problem of very many points is still worked by its one workgroup, which walks all of them for
+ * every band row: the entry is for many SMALL problems; splitting a large one is out of scope (use splpak_fit_*).
+ * Shapes.  ndim 1 or 2, and a grid whose band, vectors and staging area fit in 64 KiB of LDS: splpak_fit_many_lds_bytes returns
+ * the bytes, 8 ((hb + 5) ncol + 128 (4 ndim + 2) + 16) + 512 (ndim + 1) + ncol rounded up to 4, with hb = 3 in 1-D and
+ * 3 min(nodes) + 3 in 2-D: 1-D grids up to 896 nodes; 2-D up to 12 x 12 (62 736 bytes; 12 x 11: 55 332; 13 x 12: 66 972, refused).
+ * It needs no device and returns SPLPAK_E_BADARG for null nodes, ndim other than 1 or 2, or fewer than 4
+ * nodes.
+ * Determinism.  Every sum has one owner and a fixed order -- the owner of a band row walks the problem's points in index order
+ * -- and there are no floating-point atomics.  The bits of problem k depend on its own points, values, weights and the grid
+ * alone: not on nbatch, its position in the batch, its neighbours, the host / _dev entry, or the workgroup that ran it.
+ * Status.  Decided on the host before any device work, the first failing check wins, coef and status untouched:
+ *   SPLPAK_E_BADARG (offsets, nodes, xmin or xmax null); 101; SPLPAK_E_UNSUPPORTED (ndim > 2); 102; 103; 104 (ldcoef < ncol);
+ *   SPLPAK_E_BADARG (nbatch < 1, offsets that decrease, a problem of 2^31 points or more, l1xdat < ndim, xdata, ydata or coef
+ *   null); SPLPAK_E_UNSUPPORTED (the LDS rule, with a message that says to loop the single fit: never a silent fallback).
+ * Then per problem, status[k] (may be NULL) = 105 for a problem without points (its coefficients untouched; it is never sent
+ * to the device), 107 where a pivot fails the test or the refinement rule fails (ITS coefficients set to 0; no other problem
+ * is touched), otherwise 0.  Returns 0 when every problem ended in 0, otherwise the status of the lowest-numbered problem that
+ * did not; SPLPAK_E_NODEVICE / SPLPAK_E_NOMEM from the device part.
+ * info (10 per problem, may be NULL) as for splpak_fit_f64: [0] data rows, [1] constraint rows, [2] refinement steps, [3] last
+ * correction, [4] smallest pivot, [5] [6] 0, [7] the launch's device seconds divided by the problems that ran, [8] reserr over
+ * the data and constraint rows -- of the coefficients BEFORE the last correction, whose residuals the last refinement step
+ * computed anyway (the correction is below 1e-8 of the coefficients and reserr is stationary at the minimiser) --, [9] 0: the
+ * backward error needs |N| |x|, which the workgroup no longer holds once the band is factored.  All 0 for a problem of status
+ * 105. */
+int32_t splpak_fit_many_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xdata, int32_t l1xdat,
+                            const double *ydata, const double *wdata /* may be NULL */, const double *xmin, const double *xmax,
+                            const int32_t *nodes, double xtrap, double *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
+                            double *info /* 10 per problem, may be NULL */);
+/* REAL32 storage, arithmetic in double, one rounding at the store of coef */
+int32_t splpak_fit_many_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xdata, int32_t l1xdat,
+                            const float *ydata, const float *wdata /* may be NULL */, const float *xmin, const float *xmax,
+                            const int32_t *nodes, float xtrap, float *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
+                            double *info /* 10 per problem, may be NULL */);
+/* the same on resident data: xdata, ydata, wdata and coef are device arrays; offsets, xmin, xmax, nodes, status and info are
+ * host arrays.  Not asynchronous: `stream` is synchronised once, after the launch, for the statuses. */
+int32_t splpak_fit_many_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xdata_dev, int32_t l1xdat,
+                                const double *ydata_dev, const double *wdata_dev /* may be NULL */, const double *xmin, const double *xmax,
+                                const int32_t *nodes, double xtrap, double *coef_dev, int64_t ldcoef, int32_t *status /* host */,
+                                double *info /* host */, void *stream);
+int32_t splpak_fit_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xdata_dev, int32_t l1xdat,
+                                const float *ydata_dev, const float *wdata_dev /* may be NULL */, const float *xmin, const float *xmax,
+                                const int32_t *nodes, float xtrap, float *coef_dev, int64_t ldcoef, int32_t *status /* host */,
+                                double *info /* host */, void *stream);
+int64_t splpak_fit_many_lds_bytes(int32_t ndim, const int32_t *nodes);
+/* host counters of the calling thread's last splpak_fit_many_* call (nothing is waited for): [0] workgroups launched, [1] LDS
+ * bytes per workgroup, [2] launches of the call, [3] problems sent to the device, [4] problems refused with 105, [5] the
+ * largest number of refinement steps over the problems, [6] [7] 0. */
+int32_t splpak_debug_fit_many_stats(int64_t out8[8]);
+
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
  * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one
  * splpak_eval_* call per field -- each reading the coordinates, building the factor tables and, for a large batch on a

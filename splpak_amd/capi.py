@@ -42,6 +42,8 @@ SYMBOLS = [
     "splpak_debug_fit_grid_stage_f64", "splpak_debug_fit_grid_stats",
     "splpak_fit_grid_weighted_f64", "splpak_fit_grid_weighted_f32", "splpak_fit_grid_weighted_dev_f64",
     "splpak_fit_grid_weighted_dev_f32", "splpak_debug_fit_grid_weighted_stage_f64", "splpak_debug_fit_grid_weighted_stats",
+    "splpak_fit_many_f64", "splpak_fit_many_f32", "splpak_fit_many_dev_f64", "splpak_fit_many_dev_f32", "splpak_fit_many_lds_bytes",
+    "splpak_debug_fit_many_stats",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
     "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
@@ -206,6 +208,18 @@ def lib() -> C.CDLL:
     L.splpak_debug_fit_grid_weighted_stage_f64.argtypes = [i32, i32, _lp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]
     L.splpak_debug_fit_grid_weighted_stats.restype = i32
     L.splpak_debug_fit_grid_weighted_stats.argtypes = [_lp]
+    L.splpak_fit_many_f64.restype = i32
+    L.splpak_fit_many_f64.argtypes = [i32, i32, _lp, _dp, i32, _dp, _dp, _dp, _dp, _ip, dbl, _dp, i64, _ip, _dp]
+    L.splpak_fit_many_f32.restype = i32
+    L.splpak_fit_many_f32.argtypes = [i32, i32, _lp, _fp, i32, _fp, _fp, _fp, _fp, _ip, C.c_float, _fp, i64, _ip, _dp]
+    L.splpak_fit_many_dev_f64.restype = i32
+    L.splpak_fit_many_dev_f64.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _dp, _dp, _ip, dbl, vp, i64, _ip, _dp, vp]
+    L.splpak_fit_many_dev_f32.restype = i32
+    L.splpak_fit_many_dev_f32.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _fp, _fp, _ip, C.c_float, vp, i64, _ip, _dp, vp]
+    L.splpak_fit_many_lds_bytes.restype = i64
+    L.splpak_fit_many_lds_bytes.argtypes = [i32, _ip]
+    L.splpak_debug_fit_many_stats.restype = i32
+    L.splpak_debug_fit_many_stats.argtypes = [_lp]
     L.splpak_eval_fields_f64.restype = i32
     L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
     L.splpak_eval_fields_f32.restype = i32
@@ -732,6 +746,71 @@ def debug_fit_grid_weighted_stats():
     solves, weight analyses of the call)."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_fit_grid_weighted_stats(_p(v, _lp)))
+    return tuple(int(t) for t in v)
+
+
+def fit_many(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, real32=False, ldcoef=None, coef=None, l1xdat=None):
+    """Many small independent fits on one node grid in one launch (splpak_fit_many_*): problem k owns the points
+    offsets[k] .. offsets[k+1]-1 of xdata (npoints, l1xdat), ydata and wdata (None: splcc); its coefficients go to row k of
+    `coef` (nbatch, ldcoef), the layout evaluate_fields reads.  -> (coef, ierror, status (nbatch), info (nbatch, 10)); a
+    problem without points has status 105 and its row of `coef` is left as it was."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nbatch = offsets.size - 1
+    xdata = np.ascontiguousarray(xdata, dtype=dt)
+    if xdata.ndim == 1:
+        xdata = xdata.reshape(-1, 1)
+    ydata = np.ascontiguousarray(ydata, dtype=dt)
+    if wdata is not None:
+        wdata = np.ascontiguousarray(wdata, dtype=dt)
+    if l1xdat is None:
+        l1xdat = xdata.shape[1]
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
+    ldc = ncol if ldcoef is None else int(ldcoef)
+    if coef is None:
+        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    fn = lib().splpak_fit_many_f32 if real32 else lib().splpak_fit_many_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(status, _ip), _p(info, _dp)))
+    return coef, rc, status, info
+
+
+def fit_many_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap=0.0, l1xdat=None, ldcoef=None, stream=0):
+    """fit_many on torch device tensors: xdata, ydata, wdata (or None) and coef on the device, offsets on the host.
+    -> (ierror, status (nbatch), info (nbatch, 10))."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nbatch = offsets.size - 1
+    real32 = str(xdata.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    if l1xdat is None:
+        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    fn = lib().splpak_fit_many_dev_f32 if real32 else lib().splpak_fit_many_dev_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
+                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap),
+                   coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(status, _ip), _p(info, _dp), C.c_void_p(stream)))
+    return rc, status, info
+
+
+def fit_many_lds_bytes(ndim, nodes) -> int:
+    """LDS bytes a problem of this grid takes in fit_many (host only; splpak_fit_many_lds_bytes); raises for a shape the
+    entry's ladder rejects."""
+    nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+    return int(_check(lib().splpak_fit_many_lds_bytes(int(ndim), _p(nodes, _ip))))
+
+
+def debug_fit_many_stats():
+    """Host counters of this thread's last fit_many call: (workgroups launched, LDS bytes per workgroup, launches, problems sent
+    to the device, problems refused with 105, the largest number of refinement steps, 0, 0)."""
+    v = np.zeros(8, dtype=np.int64)
+    _check(lib().splpak_debug_fit_many_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)
 
 

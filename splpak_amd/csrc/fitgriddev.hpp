@@ -82,7 +82,7 @@ struct RefineRule {
     double last_rel = 0.0, prev_rel = std::numeric_limits<double>::infinity(), ratio = 0.0;
     bool converged = false;
     // after step `it` (from 0): am = |correction|_inf, |coef|_inf.  True: the loop ends.
-    bool advance(int it, const double *am)
+    __host__ __device__ bool advance(int it, const double *am)
     {
         ++steps;
         last_rel = am[1] > 0.0 ? am[0] / am[1] : 0.0;
@@ -98,7 +98,7 @@ struct RefineRule {
         return false;
     }
     // the estimate that decides 107 where the loop ended without converging
-    double estimate() const { return steps >= 2 && ratio > 0.0 && ratio < 1.0 ? last_rel * ratio / (1.0 - ratio) : last_rel; }
+    __host__ __device__ double estimate() const { return steps >= 2 && ratio > 0.0 && ratio < 1.0 ? last_rel * ratio / (1.0 - ratio) : last_rel; }
 };
 
 }  // namespace splpak

@@ -1,0 +1,75 @@
+// Many small independent fits on one node grid (include/splpak_hip.h: splpak_fit_many_*): what the entries (fitmanyapi.hip)
+// and the kernel with its driver (fitmany.hip) share.
+#pragma once
+#include "common.hpp"
+
+namespace splpak {
+
+constexpr int FITMANY_THREADS = 256;            // threads of a workgroup: one workgroup per problem
+constexpr int FITMANY_SMALL_NCOL = 64;          // grids of up to this many nodes run in workgroups of one wave (64 threads)
+constexpr int FITMANY_CHUNK = 128;              // points staged in LDS at a time
+constexpr int FITMANY_WALK = 8;                 // staged points whose words an owner reads together (divides FITMANY_CHUNK)
+constexpr long long FITMANY_LDS_BUDGET = 65536; // bytes of LDS a workgroup may ask for (no launch of the library asks for more)
+constexpr int FITMANY_MAX_STEPS = 30;           // refinement steps at the most (RefineRule decides earlier)
+
+// The LDS of one workgroup, for a grid in the internal order (smaller dimension fastest), offsets in doubles from the start:
+//   band    [ncol][hb + 1]   row i holds N(i, i - o) at o = 0 .. hb, later the Cholesky factor
+//   rhs     [ncol]           A^T W^2 y
+//   x       [ncol]           the coefficients
+//   rho     [ncol]           the residual's gradient, then the correction
+//   dcw     [ncol]           the nearest-node histogram (caller's node order), then the constraint weights (internal order)
+//   stage   [CHUNK][4 D + 2] per staged point: D window tables, w, w y (or the row's residual); the reductions reuse it
+//   scal    [16]
+// then, in 4-byte words, ws [CHUNK][D] (window starts), addr [CHUNK] (histogram address) and ncol bytes of sparse flags.
+struct FitManyShape {
+    int ndim, ncol, hb, ld;                     // ld = hb + 1
+    long long band, rhs, x, rho, dcw, stage, scal, doubles;
+    long long bytes;
+};
+
+inline FitManyShape fit_many_shape(int ndim, const int *nodes)
+{
+    FitManyShape s{};
+    s.ndim = ndim;
+    int n0 = nodes[0], n1 = 1;
+    if (ndim == 2) { n0 = nodes[0] < nodes[1] ? nodes[0] : nodes[1]; n1 = nodes[0] < nodes[1] ? nodes[1] : nodes[0]; }
+    const long long ncol = (long long)n0 * n1;
+    s.hb = ndim == 2 ? 3 * n0 + 3 : 3;
+    s.ld = s.hb + 1;
+    s.ncol = (int)(ncol < (1LL << 30) ? ncol : (1LL << 30));
+    s.band = 0;
+    s.rhs = ncol * s.ld;
+    s.x = s.rhs + ncol;
+    s.rho = s.x + ncol;
+    s.dcw = s.rho + ncol;
+    s.stage = s.dcw + ncol;
+    s.scal = s.stage + (long long)FITMANY_CHUNK * (4 * ndim + 2);
+    s.doubles = s.scal + 16;
+    s.bytes = 8 * s.doubles + 4LL * FITMANY_CHUNK * (ndim + 1) + ((ncol + 3) / 4) * 4;
+    return s;
+}
+
+// What the kernel leaves per problem that ran (doubles).
+enum { FM_ROWS = 0, FM_CROWS, FM_STEPS, FM_LASTREL, FM_MINPIV, FM_RESERR, FM_STATUS, FM_SPARE, FM_RESULT };
+
+struct FitManyArgs {
+    Grid g;                        // internal order (build_grid with reorder)
+    FitManyShape sh;
+    int nrun;                      // problems sent to the device
+    const int *plist;              // [nrun] their numbers in the batch
+    const long long *offsets;      // [nbatch + 1]
+    long long base;                // point number of xdata[0] (the host entries upload the span of the batch alone)
+    int l1xdat;
+    double xtrap;
+    long long ldcoef;
+    int compact;                   // coef of run r at r * ldcoef (host entries) instead of plist[r] * ldcoef
+    double *result;                // [nrun][FM_RESULT]
+};
+
+extern thread_local long long t_fit_many_stats[8];
+
+// The device part on device arrays: one launch.  0 or SPLPAK_E_*; *seconds = the launch's device time.
+template <typename T>
+int fit_many_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, hipStream_t st, double *seconds);
+
+}  // namespace splpak

@@ -1,0 +1,226 @@
+// The entries of the batch of small fits (include/splpak_hip.h): splpak_fit_many_* on host and device pointers, the LDS
+// rule and the counters.  The ladder of checks in the order the header gives, all on the host; then fitmany.hip.
+#include "plan.hpp"
+#include "fitmany.hpp"
+
+#include <new>
+#include <vector>
+
+using namespace splpak;
+
+namespace {
+
+// device memory of one call, released with it
+struct CallScratch {
+    std::vector<void *> held;
+    ~CallScratch() { for (void *p : held) (void)hipFree(p); }
+    template <typename U> bool get(U **out, size_t count)
+    {
+        void *q = nullptr;
+        if (hipMalloc(&q, (count ? count : 1) * sizeof(U)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("the device scratch of the batch of fits could not be allocated");
+            return false;
+        }
+        held.push_back(q);
+        *out = static_cast<U *>(q);
+        return true;
+    }
+};
+
+const char *LDS_MESSAGE =
+    "the grid needs more than 64 KiB of LDS per problem (splpak_fit_many_lds_bytes): loop splpak_fit_* over the problems instead";
+
+template <typename T>
+int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *offsets, const T *xdata, int32_t l1xdat, const T *ydata,
+                       const T *wdata, const T *xmin_t, const T *xmax_t, const int32_t *nodes, double xtrap, T *coef, int64_t ldcoef,
+                       int32_t *status, double *info, hipStream_t st)
+{
+    for (int j = 0; j < 8; ++j) t_fit_many_stats[j] = 0;
+    if (!offsets || !nodes || !xmin_t || !xmax_t) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (ndim < 1) return 101;
+    if (ndim > 2) {
+        set_error("splpak_fit_many_* fits 1-D and 2-D grids: loop splpak_fit_* over the problems instead");
+        return SPLPAK_E_UNSUPPORTED;
+    }
+    double xmin[MAXD] = {0, 0, 0, 0}, xmax[MAXD] = {0, 0, 0, 0};
+    for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_t[d]; xmax[d] = (double)xmax_t[d]; }
+    FitManyArgs a{};
+    if (int rc = build_grid(ndim, nodes, xmin, xmax, a.g, nullptr, true)) {      // 102, 103
+        if (rc == SPLPAK_E_UNSUPPORTED) set_error("more than 2^30 nodes is not supported");
+        return rc;
+    }
+    if (ldcoef < a.g.ncol) return 104;
+    bool ok = nbatch >= 1 && l1xdat >= ndim && xdata && ydata && coef;
+    for (int k = 0; ok && k < nbatch; ++k) ok = offsets[k + 1] >= offsets[k] && offsets[k + 1] - offsets[k] < (1LL << 31);
+    if (!ok) {
+        set_error("nbatch < 1, offsets that decrease, a problem of 2^31 points or more, l1xdat < ndim or a null pointer");
+        return SPLPAK_E_BADARG;
+    }
+    a.sh = fit_many_shape(ndim, nodes);
+    if (a.sh.bytes > FITMANY_LDS_BUDGET) { set_error(LDS_MESSAGE); return SPLPAK_E_UNSUPPORTED; }
+
+    try {
+        const int ncol = a.g.ncol;
+        std::vector<int> plist;
+        int first = 0;      // the status of the lowest-numbered problem that did not end in 0
+        for (int k = 0; k < nbatch; ++k) {
+            const bool empty = offsets[k + 1] == offsets[k];
+            if (!empty) plist.push_back(k);
+            else if (first == 0) first = 105;
+            if (status) status[k] = empty ? 105 : 0;
+            if (info) for (int j = 0; j < 10; ++j) info[(size_t)k * 10 + j] = 0.0;
+        }
+        const int nrun = (int)plist.size();
+        t_fit_many_stats[1] = a.sh.bytes;
+        t_fit_many_stats[3] = nrun;
+        t_fit_many_stats[4] = nbatch - nrun;
+        if (nrun == 0) return first;
+
+        if (int r = device_ready()) return r;
+        // (declared before the scratch: an error return frees the scratch first, which waits for the copies queued into these)
+        std::vector<double> res((size_t)nrun * FM_RESULT);
+        std::vector<T> ch;
+        CallScratch cs;
+        int *plist_dev = nullptr;
+        long long *off_dev = nullptr;
+        double *res_dev = nullptr;
+        if (!cs.get(&plist_dev, (size_t)nrun) || !cs.get(&off_dev, (size_t)nbatch + 1) || !cs.get(&res_dev, (size_t)nrun * FM_RESULT))
+            return SPLPAK_E_NOMEM;
+        static_assert(sizeof(long long) == sizeof(int64_t), "offsets are uploaded as they are");
+        SPLPAK_HIP_TRY(hipMemcpyAsync(plist_dev, plist.data(), sizeof(int) * (size_t)nrun, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+        SPLPAK_HIP_TRY(hipMemcpyAsync(off_dev, offsets, sizeof(int64_t) * ((size_t)nbatch + 1), hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+        a.nrun = nrun;
+        a.plist = plist_dev;
+        a.offsets = off_dev;
+        a.l1xdat = l1xdat;
+        a.xtrap = xtrap;
+        a.result = res_dev;
+        const T *xd = xdata, *yd = ydata, *wd = wdata;
+        T *cd = coef;
+        if (dev) {
+            a.base = 0;
+            a.ldcoef = ldcoef;
+            a.compact = 0;
+        } else {
+            // the span of the batch's points alone, the coefficients of the problems that run back to back
+            const long long lo = offsets[0], npt = offsets[nbatch] - offsets[0];
+            T *xs = nullptr, *ys = nullptr, *wsd = nullptr;
+            if (!cs.get(&xs, (size_t)npt * (size_t)l1xdat) || !cs.get(&ys, (size_t)npt) || (wdata && !cs.get(&wsd, (size_t)npt)) ||
+                !cs.get(&cd, (size_t)nrun * (size_t)ncol))
+                return SPLPAK_E_NOMEM;
+            SPLPAK_HIP_TRY(hipMemcpyAsync(xs, xdata + lo * l1xdat, sizeof(T) * (size_t)npt * (size_t)l1xdat, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+            SPLPAK_HIP_TRY(hipMemcpyAsync(ys, ydata + lo, sizeof(T) * (size_t)npt, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+            if (wdata) SPLPAK_HIP_TRY(hipMemcpyAsync(wsd, wdata + lo, sizeof(T) * (size_t)npt, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+            xd = xs; yd = ys; wd = wsd;
+            a.base = lo;
+            a.ldcoef = ncol;
+            a.compact = 1;
+        }
+        double seconds = 0.0;
+        if (int r = fit_many_launch<T>(a, xd, yd, wd, cd, st, &seconds)) return r;
+
+        SPLPAK_HIP_TRY(hipMemcpyAsync(res.data(), res_dev, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+        if (!dev) {
+            ch.resize((size_t)nrun * (size_t)ncol);
+            SPLPAK_HIP_TRY(hipMemcpyAsync(ch.data(), cd, sizeof(T) * ch.size(), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
+        }
+        SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+        long long maxsteps = 0;
+        int first_failed = -1;
+        for (int r = 0; r < nrun; ++r) {
+            const int k = plist[(size_t)r];
+            const double *v = res.data() + (size_t)r * FM_RESULT;
+            const int sk = v[FM_STATUS] != 0.0 ? 107 : 0;
+            if (status) status[k] = sk;
+            if (sk != 0 && first_failed < 0) first_failed = k;
+            if ((long long)v[FM_STEPS] > maxsteps) maxsteps = (long long)v[FM_STEPS];
+            if (info) {
+                double *ik = info + (size_t)k * 10;
+                ik[0] = v[FM_ROWS];
+                ik[1] = v[FM_CROWS];
+                ik[2] = v[FM_STEPS];
+                ik[3] = v[FM_LASTREL];
+                ik[4] = v[FM_MINPIV];
+                ik[7] = seconds / (double)nrun;
+                ik[8] = v[FM_RESERR];
+            }
+            if (!dev) {
+                T *ck = coef + (long long)k * ldcoef;
+                for (int i = 0; i < ncol; ++i) ck[i] = ch[(size_t)r * (size_t)ncol + (size_t)i];
+            }
+        }
+        t_fit_many_stats[5] = maxsteps;
+        int rc = 0;
+        for (int k = 0; k < nbatch && rc == 0; ++k) {
+            if (offsets[k + 1] == offsets[k]) rc = 105;
+            else if (k == first_failed) rc = 107;
+        }
+        if (first_failed >= 0) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "problem %d of the batch: a pivot failed the rank test or the refinement missed 1e-10 (too few points?)", first_failed);
+            set_error(buf);
+        }
+        return rc;
+    } catch (const std::bad_alloc &) {
+        set_error("the host tables of the batch of fits could not be allocated");
+        return SPLPAK_E_NOMEM;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t splpak_fit_many_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata, int32_t l1xdat, const double *ydata,
+                            const double *wdata, const double *xmin, const double *xmax, const int32_t *nodes, double xtrap, double *coef,
+                            int64_t ldcoef, int32_t *status, double *info)
+{
+    return fit_many_entry<double>(false, ndim, nbatch, offsets, xdata, l1xdat, ydata, wdata, xmin, xmax, nodes, xtrap, coef, ldcoef, status, info,
+                                  nullptr);
+}
+
+int32_t splpak_fit_many_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xdata, int32_t l1xdat, const float *ydata,
+                            const float *wdata, const float *xmin, const float *xmax, const int32_t *nodes, float xtrap, float *coef,
+                            int64_t ldcoef, int32_t *status, double *info)
+{
+    return fit_many_entry<float>(false, ndim, nbatch, offsets, xdata, l1xdat, ydata, wdata, xmin, xmax, nodes, (double)xtrap, coef, ldcoef, status,
+                                 info, nullptr);
+}
+
+int32_t splpak_fit_many_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata_dev, int32_t l1xdat,
+                                const double *ydata_dev, const double *wdata_dev, const double *xmin, const double *xmax, const int32_t *nodes,
+                                double xtrap, double *coef_dev, int64_t ldcoef, int32_t *status, double *info, void *stream)
+{
+    return fit_many_entry<double>(true, ndim, nbatch, offsets, xdata_dev, l1xdat, ydata_dev, wdata_dev, xmin, xmax, nodes, xtrap, coef_dev, ldcoef,
+                                  status, info, (hipStream_t)stream);
+}
+
+int32_t splpak_fit_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xdata_dev, int32_t l1xdat,
+                                const float *ydata_dev, const float *wdata_dev, const float *xmin, const float *xmax, const int32_t *nodes,
+                                float xtrap, float *coef_dev, int64_t ldcoef, int32_t *status, double *info, void *stream)
+{
+    return fit_many_entry<float>(true, ndim, nbatch, offsets, xdata_dev, l1xdat, ydata_dev, wdata_dev, xmin, xmax, nodes, (double)xtrap, coef_dev,
+                                 ldcoef, status, info, (hipStream_t)stream);
+}
+
+// the LDS bytes a problem of this grid takes (host only); SPLPAK_E_BADARG for a shape the ladder rejects
+int64_t splpak_fit_many_lds_bytes(int32_t ndim, const int32_t *nodes)
+{
+    if (!nodes || ndim < 1 || ndim > 2) { set_error("nodes is null or ndim is not 1 or 2"); return SPLPAK_E_BADARG; }
+    for (int d = 0; d < ndim; ++d)
+        if (nodes[d] < 4) { set_error("fewer than 4 nodes in a dimension"); return SPLPAK_E_BADARG; }
+    for (int d = 0; d < ndim; ++d)
+        if (nodes[d] > (1 << 20)) return INT64_MAX / 2;      // (far beyond any budget; keeps the products below within int64)
+    return fit_many_shape(ndim, nodes).bytes;
+}
+
+// host counters of the calling thread's last splpak_fit_many_* call (no device is asked, nothing is waited for)
+int32_t splpak_debug_fit_many_stats(int64_t out8[8])
+{
+    if (!out8) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    for (int j = 0; j < 8; ++j) out8[j] = t_fit_many_stats[j];
+    return 0;
+}
+
+}  // extern "C"

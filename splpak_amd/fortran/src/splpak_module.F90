@@ -73,6 +73,7 @@ module splpak_module
         generic,public   :: initialize    => splcc, splcw        !! fit
         procedure,public :: initialize_grid => splpak_fit_grid      !! fit of samples on a tensor-product grid of points (additive)
         procedure,public :: initialize_grid_weighted => splpak_fit_grid_weighted   !! the same with a weight per sample (additive)
+        procedure,public :: initialize_many => splpak_fit_many      !! many small independent fits on one node grid in one launch (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
@@ -200,6 +201,19 @@ module splpak_module
             type(c_ptr),value :: npts, axes, values, weights, xmin, xmax, nodes, coef, info
             real(wp),value :: xtrap
         end function c_fit_grid_weighted
+#ifdef REAL32
+        integer(c_int32_t) function c_fit_many(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,coef,ldcoef, &
+                                               status,info) bind(C,name='splpak_fit_many_f32')
+#else
+        integer(c_int32_t) function c_fit_many(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,coef,ldcoef, &
+                                               status,info) bind(C,name='splpak_fit_many_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr, wp
+            integer(c_int32_t),value :: ndim, nbatch, l1xdat
+            integer(c_int64_t),value :: ldcoef
+            type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, status, info
+            real(wp),value :: xtrap
+        end function c_fit_many
 #ifdef REAL32
         integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
                                                   bind(C,name='splpak_eval_fields_f32')
@@ -700,6 +714,53 @@ module splpak_module
             call report_library_failure(ierror,'initialize_grid_weighted')
         end if
     end subroutine splpak_fit_grid_weighted
+
+    !> Many small independent fits on one node grid in one launch (include/splpak_hip.h, splpak_fit_many_f64): problem k owns
+    !! the points offsets(k)+1 .. offsets(k+1) of xdata(l1xdat,*), ydata and wdata (`offsets(nbatch+1)`, zero based, not
+    !! decreasing); its coefficients go to coef(:,k), `ldcoef` apart.  Every problem gets what `initialize` does for its own
+    !! points (without `wdata`: splcc); only ndim, nodes, xmin, xmax and xtrap are shared.  ierrors(k): 0, 105 for a problem
+    !! without points (its coefficients untouched), 107 with its coefficients zeroed; ierror: 0, or the status of the first
+    !! problem that did not end in 0, the argument errors of `initialize`, -3 for a bad offset or leading dimension and -4 for
+    !! ndim > 2 or a grid beyond the 64 KiB of LDS a problem may take (the library's message says which) -- never a silent
+    !! fallback: loop `initialize` there.  Refused with -4 and a message of its own under set_host, set_gpus(n > 1) and in the
+    !! -DREAL128 build, as `refit` is.  The object is left as it was.
+    subroutine splpak_fit_many(me,ndim,nbatch,offsets,xdata,l1xdat,ydata,xmin,xmax,nodes,xtrap,coef,ldcoef,ierrors,ierror,wdata)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, l1xdat, ldcoef
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: xdata(l1xdat,*), ydata(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(in) :: xtrap
+        real(wp),intent(inout),target :: coef(ldcoef,*)
+        integer,intent(out),target :: ierrors(*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: wdata(*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pw
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' initialize_many - not available in the -DREAL128 build: call initialize for every problem')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' initialize_many - not available under set_host or set_gpus(n > 1): '// &
+                               'call initialize for every problem')
+            return
+        end if
+        pw = c_null_ptr
+        if (present(wdata)) pw = c_loc(wdata)
+        rc = c_fit_many(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
+                        c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, c_loc(coef), int(ldcoef,c_int64_t), &
+                        c_loc(ierrors), c_null_ptr)
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'initialize_many')
+        end if
+#endif
+    end subroutine splpak_fit_many
 
     !> New values on the points of this object's last `initialize`: several fields sampled at the same points (the
     !! components of a velocity, a time series on a fixed sensor layout, bootstrap replicas) cost one `initialize` and one
