@@ -743,6 +743,103 @@ int64_t splpak_fit_many_lds_bytes(int32_t ndim, const int32_t *nodes);
  * largest number of refinement steps over the problems, [6] [7] 0. */
 int32_t splpak_debug_fit_many_stats(int64_t out8[8]);
 
+/* The evaluation side of splpak_fit_many_*: problem k's coefficients at problem k's own points, one launch whatever nbatch is
+ * (a spline per spectrum resampled on its own abscissa).  splpak_eval_fields_* evaluates every set at ONE shared batch of points
+ * and splpak_eval_* takes one set per call; a host loop of nbatch such calls is latency bound.  The layouts are those of
+ * splpak_fit_many_*:
+ *   offsets  nbatch + 1 of them: problem k owns the global indices offsets[k] .. offsets[k+1]-1 of xq(ldxq, *) and out;
+ *            offsets[0] need not be 0;
+ *   coef     problem k's ncol coefficients are at coef + k*ldcoef, ldcoef >= ncol, problems without queries included: exactly
+ *            where splpak_fit_many_* (or splpak_refit_*) put them;
+ *   nderiv   one pattern for all problems (NULL: values).
+ * ndim is 1 to 4 and any grid is accepted (there is no LDS rule).  out[i] is the very value splpak_eval_* returns for query i
+ * with the coefficients of the problem that owns i and the same nderiv (identical bits: the same factor table and the same sum
+ * over the window; nothing is shared between problems).  Words of `out` outside [offsets[0], offsets[nbatch]), rows of xq
+ * beyond ndim and words of `coef` between the sets are neither read nor written.
+ * Algorithm.  One thread per query over the concatenated list, so 10^5 problems of 8 queries and 4 problems of 10^6 are balanced
+ * alike.  A wave looks its first query's problem up in the uploaded offsets; where its last query has the same problem (the
+ * common case) all its lanes take that coefficient set, otherwise each lane searches between the two.  Problems without
+ * queries, and runs of them, are stepped over.  How the problem was found does not enter the arithmetic.
+ * Status, decided on the host before any device work, the first failing check wins:
+ *   SPLPAK_E_BADARG       offsets, nodes, xmin or xmax null; then nbatch < 1 or offsets that decrease;
+ *   101, then SPLPAK_E_UNSUPPORTED (ndim > 4), then 102 / 103 as splpak_eval_f64 -- on 101 / 102 / 103 the results
+ *                         out[offsets[0] .. offsets[nbatch]) are set to 0 (if `out` is not null), on the others nothing is written;
+ *   SPLPAK_E_BADARG       ldxq < ndim or ldcoef < ncol;
+ *   no queries at all     0, or 104 for an nderiv outside 0..2; nothing is written and the data pointers are not looked at;
+ *   SPLPAK_E_BADARG       xq, coef or out null.
+ * 104 is reported but the values are computed with nderiv clamped to 0..2 (:1190-1194).
+ * The host forms stage through the device: the span of the batch's queries alone and (nbatch-1)*ldcoef + ncol coefficients. */
+int32_t splpak_eval_many_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xq, int32_t ldxq,
+                             const int32_t *nderiv /* may be NULL */, const double *coef, int64_t ldcoef, const double *xmin,
+                             const double *xmax, const int32_t *nodes, double *out);
+/* REAL32 storage, arithmetic in double, as splpak_eval_f32 */
+int32_t splpak_eval_many_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xq, int32_t ldxq,
+                             const int32_t *nderiv /* may be NULL */, const float *coef, int64_t ldcoef, const float *xmin,
+                             const float *xmax, const int32_t *nodes, float *out);
+/* the same on resident data: xq, coef and out are device arrays; offsets, nderiv, xmin, xmax and nodes are host arrays.
+ * Asynchronous on `stream`: the call only enqueues -- no read-back, no synchronisation of the stream, and once the calling
+ * thread's scratch holds nbatch + 1 offsets no hipMalloc / hipFree.  The one thing it uploads is `offsets`, into that scratch
+ * (released by splpak_shutdown); `offsets` has been read when the call returns. */
+int32_t splpak_eval_many_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xq_dev, int32_t ldxq,
+                                 const int32_t *nderiv /* host, may be NULL */, const double *coef_dev, int64_t ldcoef,
+                                 const double *xmin, const double *xmax, const int32_t *nodes, double *out_dev, void *stream);
+int32_t splpak_eval_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xq_dev, int32_t ldxq,
+                                 const int32_t *nderiv /* host, may be NULL */, const float *coef_dev, int64_t ldcoef,
+                                 const float *xmin, const float *xmax, const int32_t *nodes, float *out_dev, void *stream);
+
+/* The residual pass of a clipping loop on a batch of small fits (fit_many -> residuals_many -> set the rejected weights to 0 ->
+ * fit_many): residuals at every problem's own points and four numbers per problem, in one launch.  Layouts as above, with
+ * xdata(l1xdat, *), ydata, wdata and resid addressed by the global index.  For point i, local index p = i - offsets[k], of
+ * problem k:
+ *   f_i      the double window sum splpak_eval_many_* forms for it (value pattern), before any rounding;
+ *   r_i      (double) y_i - f_i;   resid[i] = (T) r_i, written for EVERY point, a weight of 0 included (a caller clips on it);
+ *   w_i      1 for every point of the problem when wdata == NULL or the problem's FIRST weight is negative (as
+ *            splpak_fit_many_*), else (double) wdata[i].  A point with w_i == 0 is selected out of the statistics and never
+ *            multiplied: its value may be NaN.
+ *   stats + 4k   [0] the points counted, [1] S = sum (w_i r_i)^2, [2] m = max |w_i r_i|, [3] the smallest local index p that
+ *            attains m; [3] = -1 and [1] = [2] = 0 when nothing is counted.
+ * The order of S is part of the contract: lane l of 64 starts from 0 and adds, for p = l, l + 64, l + 128, ... in ascending
+ * order, the product t*t with t = w_i*r_i -- every multiplication and every addition rounded on its own, no contraction --, and
+ * the 64 lane sums are combined by a butterfly: for o = 32, 16, .., 1 every lane adds the sum of lane (l xor o) to its own.
+ * The bits of a problem's four numbers therefore depend on its own points, values, weights and coefficients alone: not on
+ * nbatch, its position, its neighbours, the launch shape or the host / _dev entry.  There are no floating-point atomics.
+ * Non-finite values among the counted points may give non-finite or unspecified [1..3].
+ * Algorithm.  One wave per problem, the waves stride over the problems; the wave reads x, y and w once, evaluates, writes the
+ * residual and keeps its lane accumulators.  A problem of very many points is walked by its one wave: the entry is for many
+ * SMALL problems, as splpak_fit_many_* is.
+ * resid or stats may be NULL, not both.  Status, decided on the host before any device work, the first failing check wins, and
+ * on every one of them nothing is written:
+ *   SPLPAK_E_BADARG (offsets, nodes, xmin or xmax null; nbatch < 1; offsets that decrease); 101; SPLPAK_E_UNSUPPORTED
+ *   (ndim > 4); 102; 103; 104 (ldcoef < ncol, as splpak_fit_many_* says it); SPLPAK_E_BADARG (l1xdat < ndim; xdata, ydata or
+ *   coef null; resid and stats both null).
+ * A batch without points returns 0 with stats filled as for problems without points. */
+int32_t splpak_residuals_many_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xdata,
+                                  int32_t l1xdat, const double *ydata, const double *wdata /* may be NULL */, const double *coef,
+                                  int64_t ldcoef, const double *xmin, const double *xmax, const int32_t *nodes,
+                                  double *resid /* may be NULL */, double *stats /* 4 per problem, may be NULL */);
+/* REAL32 storage: resid is float, the arithmetic and stats stay double */
+int32_t splpak_residuals_many_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xdata,
+                                  int32_t l1xdat, const float *ydata, const float *wdata /* may be NULL */, const float *coef,
+                                  int64_t ldcoef, const float *xmin, const float *xmax, const int32_t *nodes,
+                                  float *resid /* may be NULL */, double *stats /* 4 per problem, may be NULL */);
+/* the same on resident data: xdata, ydata, wdata, coef, resid and stats are device arrays; offsets, xmin, xmax and nodes are host
+ * arrays.  Asynchronous on `stream` exactly as splpak_eval_many_dev_*: stats stays in the caller's device memory. */
+int32_t splpak_residuals_many_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xdata_dev,
+                                      int32_t l1xdat, const double *ydata_dev, const double *wdata_dev /* may be NULL */,
+                                      const double *coef_dev, int64_t ldcoef, const double *xmin, const double *xmax,
+                                      const int32_t *nodes, double *resid_dev /* may be NULL */, double *stats_dev /* may be NULL */,
+                                      void *stream);
+int32_t splpak_residuals_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xdata_dev,
+                                      int32_t l1xdat, const float *ydata_dev, const float *wdata_dev /* may be NULL */,
+                                      const float *coef_dev, int64_t ldcoef, const float *xmin, const float *xmax,
+                                      const int32_t *nodes, float *resid_dev /* may be NULL */, double *stats_dev /* may be NULL */,
+                                      void *stream);
+/* host counters of the calling thread's last splpak_eval_many_* or splpak_residuals_many_* call (nothing is waited for):
+ * [0] workgroups launched, [1] launches of the call, [2] queries / points sent, [3] problems, [4] eval_many: the queries one
+ * sweep of the launch covers (the launch strides over the rest); residuals_many: 0 (a sweep covers [0] problems, one wave
+ * each), [5] 1 for eval_many, 2 for residuals_many, [6] [7] 0.  All 0 after a call its ladder refused. */
+int32_t splpak_debug_eval_many_stats(int64_t out8[8]);
+
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev
  * (the components of a velocity, a time series on fixed sensors, bootstrap replicas), which otherwise takes one
  * splpak_eval_* call per field -- each reading the coordinates, building the factor tables and, for a large batch on a

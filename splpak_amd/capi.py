@@ -44,6 +44,9 @@ SYMBOLS = [
     "splpak_fit_grid_weighted_dev_f32", "splpak_debug_fit_grid_weighted_stage_f64", "splpak_debug_fit_grid_weighted_stats",
     "splpak_fit_many_f64", "splpak_fit_many_f32", "splpak_fit_many_dev_f64", "splpak_fit_many_dev_f32", "splpak_fit_many_lds_bytes",
     "splpak_debug_fit_many_stats",
+    "splpak_eval_many_f64", "splpak_eval_many_f32", "splpak_eval_many_dev_f64", "splpak_eval_many_dev_f32",
+    "splpak_residuals_many_f64", "splpak_residuals_many_f32", "splpak_residuals_many_dev_f64", "splpak_residuals_many_dev_f32",
+    "splpak_debug_eval_many_stats",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
     "splpak_debug_eval_fields_stats",
     "splpak_synth_points_f64", "splpak_synth_queries_f64",
@@ -220,6 +223,24 @@ def lib() -> C.CDLL:
     L.splpak_fit_many_lds_bytes.argtypes = [i32, _ip]
     L.splpak_debug_fit_many_stats.restype = i32
     L.splpak_debug_fit_many_stats.argtypes = [_lp]
+    L.splpak_eval_many_f64.restype = i32
+    L.splpak_eval_many_f64.argtypes = [i32, i32, _lp, _dp, i32, _ip, _dp, i64, _dp, _dp, _ip, _dp]
+    L.splpak_eval_many_f32.restype = i32
+    L.splpak_eval_many_f32.argtypes = [i32, i32, _lp, _fp, i32, _ip, _fp, i64, _fp, _fp, _ip, _fp]
+    L.splpak_eval_many_dev_f64.restype = i32
+    L.splpak_eval_many_dev_f64.argtypes = [i32, i32, _lp, vp, i32, _ip, vp, i64, _dp, _dp, _ip, vp, vp]
+    L.splpak_eval_many_dev_f32.restype = i32
+    L.splpak_eval_many_dev_f32.argtypes = [i32, i32, _lp, vp, i32, _ip, vp, i64, _fp, _fp, _ip, vp, vp]
+    L.splpak_residuals_many_f64.restype = i32
+    L.splpak_residuals_many_f64.argtypes = [i32, i32, _lp, _dp, i32, _dp, _dp, _dp, i64, _dp, _dp, _ip, _dp, _dp]
+    L.splpak_residuals_many_f32.restype = i32
+    L.splpak_residuals_many_f32.argtypes = [i32, i32, _lp, _fp, i32, _fp, _fp, _fp, i64, _fp, _fp, _ip, _fp, _dp]
+    L.splpak_residuals_many_dev_f64.restype = i32
+    L.splpak_residuals_many_dev_f64.argtypes = [i32, i32, _lp, vp, i32, vp, vp, vp, i64, _dp, _dp, _ip, vp, vp, vp]
+    L.splpak_residuals_many_dev_f32.restype = i32
+    L.splpak_residuals_many_dev_f32.argtypes = [i32, i32, _lp, vp, i32, vp, vp, vp, i64, _fp, _fp, _ip, vp, vp, vp]
+    L.splpak_debug_eval_many_stats.restype = i32
+    L.splpak_debug_eval_many_stats.argtypes = [_lp]
     L.splpak_eval_fields_f64.restype = i32
     L.splpak_eval_fields_f64.argtypes = [i32, i64, _dp, i32, _ip, i32, _dp, i64, _dp, _dp, _ip, _dp, i64]
     L.splpak_eval_fields_f32.restype = i32
@@ -814,6 +835,67 @@ def debug_fit_many_stats():
     return tuple(int(t) for t in v)
 
 
+def _many_host(offsets, x, dt):
+    """(offsets as int64, nbatch, x as a (npoints, ld) array of dt) of a batch in fit_many's layout."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    x = np.ascontiguousarray(x, dtype=dt)
+    if x.ndim == 1:
+        x = x.reshape(-1, 1)
+    return offsets, offsets.size - 1, x
+
+
+def evaluate_many(ndim, offsets, xq, nderiv, coef, xmin, xmax, nodes, real32=False, ldxq=None, ldcoef=None, out=None):
+    """A batch of small fits at each problem's own points in one launch (splpak_eval_many_*), the evaluation side of fit_many:
+    problem k owns the queries offsets[k] .. offsets[k+1]-1 of xq (nqueries, ldxq) and has its coefficients in row k of `coef`
+    (nbatch, ldcoef), where fit_many put them; one nderiv pattern (None: values).  -> (out, ierror): `out` (given, or zeros
+    of xq's length) is written at the batch's indices only, each value with the bits of `evaluate` on that problem alone."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets, nbatch, xq = _many_host(offsets, xq, dt)
+    coef = np.ascontiguousarray(coef, dtype=dt)
+    ldc = int(ldcoef) if ldcoef is not None else (coef.shape[1] if coef.ndim > 1 else coef.size)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    if out is None:
+        out = np.zeros(max(xq.shape[0], int(offsets[-1]) if offsets.size else 0, 1), dtype=dt)
+    rc = _check((lib().splpak_eval_many_f32 if real32 else lib().splpak_eval_many_f64)(
+        ndim, nbatch, _p(offsets, _lp), _p(xq, rp), int(xq.shape[1] if ldxq is None else ldxq), _p(nd, _ip), _p(coef, rp), ldc,
+        _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), _p(out, rp)))
+    return out, rc
+
+
+def residuals_many(ndim, offsets, xdata, ydata, wdata, coef, xmin, xmax, nodes, real32=False, l1xdat=None, ldcoef=None,
+                   want_resid=True, want_stats=True):
+    """Residuals and per-problem statistics of a batch of small fits in one launch (splpak_residuals_many_*): the pass between two
+    fit_many calls of a clipping loop.  Layouts as fit_many.  -> (resid or None, stats (nbatch, 4) or None, ierror); stats[k] =
+    (points counted, sum (w r)^2, max |w r|, first local index of the max, -1 when nothing is counted).  resid is written at the
+    batch's indices only (zeros elsewhere)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
+    ydata = np.ascontiguousarray(ydata, dtype=dt)
+    if wdata is not None:
+        wdata = np.ascontiguousarray(wdata, dtype=dt)
+    coef = np.ascontiguousarray(coef, dtype=dt)
+    ldc = int(ldcoef) if ldcoef is not None else (coef.shape[1] if coef.ndim > 1 else coef.size)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    resid = np.zeros(max(ydata.size, 1), dtype=dt) if want_resid else None
+    stats = np.full((max(nbatch, 1), 4), -999.0) if want_stats else None
+    rc = _check((lib().splpak_residuals_many_f32 if real32 else lib().splpak_residuals_many_f64)(
+        ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(xdata.shape[1] if l1xdat is None else l1xdat), _p(ydata, rp), _p(wdata, rp),
+        _p(coef, rp), ldc, _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), _p(resid, rp), _p(stats, _dp)))
+    return resid, stats, rc
+
+
+def debug_eval_many_stats():
+    """Host counters of this thread's last evaluate_many / residuals_many call: (workgroups launched, launches, queries / points
+    sent, problems, queries one sweep of an evaluate_many launch covers (residuals_many: 0), 1 evaluate_many / 2 residuals_many,
+    0, 0)."""
+    v = np.zeros(8, dtype=np.int64)
+    _check(lib().splpak_debug_eval_many_stats(_p(v, _lp)))
+    return tuple(int(t) for t in v)
+
+
 def evaluate_fields(ndim, xq, nderiv, coefs, xmin, xmax, nodes, real32=False, ldcoef=None, ldout=None):
     """Several coefficient sets at the same points under one nderiv pattern (splpak_eval_fields_*): `coefs` is (nfields, ncol)
     or (ncol,), field k in row k.  ldcoef / ldout (>= ncol / nq) are the distances the library is given between the fields'
@@ -1147,6 +1229,44 @@ def evaluate_fields_dev(ndim, xq, nderiv, coef, xmin, xmax, nodes, out, stream=0
     rp = _fp if real32 else _dp
     return _check(fn(ndim, int(nq), xq.data_ptr(), int(ldx), _p(nd, _ip), nfields, coef.data_ptr(), ldc, _p(xmin, rp), _p(xmax, rp),
                      _p(nodes, _ip), out.data_ptr(), ldo, C.c_void_p(stream)))
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def evaluate_many_dev(ndim, offsets, xq, nderiv, coef, xmin, xmax, nodes, out, ldxq=None, ldcoef=None, stream=0):
+    """evaluate_many on torch device tensors (asynchronous on `stream`): xq (nqueries, ldxq), coef (nbatch, ldcoef) and out on the
+    device, offsets and nderiv on the host.  float32 tensors take the REAL32 entry.  -> ierror."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    real32 = str(xq.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    if ldxq is None:
+        ldxq = xq.shape[1] if xq.dim() > 1 else 1
+    if ldcoef is None:
+        ldcoef = coef.stride(0) if coef.dim() > 1 else coef.shape[0]
+    fn = lib().splpak_eval_many_dev_f32 if real32 else lib().splpak_eval_many_dev_f64
+    return _check(fn(ndim, offsets.size - 1, _p(offsets, _lp), xq.data_ptr(), int(ldxq), _p(nd, _ip), coef.data_ptr(), int(ldcoef),
+                     _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
+
+
+def residuals_many_dev(ndim, offsets, xdata, ydata, wdata, coef, xmin, xmax, nodes, resid, stats, l1xdat=None, ldcoef=None, stream=0):
+    """residuals_many on torch device tensors (asynchronous on `stream`): xdata, ydata, wdata (or None), coef, resid (or None)
+    and stats (nbatch, 4) float64 (or None) on the device, offsets on the host.  -> ierror."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    real32 = str(xdata.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    if l1xdat is None:
+        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
+    if ldcoef is None:
+        ldcoef = coef.stride(0) if coef.dim() > 1 else coef.shape[0]
+    fn = lib().splpak_residuals_many_dev_f32 if real32 else lib().splpak_residuals_many_dev_f64
+    return _check(fn(ndim, offsets.size - 1, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(), _ptr(wdata),
+                     coef.data_ptr(), int(ldcoef), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), _ptr(resid), _ptr(stats),
+                     C.c_void_p(stream)))
 
 
 def evaluate_grid_dev(ndim, npts, axes, nderiv, coef, xmin, xmax, nodes, out, stream=0):

@@ -23,6 +23,8 @@
 !!    `evaluate_derivatives` value + gradient (+ Hessian) of a batch in one pass,
 !!    `refit` fits new values on the points of the last `initialize` with the factorisation that fit left on the GPU,
 !!    `evaluate_fields` evaluates several coefficient sets (what `refit` returns) at the same batch of points in one call,
+!!    `evaluate_each` evaluates the fits of `initialize_many`, each at its own points, and `residuals_each` forms their residuals
+!!    and per-problem sums, one launch each,
 !!    `evaluate_grid` evaluates every point of a tensor-product grid of points from its axes alone,
 !!    `evaluate_grid_derivatives` value + gradient (+ Hessian) on such a grid, one plane per entry, in one pass,
 !!    `integrate_grid` integrates the fit over the cells of a tensor grid (cell integrals, projections), `integrate` over one box,
@@ -74,6 +76,8 @@ module splpak_module
         procedure,public :: initialize_grid => splpak_fit_grid      !! fit of samples on a tensor-product grid of points (additive)
         procedure,public :: initialize_grid_weighted => splpak_fit_grid_weighted   !! the same with a weight per sample (additive)
         procedure,public :: initialize_many => splpak_fit_many      !! many small independent fits on one node grid in one launch (additive)
+        procedure,public :: evaluate_each => splpak_eval_each       !! the fits of initialize_many, each at its own points, in one launch (additive)
+        procedure,public :: residuals_each => splpak_residuals_each !! their residuals and per-problem sums in one launch (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
         procedure,public :: evaluate_derivatives => splpak_derivs_many !! value + gradient (+ Hessian) of a batch (additive)
@@ -214,6 +218,30 @@ module splpak_module
             type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, status, info
             real(wp),value :: xtrap
         end function c_fit_many
+#ifdef REAL32
+        integer(c_int32_t) function c_eval_many(ndim,nbatch,offsets,xq,ldxq,nderiv,coef,ldcoef,xmin,xmax,nodes,out) &
+                                                bind(C,name='splpak_eval_many_f32')
+#else
+        integer(c_int32_t) function c_eval_many(ndim,nbatch,offsets,xq,ldxq,nderiv,coef,ldcoef,xmin,xmax,nodes,out) &
+                                                bind(C,name='splpak_eval_many_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr
+            integer(c_int32_t),value :: ndim, nbatch, ldxq
+            integer(c_int64_t),value :: ldcoef
+            type(c_ptr),value :: offsets, xq, nderiv, coef, xmin, xmax, nodes, out
+        end function c_eval_many
+#ifdef REAL32
+        integer(c_int32_t) function c_residuals_many(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,coef,ldcoef,xmin,xmax,nodes, &
+                                                     resid,stats) bind(C,name='splpak_residuals_many_f32')
+#else
+        integer(c_int32_t) function c_residuals_many(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,coef,ldcoef,xmin,xmax,nodes, &
+                                                     resid,stats) bind(C,name='splpak_residuals_many_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr
+            integer(c_int32_t),value :: ndim, nbatch, l1xdat
+            integer(c_int64_t),value :: ldcoef
+            type(c_ptr),value :: offsets, xdata, ydata, wdata, coef, xmin, xmax, nodes, resid, stats
+        end function c_residuals_many
 #ifdef REAL32
         integer(c_int32_t) function c_eval_fields(ndim,nq,xq,ldxq,nderiv,nfields,coef,ldcoef,xmin,xmax,nodes,out,ldout) &
                                                   bind(C,name='splpak_eval_fields_f32')
@@ -761,6 +789,98 @@ module splpak_module
         end if
 #endif
     end subroutine splpak_fit_many
+
+    !> The fits of `initialize_many`, each at its own points, in one launch (include/splpak_hip.h, splpak_eval_many_f64): problem
+    !! k owns the points offsets(k)+1 .. offsets(k+1) of x(ldx,*) and f, and has its coefficients in coef(:,k), where
+    !! `initialize_many` put them.  f(i) is the very value `evaluate_many` returns for x(:,i) with coef(:,k) (with `nderiv`, that
+    !! partial derivative; one pattern for all problems); entries of f outside offsets(1)+1 .. offsets(nbatch+1) are not touched.
+    !! (`evaluate_many` is a batch of points of ONE fit, `evaluate_fields` several fits at the SAME points.)  ierror: 101..104 as
+    !! splde (104: computed with nderiv clamped), -3 for a bad offset or leading dimension.  Refused with -4 under set_host,
+    !! set_gpus(n > 1) and in the -DREAL128 build, exactly as `initialize_many` is.
+    subroutine splpak_eval_each(me,ndim,nbatch,offsets,x,ldx,coef,ldcoef,xmin,xmax,nodes,f,ierror,nderiv)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, ldx, ldcoef
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: x(ldx,*)
+        real(wp),intent(in),target :: coef(ldcoef,*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(inout),target :: f(*)
+        integer,intent(out) :: ierror
+        integer,intent(in),optional,target :: nderiv(*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pd
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' evaluate_each - not available in the -DREAL128 build: call evaluate_many for every problem')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' evaluate_each - not available under set_host or set_gpus(n > 1): '// &
+                               'call evaluate_many for every problem')
+            return
+        end if
+        pd = c_null_ptr
+        if (present(nderiv)) pd = c_loc(nderiv)
+        rc = c_eval_many(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(x), int(ldx,c_int32_t), pd, c_loc(coef), &
+                         int(ldcoef,c_int64_t), c_loc(xmin), c_loc(xmax), c_loc(nodes), c_loc(f))
+        ierror = int(rc)
+        select case (ierror)
+        case (0)
+        case (101); call report(ierror,' splfe or splde - NDIM is less than 1')
+        case (102); call report(ierror,' splfe or splde - NODES(IDIM) is less than  4for some IDIM')
+        case (103); call report(ierror,' splfe or splde - XMIN(IDIM) = XMAX(IDIM) for some IDIM')
+        case (104); call report(ierror,' splde - NDERIV(IDIM) IS less than 0 or greater than 2 for some IDIM')
+        case default
+            if (ierror < 0) call report_library_failure(ierror,'evaluate_each')
+        end select
+#endif
+    end subroutine splpak_eval_each
+
+    !> Residuals and per-problem sums of the fits of `initialize_many` in one launch (splpak_residuals_many_f64): the pass
+    !! between two `initialize_many` calls of a clipping loop.  resid(i) = ydata(i) - f(i) for every point, a weight of 0
+    !! included; stats(:,k) = [ points counted, S = sum (w r)**2, max |w r|, the smallest ZERO-BASED local index that attains it
+    !! (-1 and S = max = 0 when nothing is counted) ].  Weights as `initialize_many`: without `wdata`, or with a negative first
+    !! weight of a problem, every point counts with weight 1; a point of weight 0 is left out of the sums.  S is summed in the
+    !! order the header fixes (64 strided partial sums, then a butterfly), so stats(:,k) depends on problem k alone.
+    !! ierror: 101..103, 104 for ldcoef below the number of coefficients, -3 for a bad offset or leading dimension.  Refused
+    !! with -4 under set_host, set_gpus(n > 1) and in the -DREAL128 build, exactly as `initialize_many` is.
+    subroutine splpak_residuals_each(me,ndim,nbatch,offsets,xdata,l1xdat,ydata,coef,ldcoef,xmin,xmax,nodes,resid,stats,ierror,wdata)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, l1xdat, ldcoef
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: xdata(l1xdat,*), ydata(*)
+        real(wp),intent(in),target :: coef(ldcoef,*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(inout),target :: resid(*)
+        real(c_double),intent(inout),target :: stats(4,*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: wdata(*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pw
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' residuals_each - not available in the -DREAL128 build')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' residuals_each - not available under set_host or set_gpus(n > 1)')
+            return
+        end if
+        pw = c_null_ptr
+        if (present(wdata)) pw = c_loc(wdata)
+        rc = c_residuals_many(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
+                              c_loc(ydata), pw, c_loc(coef), int(ldcoef,c_int64_t), c_loc(xmin), c_loc(xmax), c_loc(nodes), &
+                              c_loc(resid), c_loc(stats))
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'residuals_each')
+        end if
+#endif
+    end subroutine splpak_residuals_each
 
     !> New values on the points of this object's last `initialize`: several fields sampled at the same points (the
     !! components of a velocity, a time series on a fixed sensor layout, bootstrap replicas) cost one `initialize` and one
