@@ -728,7 +728,10 @@ int32_t splpak_fit_many_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets
                             const int32_t *nodes, float xtrap, float *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
                             double *info /* 10 per problem, may be NULL */);
 /* the same on resident data: xdata, ydata, wdata and coef are device arrays; offsets, xmin, xmax, nodes, status and info are
- * host arrays.  Not asynchronous: `stream` is synchronised once, after the launch, for the statuses. */
+ * host arrays.  Not asynchronous: `stream` is synchronised once, after the launch, for the statuses.  The offsets, the list of
+ * the problems that run and their results go through the calling thread's scratch (released by splpak_shutdown): once that
+ * holds the batch, no hipMalloc / hipFree: the call waits for `stream`, which waits for the thread's previous batch call where
+ * that still uses the scratch, and not for other work of the device. */
 int32_t splpak_fit_many_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xdata_dev, int32_t l1xdat,
                                 const double *ydata_dev, const double *wdata_dev /* may be NULL */, const double *xmin, const double *xmax,
                                 const int32_t *nodes, double xtrap, double *coef_dev, int64_t ldcoef, int32_t *status /* host */,
@@ -740,7 +743,8 @@ int32_t splpak_fit_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *off
 int64_t splpak_fit_many_lds_bytes(int32_t ndim, const int32_t *nodes);
 /* host counters of the calling thread's last splpak_fit_many_* call (nothing is waited for): [0] workgroups launched, [1] LDS
  * bytes per workgroup, [2] launches of the call, [3] problems sent to the device, [4] problems refused with 105, [5] the
- * largest number of refinement steps over the problems, [6] [7] 0. */
+ * largest number of refinement steps over the problems, [6] device allocations (hipMalloc) the call made: 0 for a _dev call
+ * whose scratch was large enough, [7] 0. */
 int32_t splpak_debug_fit_many_stats(int64_t out8[8]);
 
 /* The evaluation side of splpak_fit_many_*: problem k's coefficients at problem k's own points, one launch whatever nbatch is

@@ -829,7 +829,8 @@ def fit_many_lds_bytes(ndim, nodes) -> int:
 
 def debug_fit_many_stats():
     """Host counters of this thread's last fit_many call: (workgroups launched, LDS bytes per workgroup, launches, problems sent
-    to the device, problems refused with 105, the largest number of refinement steps, 0, 0)."""
+    to the device, problems refused with 105, the largest number of refinement steps, device allocations (hipMalloc) the call
+    made -- 0 for a fit_many_dev call whose per-thread scratch was large enough --, 0)."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_fit_many_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)

@@ -14,7 +14,7 @@
 // path (evalregion.hip), the run path (evalruns.hip) and the region sort (evalsort.hip),
 // tried in that order by the dispatchers at the end of this file.
 #include "evalpaths.hpp"
-#include "evalmany.hpp"
+#include "manyhost.hpp"
 
 namespace splpak {
 
@@ -144,7 +144,7 @@ void eval_scratch_shutdown()
     eval_persistent_shutdown();
     eval_runs_shutdown();
     eval_sort_shutdown();
-    eval_many_shutdown();
+    many_scratch_shutdown();
 }
 
 // The sorted paths, fastest first: the persistent region path, the run path, the region sort.  hipErrorNotSupported of a

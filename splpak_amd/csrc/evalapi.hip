@@ -9,6 +9,7 @@
 // Where two entries of a family have always answered differently, the difference is a named parameter of the ladder.
 #include "plan.hpp"
 #include "basis.hpp"
+#include "manyhost.hpp"
 
 #include <cstdio>
 #include <vector>
@@ -27,28 +28,6 @@ static int eval_validate(int32_t ndim, const int32_t *nderiv, const double *xmin
     return v;
 }
 
-// device copies of a host entry's arrays: freed when the entry returns
-struct DevStage {
-    std::vector<void *> owned;
-    ~DevStage() { for (void *q : owned) (void)hipFree(q); }
-    template <typename T> bool alloc(T **ptr, size_t count)
-    {
-        void *q = nullptr;
-        if (count == 0) count = 1;
-        const hipError_t e = hip_malloc_retry(&q, count * sizeof(T));      // (the one-shot fit's cached plan -- 35 GB at 64^3 -- may be in the way)
-        if (e != hipSuccess) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "hipMalloc of %.3f GB failed: %s", (double)(count * sizeof(T)) / 1e9, hipGetErrorString(e));
-            set_error(buf);
-            (void)hipGetLastError();
-            return false;
-        }
-        owned.push_back(q);
-        *ptr = static_cast<T *>(q);
-        return true;
-    }
-};
-
 // A host entry after its checks: in (n_in) and coef (ncol) go to the device, launch(in, coef, out) runs on the null stream and
 // leaves nplanes blocks of n results back to back (cleared first when `clear`); block k comes back to out + k * ldout, so that
 // the caller's words between the blocks keep their contents.  status(e) turns what the copies and the launch returned into
@@ -57,9 +36,9 @@ template <typename T, typename F, typename S>
 static int32_t staged_call(const T *in, size_t n_in, const T *coef, size_t ncol, T *out, size_t n, int nplanes, long long ldout, bool clear,
                            F &&launch, S &&status)
 {
-    DevStage stage;
+    CallStage stage;
     T *din = nullptr, *dc = nullptr, *dout = nullptr;
-    if (!stage.alloc(&din, n_in) || !stage.alloc(&dc, ncol) || !stage.alloc(&dout, n * (size_t)nplanes)) return SPLPAK_E_NOMEM;
+    if (!stage.get(&din, n_in) || !stage.get(&dc, ncol) || !stage.get(&dout, n * (size_t)nplanes)) return SPLPAK_E_NOMEM;
     hipError_t e = hipMemcpy(din, in, sizeof(T) * n_in, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dc, coef, sizeof(T) * ncol, hipMemcpyHostToDevice);
     if (e == hipSuccess && clear) e = hipMemset(dout, 0, sizeof(T) * n * (size_t)nplanes);
@@ -275,8 +254,7 @@ static int32_t eval_fields_host(int32_t ndim, int64_t nq, const T *xq, int32_t l
         if (zero) zero_results(out, nq, nfields, ldout, false, nullptr);
         return rc;
     }
-    const size_t n_coef = (size_t)(nfields - 1) * (size_t)ldcoef + (size_t)g.ncol;
-    return staged_call<T>(xq, (size_t)nq * ldxq, coef, n_coef, out, (size_t)nq, nfields, ldout, false,
+    return staged_call<T>(xq, (size_t)nq * ldxq, coef, coef_block_len(nfields, ldcoef, g.ncol), out, (size_t)nq, nfields, ldout, false,
                           [&](const T *dq, const T *dc, T *dout) {
                               return launch_eval_fields<T>(g, nq, dq, ldxq, nderiv, nfields, dc, ldcoef, dout, nq, nullptr);
                           },

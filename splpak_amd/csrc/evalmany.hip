@@ -17,8 +17,10 @@
 //                 batch, the position or the launch shape.  A problem of very many points is walked by its one wave.
 //
 // The coefficient sets are not staged in LDS: a 16-node set is 128 bytes and a wave's gathers stay in L1 / L2.
+//
+// The file also holds the per-thread device scratch of the batch entries' tables (manyhost.hpp).
 #include "evalcore.hpp"
-#include "evalscratch.hpp"
+#include "manyhost.hpp"
 #include "evalmany.hpp"
 
 #include <climits>
@@ -146,33 +148,17 @@ residuals_many_kernel(Grid g, int nbatch, const long long *__restrict__ offsets,
     }
 }
 
-thread_local DevScratch<1> g_offsets;
-
 }  // namespace
 
-hipError_t eval_many_offsets(const int64_t *offsets, int nbatch, hipStream_t st, const long long **offsets_dev)
-{
-    static_assert(sizeof(long long) == sizeof(int64_t), "offsets are uploaded as they are");
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const size_t bytes = sizeof(int64_t) * ((size_t)nbatch + 1);
-    const size_t need[1] = {bytes};
-    e = g_offsets.ensure(dev, need, /*may_release_plan=*/true);
-    if (e != hipSuccess) { (void)hipGetLastError(); return hipErrorOutOfMemory; }
-    e = g_offsets.wait_on(st);
-    // (pageable memory: the copy has left `offsets` when the call returns)
-    if (e == hipSuccess) e = hipMemcpyAsync(g_offsets.buf[0], offsets, bytes, hipMemcpyHostToDevice, st);
-    *offsets_dev = g_offsets.as<long long>(0);
-    return e;
-}
+// the per-thread scratch of the batch entries (manyhost.hpp)
+thread_local DevScratch<1> t_many_offsets;
+thread_local DevScratch<2> t_fit_many_tables;
 
-void eval_many_offsets_used(hipStream_t st)
+void many_scratch_shutdown()
 {
-    if (g_offsets.last) (void)g_offsets.mark_used(st);
+    t_many_offsets.release();
+    t_fit_many_tables.release();
 }
-
-void eval_many_shutdown() { g_offsets.release(); }
 
 template <typename T>
 hipError_t launch_eval_many(const Grid &g, int nbatch, const long long *offsets_dev, long long first, long long nq, long long base,

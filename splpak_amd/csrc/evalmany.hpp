@@ -14,11 +14,7 @@ constexpr int RESMANY_WAVES = 256 * 32;           // residuals_many: a one-wave 
 // host counters of the calling thread's last call of either family (splpak_debug_eval_many_stats)
 extern thread_local long long t_eval_many_stats[8];
 
-// The calling thread's device copy of a call's offsets (nbatch + 1), uploaded on st behind the previous use of the buffer.
-// The caller launches on st and then calls eval_many_offsets_used(st).  hipErrorOutOfMemory: no room for the copy.
-hipError_t eval_many_offsets(const int64_t *offsets, int nbatch, hipStream_t st, const long long **offsets_dev);
-void eval_many_offsets_used(hipStream_t st);
-void eval_many_shutdown();
+// offsets_dev: the device copy of a call's offsets (manyhost.hpp: many_offsets_upload).
 
 // out[i - base] for every query i of offsets[0] .. offsets[nbatch]-1: the bits of launch_eval's direct kernel on query i with
 // the coefficients of the problem that owns i.  nq = offsets[nbatch] - offsets[0] > 0; one launch.

@@ -1,35 +1,19 @@
 // The entries of the batch evaluation at each problem's own points (include/splpak_hip.h): splpak_eval_many_* and
 // splpak_residuals_many_* on host and device pointers, and their counters.  Each family has one ladder of checks, in the order
 // the header gives, all on the host; then evalmany.hip.  The _dev entries only enqueue: the one thing they upload is the
-// offsets, into the calling thread's scratch (eval_many_offsets).  The host entries stage the span of the batch's points and
-// (nbatch-1)*ldcoef + ncol coefficients through device memory of the call.
+// offsets, into the calling thread's scratch (manyhost.hpp: many_offsets_upload, held by a ScratchUse to the end of the
+// call).  The host entries stage the span of the batch's points and (nbatch-1)*ldcoef + ncol coefficients through device
+// memory of the call (manyhost.hpp: stage_span, stage_copy).
 #include "plan.hpp"
 #include "evalcore.hpp"
 #include "evalmany.hpp"
+#include "manyhost.hpp"
 
 #include <vector>
 
 using namespace splpak;
 
 namespace {
-
-// device memory of one host call, released with it
-struct CallStage {
-    std::vector<void *> held;
-    ~CallStage() { for (void *p : held) (void)hipFree(p); }
-    template <typename U> bool get(U **out, size_t count)
-    {
-        void *q = nullptr;
-        if (hip_malloc_retry(&q, (count ? count : 1) * sizeof(U)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("the device copies of the batch could not be allocated");
-            return false;
-        }
-        held.push_back(q);
-        *out = static_cast<U *>(q);
-        return true;
-    }
-};
 
 // The rungs both ladders open with.  True: the grid is built (rc = 0); false: rc is the status, and `zero` says whether it is
 // one of 101 / 102 / 103 (eval_many zeroes its results on these).
@@ -62,16 +46,6 @@ void many_counters(int family, long long npoints, int nbatch)
     t_eval_many_stats[5] = family;
 }
 
-int32_t many_status(hipError_t e, const char *what, int rc)
-{
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        set_error("the device copy of the offsets could not be allocated");
-        return SPLPAK_E_NOMEM;
-    }
-    return hip_ok(e, what) ? rc : SPLPAK_E_NODEVICE;
-}
-
 // ---- splpak_eval_many_* ----
 template <typename T>
 int32_t eval_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *offsets, const T *xq, int32_t ldxq, const int32_t *nderiv,
@@ -83,9 +57,9 @@ int32_t eval_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *o
     bool zero = false;
     if (!many_open(ndim, nbatch, offsets, xmin, xmax, nodes, g, rc, zero)) {
         if (zero && out) {
-            const long long lo = offsets[0], n = offsets[nbatch] - lo;
-            if (dev) { if (n > 0) (void)hipMemsetAsync(out + lo, 0, sizeof(T) * (size_t)n, st); }
-            else for (long long i = 0; i < n; ++i) out[lo + i] = (T)0;
+            const ManySpan sp = many_span(offsets, nbatch);
+            if (dev) { if (sp.n > 0) (void)hipMemsetAsync(out + sp.lo, 0, sizeof(T) * (size_t)sp.n, st); }
+            else for (long long i = 0; i < sp.n; ++i) out[sp.lo + i] = (T)0;
         }
         return rc;
     }
@@ -93,34 +67,35 @@ int32_t eval_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *o
     if (nderiv)
         for (int d = 0; d < ndim; ++d)
             if (nderiv[d] < 0 || nderiv[d] > 2) rc = 104;      // reported; evaluated with the orders clamped
-    const long long lo = offsets[0], nq = offsets[nbatch] - lo;
+    const ManySpan sp = many_span(offsets, nbatch);
+    const long long lo = sp.lo, nq = sp.n;
     many_counters(1, nq, nbatch);
     if (nq == 0) return rc;
     if (!xq || !coef || !out) { set_error("null argument"); return SPLPAK_E_BADARG; }
     if (int r = device_ready()) return r;
 
+    const char *what = "evaluation of a batch of fits";
+    const ScratchUse<1> use{t_many_offsets, st};
     const long long *off_dev = nullptr;
     if (dev) {
-        hipError_t e = eval_many_offsets(offsets, nbatch, st, &off_dev);
+        hipError_t e = many_offsets_upload(offsets, nbatch, st, &off_dev);
         if (e == hipSuccess) e = launch_eval_many<T>(g, nbatch, off_dev, lo, nq, 0, xq, ldxq, nderiv, coef, ldcoef, out, st);
-        eval_many_offsets_used(st);
-        return many_status(e, "evaluation of a batch of fits", rc);
+        return many_status(e, what, rc);
     }
     // the host form: the span of the batch's queries alone, the coefficient sets with the caller's ldcoef in one copy
-    const size_t ncoef = (size_t)(nbatch - 1) * (size_t)ldcoef + (size_t)g.ncol;
     std::vector<T> res((size_t)nq);
     CallStage cs;
-    T *xs = nullptr, *cd = nullptr, *od = nullptr;
-    if (!cs.get(&xs, (size_t)nq * (size_t)ldxq) || !cs.get(&cd, ncoef) || !cs.get(&od, (size_t)nq)) return SPLPAK_E_NOMEM;
-    hipError_t e = hipMemcpy(xs, xq + lo * ldxq, sizeof(T) * (size_t)nq * (size_t)ldxq, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(cd, coef, sizeof(T) * ncoef, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = eval_many_offsets(offsets, nbatch, nullptr, &off_dev);
-    if (e == hipSuccess) e = launch_eval_many<T>(g, nbatch, off_dev, lo, nq, lo, (const T *)xs, ldxq, nderiv, (const T *)cd, ldcoef, od, nullptr);
-    eval_many_offsets_used(nullptr);
+    const T *xs = nullptr, *cd = nullptr;
+    T *od = nullptr;
+    hipError_t e = stage_span<T>(cs, sp, xq, ldxq, nullptr, nullptr, &xs, nullptr, nullptr);
+    if (e == hipSuccess) e = stage_copy(cs, coef, coef_block_len(nbatch, ldcoef, g.ncol), &cd);
+    if (e == hipSuccess && !cs.get(&od, (size_t)nq)) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = many_offsets_upload(offsets, nbatch, nullptr, &off_dev);
+    if (e == hipSuccess) e = launch_eval_many<T>(g, nbatch, off_dev, lo, nq, lo, xs, ldxq, nderiv, cd, ldcoef, od, nullptr);
     if (e == hipSuccess) e = hipMemcpy(res.data(), od, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
         for (long long i = 0; i < nq; ++i) out[lo + i] = res[(size_t)i];
-    return many_status(e, "evaluation of a batch of fits", rc);
+    return many_status(e, what, rc);
 }
 
 // ---- splpak_residuals_many_* ----
@@ -139,7 +114,8 @@ int32_t residuals_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64
         set_error("l1xdat < ndim, a null pointer, or resid and stats both null");
         return SPLPAK_E_BADARG;
     }
-    const long long lo = offsets[0], npt = offsets[nbatch] - lo;
+    const ManySpan sp = many_span(offsets, nbatch);
+    const long long lo = sp.lo, npt = sp.n;
     many_counters(2, npt, nbatch);
     if (npt == 0 && !dev) {      // nothing for a device to do
         if (stats)
@@ -149,34 +125,29 @@ int32_t residuals_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64
     if (npt == 0 && !stats) return 0;
     if (int r = device_ready()) return r;
 
+    const char *what = "residuals of a batch of fits";
+    const ScratchUse<1> use{t_many_offsets, st};
     const long long *off_dev = nullptr;
     if (dev) {
-        hipError_t e = eval_many_offsets(offsets, nbatch, st, &off_dev);
+        hipError_t e = many_offsets_upload(offsets, nbatch, st, &off_dev);
         if (e == hipSuccess) e = launch_residuals_many<T>(g, nbatch, off_dev, 0, xdata, l1xdat, ydata, wdata, coef, ldcoef, resid, stats, st);
-        eval_many_offsets_used(st);
-        return many_status(e, "residuals of a batch of fits", 0);
+        return many_status(e, what, 0);
     }
-    const size_t ncoef = (size_t)(nbatch - 1) * (size_t)ldcoef + (size_t)g.ncol;
     std::vector<T> res(resid ? (size_t)npt : 0);
     CallStage cs;
-    T *xs = nullptr, *ys = nullptr, *wsd = nullptr, *cd = nullptr, *rd = nullptr;
+    const T *xs = nullptr, *ys = nullptr, *wsd = nullptr, *cd = nullptr;
+    T *rd = nullptr;
     double *sd = nullptr;
-    if (!cs.get(&xs, (size_t)npt * (size_t)l1xdat) || !cs.get(&ys, (size_t)npt) || (wdata && !cs.get(&wsd, (size_t)npt)) || !cs.get(&cd, ncoef) ||
-        (resid && !cs.get(&rd, (size_t)npt)) || (stats && !cs.get(&sd, 4 * (size_t)nbatch)))
-        return SPLPAK_E_NOMEM;
-    hipError_t e = hipMemcpy(xs, xdata + lo * l1xdat, sizeof(T) * (size_t)npt * (size_t)l1xdat, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ys, ydata + lo, sizeof(T) * (size_t)npt, hipMemcpyHostToDevice);
-    if (e == hipSuccess && wdata) e = hipMemcpy(wsd, wdata + lo, sizeof(T) * (size_t)npt, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(cd, coef, sizeof(T) * ncoef, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = eval_many_offsets(offsets, nbatch, nullptr, &off_dev);
-    if (e == hipSuccess)
-        e = launch_residuals_many<T>(g, nbatch, off_dev, lo, (const T *)xs, l1xdat, (const T *)ys, (const T *)wsd, (const T *)cd, ldcoef, rd, sd, nullptr);
-    eval_many_offsets_used(nullptr);
+    hipError_t e = stage_span(cs, sp, xdata, l1xdat, ydata, wdata, &xs, &ys, &wsd);
+    if (e == hipSuccess) e = stage_copy(cs, coef, coef_block_len(nbatch, ldcoef, g.ncol), &cd);
+    if (e == hipSuccess && ((resid && !cs.get(&rd, (size_t)npt)) || (stats && !cs.get(&sd, 4 * (size_t)nbatch)))) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = many_offsets_upload(offsets, nbatch, nullptr, &off_dev);
+    if (e == hipSuccess) e = launch_residuals_many<T>(g, nbatch, off_dev, lo, xs, l1xdat, ys, wsd, cd, ldcoef, rd, sd, nullptr);
     if (e == hipSuccess && resid) e = hipMemcpy(res.data(), rd, sizeof(T) * (size_t)npt, hipMemcpyDeviceToHost);
     if (e == hipSuccess && stats) e = hipMemcpy(stats, sd, sizeof(double) * 4 * (size_t)nbatch, hipMemcpyDeviceToHost);
     if (e == hipSuccess && resid)
         for (long long i = 0; i < npt; ++i) resid[lo + i] = res[(size_t)i];
-    return many_status(e, "residuals of a batch of fits", 0);
+    return many_status(e, what, 0);
 }
 
 }  // namespace

@@ -16,6 +16,7 @@ struct DevScratch {
     hipEvent_t last = nullptr;
     int dev = -1;
     bool used = false;            // `last` has been recorded since the buffers were allocated
+    long long allocs = 0;         // hipMalloc calls that succeeded, over the life of the object (the entries' debug counters)
 
     template <typename T> T *as(int i) const { return static_cast<T *>(buf[i]); }
 
@@ -47,7 +48,7 @@ struct DevScratch {
             bool released = false;
             e = may_release_plan ? hip_malloc_retry(&buf[i], want[i], &released) : hipMalloc(&buf[i], want[i]);
             if (released) may_release_plan = false;
-            if (e == hipSuccess) bytes[i] = want[i];
+            if (e == hipSuccess) { bytes[i] = want[i]; ++allocs; }
             else buf[i] = nullptr;
         }
         if (e != hipSuccess) { release(); return e; }

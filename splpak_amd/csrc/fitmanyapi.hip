@@ -1,7 +1,11 @@
 // The entries of the batch of small fits (include/splpak_hip.h): splpak_fit_many_* on host and device pointers, the LDS
-// rule and the counters.  The ladder of checks in the order the header gives, all on the host; then fitmany.hip.
+// rule and the counters.  The ladder of checks in the order the header gives, all on the host; then fitmany.hip.  The tables
+// of a call -- offsets, problem list, results -- live in the calling thread's scratch (manyhost.hpp), each held by a
+// ScratchUse to the end of the call: a _dev call whose scratch is large enough allocates and frees nothing.  The host
+// entries stage the span of the batch's points and the compact coefficients through device memory of the call.
 #include "plan.hpp"
 #include "fitmany.hpp"
+#include "manyhost.hpp"
 
 #include <new>
 #include <vector>
@@ -9,24 +13,6 @@
 using namespace splpak;
 
 namespace {
-
-// device memory of one call, released with it
-struct CallScratch {
-    std::vector<void *> held;
-    ~CallScratch() { for (void *p : held) (void)hipFree(p); }
-    template <typename U> bool get(U **out, size_t count)
-    {
-        void *q = nullptr;
-        if (hipMalloc(&q, (count ? count : 1) * sizeof(U)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("the device scratch of the batch of fits could not be allocated");
-            return false;
-        }
-        held.push_back(q);
-        *out = static_cast<U *>(q);
-        return true;
-    }
-};
 
 const char *LDS_MESSAGE =
     "the grid needs more than 64 KiB of LDS per problem (splpak_fit_many_lds_bytes): loop splpak_fit_* over the problems instead";
@@ -63,11 +49,9 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
     try {
         const int ncol = a.g.ncol;
         std::vector<int> plist;
-        int first = 0;      // the status of the lowest-numbered problem that did not end in 0
         for (int k = 0; k < nbatch; ++k) {
             const bool empty = offsets[k + 1] == offsets[k];
             if (!empty) plist.push_back(k);
-            else if (first == 0) first = 105;
             if (status) status[k] = empty ? 105 : 0;
             if (info) for (int j = 0; j < 10; ++j) info[(size_t)k * 10 + j] = 0.0;
         }
@@ -75,57 +59,50 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
         t_fit_many_stats[1] = a.sh.bytes;
         t_fit_many_stats[3] = nrun;
         t_fit_many_stats[4] = nbatch - nrun;
-        if (nrun == 0) return first;
+        if (nrun == 0) return 105;
 
         if (int r = device_ready()) return r;
-        // (declared before the scratch: an error return frees the scratch first, which waits for the copies queued into these)
+        const char *what = "a batch of fits";
         std::vector<double> res((size_t)nrun * FM_RESULT);
-        std::vector<T> ch;
-        CallScratch cs;
-        int *plist_dev = nullptr;
-        long long *off_dev = nullptr;
-        double *res_dev = nullptr;
-        if (!cs.get(&plist_dev, (size_t)nrun) || !cs.get(&off_dev, (size_t)nbatch + 1) || !cs.get(&res_dev, (size_t)nrun * FM_RESULT))
-            return SPLPAK_E_NOMEM;
-        static_assert(sizeof(long long) == sizeof(int64_t), "offsets are uploaded as they are");
-        SPLPAK_HIP_TRY(hipMemcpyAsync(plist_dev, plist.data(), sizeof(int) * (size_t)nrun, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
-        SPLPAK_HIP_TRY(hipMemcpyAsync(off_dev, offsets, sizeof(int64_t) * ((size_t)nbatch + 1), hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
+        std::vector<T> ch(dev ? 0 : (size_t)nrun * (size_t)ncol);
+        const long long allocs_before = t_many_offsets.allocs + t_fit_many_tables.allocs;
+        const ScratchUse<1> use_offsets{t_many_offsets, st};
+        const ScratchUse<2> use_tables{t_fit_many_tables, st};
+        CallStage cs;      // (the host entries alone)
+        const size_t need[2] = {sizeof(int) * (size_t)nrun, sizeof(double) * res.size()};
+        hipError_t e = many_offsets_upload(offsets, nbatch, st, &a.offsets);
+        if (e == hipSuccess) e = scratch_begin(t_fit_many_tables, need, st);
+        // (pageable memory: the copy has left `plist` when the call returns)
+        if (e == hipSuccess) e = hipMemcpyAsync(t_fit_many_tables.buf[0], plist.data(), need[0], hipMemcpyHostToDevice, st);
         a.nrun = nrun;
-        a.plist = plist_dev;
-        a.offsets = off_dev;
+        a.plist = t_fit_many_tables.as<int>(0);
+        a.result = t_fit_many_tables.as<double>(1);
         a.l1xdat = l1xdat;
         a.xtrap = xtrap;
-        a.result = res_dev;
+        a.base = 0;
+        a.ldcoef = ldcoef;
+        a.compact = 0;
         const T *xd = xdata, *yd = ydata, *wd = wdata;
         T *cd = coef;
-        if (dev) {
-            a.base = 0;
-            a.ldcoef = ldcoef;
-            a.compact = 0;
-        } else {
+        if (!dev) {
             // the span of the batch's points alone, the coefficients of the problems that run back to back
-            const long long lo = offsets[0], npt = offsets[nbatch] - offsets[0];
-            T *xs = nullptr, *ys = nullptr, *wsd = nullptr;
-            if (!cs.get(&xs, (size_t)npt * (size_t)l1xdat) || !cs.get(&ys, (size_t)npt) || (wdata && !cs.get(&wsd, (size_t)npt)) ||
-                !cs.get(&cd, (size_t)nrun * (size_t)ncol))
-                return SPLPAK_E_NOMEM;
-            SPLPAK_HIP_TRY(hipMemcpyAsync(xs, xdata + lo * l1xdat, sizeof(T) * (size_t)npt * (size_t)l1xdat, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
-            SPLPAK_HIP_TRY(hipMemcpyAsync(ys, ydata + lo, sizeof(T) * (size_t)npt, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
-            if (wdata) SPLPAK_HIP_TRY(hipMemcpyAsync(wsd, wdata + lo, sizeof(T) * (size_t)npt, hipMemcpyHostToDevice, st), SPLPAK_E_NODEVICE);
-            xd = xs; yd = ys; wd = wsd;
-            a.base = lo;
+            const ManySpan sp = many_span(offsets, nbatch);
+            if (e == hipSuccess) e = stage_span(cs, sp, xdata, l1xdat, ydata, wdata, &xd, &yd, &wd);
+            if (e == hipSuccess && !cs.get(&cd, ch.size())) e = hipErrorOutOfMemory;
+            a.base = sp.lo;
             a.ldcoef = ncol;
             a.compact = 1;
         }
+        t_fit_many_stats[6] = t_many_offsets.allocs + t_fit_many_tables.allocs - allocs_before + (long long)cs.held.size();
+        if (e != hipSuccess) return many_status(e, what, 0);
         double seconds = 0.0;
         if (int r = fit_many_launch<T>(a, xd, yd, wd, cd, st, &seconds)) return r;
 
-        SPLPAK_HIP_TRY(hipMemcpyAsync(res.data(), res_dev, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
-        if (!dev) {
-            ch.resize((size_t)nrun * (size_t)ncol);
-            SPLPAK_HIP_TRY(hipMemcpyAsync(ch.data(), cd, sizeof(T) * ch.size(), hipMemcpyDeviceToHost, st), SPLPAK_E_NODEVICE);
-        }
-        SPLPAK_HIP_TRY(hipStreamSynchronize(st), SPLPAK_E_NODEVICE);
+        e = hipMemcpyAsync(res.data(), a.result, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !dev) e = hipMemcpyAsync(ch.data(), cd, sizeof(T) * ch.size(), hipMemcpyDeviceToHost, st);
+        const hipError_t waited = hipStreamSynchronize(st);      // (also after a failed copy: the one before it may still write `res`)
+        if (e == hipSuccess) e = waited;
+        if (e != hipSuccess) return many_status(e, what, 0);
         long long maxsteps = 0;
         int first_failed = -1;
         for (int r = 0; r < nrun; ++r) {

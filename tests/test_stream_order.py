@@ -717,3 +717,147 @@ def test_synth_points_then_a_fit_on_the_same_stream(monkeypatch, clock, streams)
         assert not got.differs(yi), (what, got.differs(yi), "equals the decoy's" if not got.differs(yd) else "neither")
     finally:
         plan.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# F. the batch entries and the per-thread scratch behind them (the offsets of all three families, fit_many's tables)
+SMALL_NODES = (9,)
+OFF_A = np.array([0, 40, 80, 120], dtype=np.int64)
+OFF_B = np.array([0, 20, 100, 120], dtype=np.int64)        # the same total and nbatch as OFF_A: every index stays in bounds
+
+
+def _small_batch(seed, keys):
+    """120 points of a 1-D batch of 3 problems on 9 nodes, and a coefficient row per problem."""
+    rng = np.random.default_rng(seed)
+    n = int(OFF_A[-1])
+    d = {"x": rng.uniform(0.0, 1.0, (n, 1)), "y": rng.standard_normal(n), "w": rng.uniform(0.5, 1.5, n),
+         "coef": rng.standard_normal((3, SMALL_NODES[0]))}
+    return {k: d[k] for k in keys}
+
+
+def _eval_many_entry(off):
+    def call(t, stream):
+        return (capi.evaluate_many_dev(1, off, t["x"], None, t["coef"], [0.0], [1.0], list(SMALL_NODES), t["out"], stream=stream),)
+    return _Entry(call, {"out": (int(off[-1]),)})
+
+
+def _residuals_many_entry(off):
+    def call(t, stream):
+        return (capi.residuals_many_dev(1, off, t["x"], t["y"], t["w"], t["coef"], [0.0], [1.0], list(SMALL_NODES), t["resid"], t["stats"],
+                                        stream=stream),)
+    return _Entry(call, {"resid": (int(off[-1]),), "stats": (off.size - 1, 4)})
+
+
+def _fit_many_entry(off, nodes=SMALL_NODES, counters=None):
+    """counters: a list that receives debug_fit_many_stats() of every call."""
+    nd, nbatch = len(nodes), off.size - 1
+
+    def call(t, stream):
+        rc, status, info = capi.fit_many_dev(nd, off, t["x"], t["y"], t["w"], [0.0] * nd, [1.0] * nd, list(nodes), t["coef"], xtrap=1.0,
+                                             stream=stream)
+        if counters is not None:
+            counters.append(capi.debug_fit_many_stats())
+        return rc, status, info[:, INFO]
+    return _Entry(call, {"coef": (nbatch, int(np.prod(nodes)))})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", ["evaluate_many", "residuals_many"])
+def test_many_evaluation_with_late_inputs(family, clock, streams):
+    """Both entries only enqueue; resid and stats of the residual pass are compared alike."""
+    if family == "evaluate_many":
+        entry, keys = _eval_many_entry(OFF_A), ("x", "coef")
+    else:
+        entry, keys = _residuals_many_entry(OFF_A), ("x", "y", "w", "coef")
+    _check_late(entry, _small_batch(51, keys), _small_batch(52, keys), streams, clock, family)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("second", ["evaluate_many", "fit_many"])
+def test_two_batches_share_the_offsets_scratch_across_streams(second, clock, streams):
+    """evaluate_many_dev with OFF_A on S behind a delay, then with no wait a call with OFF_B on S2 (fit_many_dev may block until
+    the delay ends): the second upload of the offsets has to wait for the first kernel.  Without the wait the first kernel reads
+    OFF_B: the values of `swapped` below."""
+    import torch
+    first = _eval_many_entry(OFF_A)
+    data_a = _small_batch(53, ("x", "coef"))
+    if second == "evaluate_many":
+        other, data_b = _eval_many_entry(OFF_B), _small_batch(54, ("x", "coef"))
+    else:
+        other, data_b = _fit_many_entry(OFF_B), _small_batch(54, ("x", "y", "w"))
+    (want_a, ms), (want_b, _) = _plain(first, data_a), _plain(other, data_b)
+    swapped, _ = _plain(_eval_many_entry(OFF_B), data_a)
+    assert want_a.differs(swapped), "the first batch gives the same values under either offsets: the test proves nothing"
+    if second == "evaluate_many":
+        assert want_a.differs(want_b)
+    else:
+        assert _fits_ok(want_b) and not want_b.host[1].any()
+    entries, ts, pinned = [first, other], [], []
+    for e, d in zip(entries, (data_a, data_b)):
+        t = {k: _dev(v) for k, v in d.items()}
+        t.update(e.outputs())
+        ts.append(t)
+        pinned.append(e.pinned())
+    queues = [streams.S, streams.S2]
+    torch.cuda.synchronize()
+    host = []
+    try:
+        d = clock.delay(streams.S, max(T_FACTOR * ms, T_FLOOR_MS))
+        for e, t, p, q in zip(entries, ts, pinned, queues):
+            host.append(e.call(t, q.cuda_stream))
+            with torch.cuda.stream(q):
+                for k in p:
+                    p[k].copy_(t[k], non_blocking=True)
+    finally:
+        for q in queues:
+            q.synchronize()
+    d.check(f"offsets scratch, then {second}")
+    for i, want in enumerate((want_a, want_b)):
+        got = _Result({k: pinned[i][k].numpy().copy() for k in pinned[i]}, host[i])
+        assert not got.differs(want), ("call", i + 1, got.differs(want))
+
+
+@pytest.mark.gpu
+def test_fit_many_scratch_regrows_and_is_kept():
+    """3 problems, 300, 300 again, 3 again: the small batch gives the same bits before and after the scratch grew, and a call
+    whose scratch is large enough makes no device allocation (slot [6] of the counters)."""
+    capi.shutdown()                         # (the scratch of earlier tests: the first calls below have to allocate)
+    counters = []
+    small, big = _fit_many_entry(OFF_A, counters=counters), _fit_many_entry(_many_offsets("1d"), MANY["1d"][0], counters=counters)
+    data_small, data_big = _small_batch(55, ("x", "y", "w")), _many_data("1d", 21)
+    r1, _ = _plain(small, data_small)
+    r2, _ = _plain(big, data_big)
+    r2b, _ = _plain(big, data_big)
+    r3, _ = _plain(small, data_small)
+    assert _fits_ok(r1, r2, r2b, r3)
+    assert not r3.differs(r1), r3.differs(r1)
+    assert not r2b.differs(r2), r2b.differs(r2)
+    allocs = [c[6] for c in counters]
+    print(f"device allocations of the four calls: {allocs}")
+    assert allocs[0] > 0 and allocs[1] > 0, allocs          # (the counter counts)
+    assert allocs[2] == 0 and allocs[3] == 0, allocs
+
+
+@pytest.mark.gpu
+def test_fit_many_does_not_wait_for_other_streams(clock, streams):
+    """With its scratch in place fit_many_dev frees nothing, so it returns while a delay still runs on another stream."""
+    import torch
+    assert streams.concurrent, NO_WINDOW
+    entry, data = _fit_many_entry(OFF_A), _small_batch(56, ("x", "y", "w"))
+    _plain(entry, data)                     # (the warm-up: what a first call allocates)
+    want, ms = _plain(entry, data)
+    assert _fits_ok(want)
+    t = {k: _dev(v) for k, v in data.items()}
+    t.update(entry.outputs())
+    torch.cuda.synchronize()
+    try:
+        d = clock.delay(streams.S, max(T_FACTOR * ms, T_FLOOR_MS))
+        host = entry.call(t, streams.S2.cuda_stream)
+        running = d.running()
+    finally:
+        streams.S.synchronize()
+        streams.S2.synchronize()
+    d.check("fit_many beside a delay")
+    got = _Result({"coef": t["coef"].cpu().numpy()}, host)
+    assert not got.differs(want), got.differs(want)
+    assert running, "fit_many_dev on S2 returned only when the delay on S had ended"
