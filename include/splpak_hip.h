@@ -744,8 +744,69 @@ int64_t splpak_fit_many_lds_bytes(int32_t ndim, const int32_t *nodes);
 /* host counters of the calling thread's last splpak_fit_many_* call (nothing is waited for): [0] workgroups launched, [1] LDS
  * bytes per workgroup, [2] launches of the call, [3] problems sent to the device, [4] problems refused with 105, [5] the
  * largest number of refinement steps over the problems, [6] device allocations (hipMalloc) the call made: 0 for a _dev call
- * whose scratch was large enough, [7] 0. */
+ * whose scratch was large enough, [7] 0.  After a splpak_fit_many_clip_* call the same slots ([5] over the LAST fits), and
+ * [7] the largest number of fits any problem ran. */
 int32_t splpak_debug_fit_many_stats(int64_t out8[8]);
+
+/* Sigma-clipped batch fits: the clipping loop splpak_fit_many_* -> splpak_residuals_many_* -> set the rejected weights to 0 ->
+ * splpak_fit_many_* ..., run to its end for every problem in ONE launch.  The workgroup that owns a problem fits it, forms its
+ * residuals, rejects, and fits again until a pass rejects nothing or maxpass passes have run; it then takes its next problem,
+ * so a problem that settles after one pass costs one pass, whatever its neighbours need.  The arguments are those of
+ * splpak_fit_many_* with, after xtrap, klo, khi (the thresholds below and above the fit, in units of the rms of the weighted
+ * residuals), maxpass, and wout: the weights the problem ended with, addressed by the global point index like wdata -- the mask
+ * is wout[i] == 0 where wdata[i] was not --; and, after info, clip (4 per problem, host, may be NULL).
+ * The rule, per problem, is part of the contract; T is the storage type and all arithmetic is in double, every operation
+ * rounded on its own (no contraction):
+ *   1 start    w_i = 1 for every point when wdata == NULL or the problem's first weight is negative, else (double) wdata[i];
+ *              wout[i] = (T) w_i.  The first-weight decision is taken once, from wdata, before any pass.
+ *   2 fit      (pass j = 0, 1, ..) coefficients, status and info are exactly what splpak_fit_many_* returns for the problem with
+ *              wout as its weights.  If that is 107: stop; the coefficients are 0 and wout stays as that fit saw it.
+ *   3 limit    if j == maxpass: stop.
+ *   4 resid    over the points with wout[i] != 0: cnt and S exactly as splpak_residuals_many_* defines them on the coefficients
+ *              as stored (rounded to T, the caller's node order): r = (double) y - f, t = w r, tt = t t; lane l of 64 adds tt
+ *              for p = l, l + 64, .. in ascending order, then the butterfly o = 32 .. 1.  v = S / cnt.
+ *   5 reject   a counted point is rejected where (t > 0 and tt > khi^2 v) or (t < 0 and tt > klo^2 v); khi^2 and klo^2 are
+ *              formed once in double (the _f32 entries widen klo and khi first).  No point rejected: stop.  Otherwise
+ *              wout[i] = (T) 0 for the rejected points and step 2 with j + 1.  Rejected points never return.
+ * The result is therefore bit for bit what that loop of the three entries gives with step 5 applied on the host (REAL32: where
+ * no decision hinges on the rounding of resid to float, which the entry does not do).  klo >= 1 and khi >= 1 are required
+ * (+inf switches a side off): the counted point of smallest tt then always survives, so a problem cannot clip itself empty; it
+ * can still end in 107 by becoming rank-deficient at xtrap = 0.  The coefficients returned always belong to the wout returned.
+ * maxpass = 0 is splpak_fit_many_* plus step 1.
+ *   clip + 4k  [0] residual passes that ran, [1] points rejected in total, [2] points counted by the last fit, [3] v of the
+ *              last residual pass (0 if none ran); all 0 for status 105.
+ *   info       what splpak_fit_many_* reports for the LAST fit of the problem, slot for slot; [7] the launch's device seconds
+ *              divided by the problems that ran.
+ * Shapes: exactly those of splpak_fit_many_* (splpak_fit_many_lds_bytes is the rule; the loop needs no LDS beyond the fit's).
+ * Status: the ladder of splpak_fit_many_* in its order, with, in the SPLPAK_E_BADARG group of the null data pointers: wout
+ * null, wout == wdata, maxpass < 0, klo or khi below 1 or NaN.  wout overlapping wdata in part is the caller's fault and is not
+ * detected.  A problem without points: 105, never sent to the device, coef and wout untouched.
+ * Determinism as splpak_fit_many_*: the bits of problem k depend on its own points, values, weights, the grid and (klo, khi,
+ * maxpass) alone: not on the batch, its position, the workgroup, or the host / _dev entry.  No atomics. */
+int32_t splpak_fit_many_clip_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xdata,
+                                 int32_t l1xdat, const double *ydata, const double *wdata /* may be NULL */, const double *xmin,
+                                 const double *xmax, const int32_t *nodes, double xtrap, double klo, double khi, int32_t maxpass,
+                                 double *wout, double *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
+                                 double *info /* 10 per problem, may be NULL */, double *clip /* 4 per problem, may be NULL */);
+/* REAL32 storage, arithmetic in double */
+int32_t splpak_fit_many_clip_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xdata,
+                                 int32_t l1xdat, const float *ydata, const float *wdata /* may be NULL */, const float *xmin,
+                                 const float *xmax, const int32_t *nodes, float xtrap, float klo, float khi, int32_t maxpass,
+                                 float *wout, float *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
+                                 double *info /* 10 per problem, may be NULL */, double *clip /* 4 per problem, may be NULL */);
+/* the same on resident data, like splpak_fit_many_dev_*: xdata, ydata, wdata, wout and coef are device arrays, the rest host
+ * arrays.  One launch; `stream` is synchronised once, for the statuses; no hipMalloc / hipFree once the calling thread's
+ * scratch holds the batch. */
+int32_t splpak_fit_many_clip_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xdata_dev,
+                                     int32_t l1xdat, const double *ydata_dev, const double *wdata_dev /* may be NULL */,
+                                     const double *xmin, const double *xmax, const int32_t *nodes, double xtrap, double klo, double khi,
+                                     int32_t maxpass, double *wout_dev, double *coef_dev, int64_t ldcoef, int32_t *status /* host */,
+                                     double *info /* host */, double *clip /* host */, void *stream);
+int32_t splpak_fit_many_clip_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xdata_dev,
+                                     int32_t l1xdat, const float *ydata_dev, const float *wdata_dev /* may be NULL */,
+                                     const float *xmin, const float *xmax, const int32_t *nodes, float xtrap, float klo, float khi,
+                                     int32_t maxpass, float *wout_dev, float *coef_dev, int64_t ldcoef, int32_t *status /* host */,
+                                     double *info /* host */, double *clip /* host */, void *stream);
 
 /* The evaluation side of splpak_fit_many_*: problem k's coefficients at problem k's own points, one launch whatever nbatch is
  * (a spline per spectrum resampled on its own abscissa).  splpak_eval_fields_* evaluates every set at ONE shared batch of points
@@ -792,7 +853,8 @@ int32_t splpak_eval_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *of
                                  const float *xmin, const float *xmax, const int32_t *nodes, float *out_dev, void *stream);
 
 /* The residual pass of a clipping loop on a batch of small fits (fit_many -> residuals_many -> set the rejected weights to 0 ->
- * fit_many): residuals at every problem's own points and four numbers per problem, in one launch.  Layouts as above, with
+ * fit_many; splpak_fit_many_clip_* above runs that whole loop in one launch, with S as defined here): residuals at every
+ * problem's own points and four numbers per problem, in one launch.  Layouts as above, with
  * xdata(l1xdat, *), ydata, wdata and resid addressed by the global index.  For point i, local index p = i - offsets[k], of
  * problem k:
  *   f_i      the double window sum splpak_eval_many_* forms for it (value pattern), before any rounding;

@@ -44,6 +44,7 @@ SYMBOLS = [
     "splpak_fit_grid_weighted_dev_f32", "splpak_debug_fit_grid_weighted_stage_f64", "splpak_debug_fit_grid_weighted_stats",
     "splpak_fit_many_f64", "splpak_fit_many_f32", "splpak_fit_many_dev_f64", "splpak_fit_many_dev_f32", "splpak_fit_many_lds_bytes",
     "splpak_debug_fit_many_stats",
+    "splpak_fit_many_clip_f64", "splpak_fit_many_clip_f32", "splpak_fit_many_clip_dev_f64", "splpak_fit_many_clip_dev_f32",
     "splpak_eval_many_f64", "splpak_eval_many_f32", "splpak_eval_many_dev_f64", "splpak_eval_many_dev_f32",
     "splpak_residuals_many_f64", "splpak_residuals_many_f32", "splpak_residuals_many_dev_f64", "splpak_residuals_many_dev_f32",
     "splpak_debug_eval_many_stats",
@@ -223,6 +224,15 @@ def lib() -> C.CDLL:
     L.splpak_fit_many_lds_bytes.argtypes = [i32, _ip]
     L.splpak_debug_fit_many_stats.restype = i32
     L.splpak_debug_fit_many_stats.argtypes = [_lp]
+    flt = C.c_float
+    L.splpak_fit_many_clip_f64.restype = i32
+    L.splpak_fit_many_clip_f64.argtypes = [i32, i32, _lp, _dp, i32, _dp, _dp, _dp, _dp, _ip, dbl, dbl, dbl, i32, _dp, _dp, i64, _ip, _dp, _dp]
+    L.splpak_fit_many_clip_f32.restype = i32
+    L.splpak_fit_many_clip_f32.argtypes = [i32, i32, _lp, _fp, i32, _fp, _fp, _fp, _fp, _ip, flt, flt, flt, i32, _fp, _fp, i64, _ip, _dp, _dp]
+    L.splpak_fit_many_clip_dev_f64.restype = i32
+    L.splpak_fit_many_clip_dev_f64.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _dp, _dp, _ip, dbl, dbl, dbl, i32, vp, vp, i64, _ip, _dp, _dp, vp]
+    L.splpak_fit_many_clip_dev_f32.restype = i32
+    L.splpak_fit_many_clip_dev_f32.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _fp, _fp, _ip, flt, flt, flt, i32, vp, vp, i64, _ip, _dp, _dp, vp]
     L.splpak_eval_many_f64.restype = i32
     L.splpak_eval_many_f64.argtypes = [i32, i32, _lp, _dp, i32, _ip, _dp, i64, _dp, _dp, _ip, _dp]
     L.splpak_eval_many_f32.restype = i32
@@ -820,6 +830,62 @@ def fit_many_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xt
     return rc, status, info
 
 
+def fit_many_clip(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, real32=False, ldcoef=None,
+                  coef=None, l1xdat=None, wout=None):
+    """Sigma-clipped batch fits in one launch (splpak_fit_many_clip_*): for every problem the loop fit_many -> residuals_many ->
+    reject where t = w r lies beyond khi (above) or klo (below) times the rms of the counted t -> fit_many, until a pass rejects
+    nothing or `maxpass` passes have run; bit for bit what that loop of the three entries gives.  Layouts as fit_many.
+    -> (coef, wout, ierror, status (nbatch), info (nbatch, 10) of the last fit, clip (nbatch, 4) = (residual passes, points
+    rejected, points counted by the last fit, S / cnt of the last pass)); wout (given, or zeros of ydata's length) holds the
+    weights every problem ended with: 0 where a point was rejected."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
+    ydata = np.ascontiguousarray(ydata, dtype=dt)
+    if wdata is not None:
+        wdata = np.ascontiguousarray(wdata, dtype=dt)
+    if l1xdat is None:
+        l1xdat = xdata.shape[1]
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
+    ldc = ncol if ldcoef is None else int(ldcoef)
+    if coef is None:
+        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
+    if wout is None:
+        wout = np.zeros(max(ydata.size, 1), dtype=dt)
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    clip = np.zeros((max(nbatch, 1), 4))
+    fn = lib().splpak_fit_many_clip_f32 if real32 else lib().splpak_fit_many_clip_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), float(xtrap), float(klo), float(khi), int(maxpass), _p(wout, rp), _p(coef, rp), ldc, _p(status, _ip),
+                   _p(info, _dp), _p(clip, _dp)))
+    return coef, wout, rc, status, info, clip
+
+
+def fit_many_clip_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, wout, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5,
+                      l1xdat=None, ldcoef=None, stream=0):
+    """fit_many_clip on torch device tensors: xdata, ydata, wdata (or None), coef and wout on the device, offsets on the host.
+    -> (ierror, status (nbatch), info (nbatch, 10), clip (nbatch, 4))."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nbatch = offsets.size - 1
+    real32 = str(xdata.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    if l1xdat is None:
+        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    clip = np.zeros((max(nbatch, 1), 4))
+    fn = lib().splpak_fit_many_clip_dev_f32 if real32 else lib().splpak_fit_many_clip_dev_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
+                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap), float(klo),
+                   float(khi), int(maxpass), wout.data_ptr(), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(status, _ip),
+                   _p(info, _dp), _p(clip, _dp), C.c_void_p(stream)))
+    return rc, status, info, clip
+
+
 def fit_many_lds_bytes(ndim, nodes) -> int:
     """LDS bytes a problem of this grid takes in fit_many (host only; splpak_fit_many_lds_bytes); raises for a shape the
     entry's ladder rejects."""
@@ -830,7 +896,8 @@ def fit_many_lds_bytes(ndim, nodes) -> int:
 def debug_fit_many_stats():
     """Host counters of this thread's last fit_many call: (workgroups launched, LDS bytes per workgroup, launches, problems sent
     to the device, problems refused with 105, the largest number of refinement steps, device allocations (hipMalloc) the call
-    made -- 0 for a fit_many_dev call whose per-thread scratch was large enough --, 0)."""
+    made -- 0 for a fit_many_dev call whose per-thread scratch was large enough --, 0).  After a fit_many_clip call the same
+    slots, the steps of the last fits, and in the last slot the largest number of fits any problem ran."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_fit_many_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)

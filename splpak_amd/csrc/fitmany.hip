@@ -1,28 +1,8 @@
 // Many small independent fits on one node grid: splpak_fit_many_* (include/splpak_hip.h).  One workgroup takes a problem
-// from its points to its coefficients; a batch is ONE launch whose workgroups stride over the problems.
-//
-// Phases of a problem (LDS map: fitmany.hpp), all on the workgroup's own LDS:
-//   1 assemble   the points are staged FITMANY_CHUNK at a time: a thread per point computes the window tables of basis.hpp,
-//                w, w y and the nearest-node address; then the OWNER of band row i (thread i mod 256) walks the staged points
-//                in index order and adds the entries of its row, its right-hand side and its histogram word.
-//   2 sparse     (xtrap != 0) the 0.75 rule per node, dcwght, and C^T C of the derivative-constraint rows into the band,
-//                row by row, from the row patterns of assemble_dev.hpp (what constraints.hip adds for the single fit).
-//   3 factor     right-looking Cholesky of the band in place, with the pivot test of the point fit (chol_device.hpp): a pivot
-//                that is not positive fails.  (The floor of the grid fit, ncol * eps * the largest diagonal entry, has no place
-//                here: a constraint row puts 1e13 on the diagonal beside the 1 of a node that only data rows reach.)
-//   4 solve      forward and backward substitution (1-D: one thread with the last three unknowns in registers; 2-D: wave 0,
-//                one lane per band entry of the row, summed by the fixed butterfly of wave_sum).
-//   5 refine     RefineRule of fitgriddev.hpp: the gradient A^T W (W y - W A x) - C^T C x is recomputed from the rows
-//                (points staged again, owners walk them in index order), solved, added.
-// Determinism: every sum has one owner and a fixed order -- the point order of the problem, the neighbour order of a node,
-// the lane tree of a reduction -- none of which depends on the batch, the position in it or the workgroup.  No atomics.
-#include "fitmany.hpp"
-#include "fitgriddev.hpp"
-#include "assemble_dev.hpp"
+// from its points to its coefficients (fitmanydev.hpp: fit_problem, its phases and its LDS); a batch is ONE launch whose
+// workgroups stride over the problems.
+#include "fitmanydev.hpp"
 #include "../../include/splpak_hip.h"
-
-#include <algorithm>
-#include <cmath>
 
 namespace splpak {
 
@@ -30,273 +10,7 @@ thread_local long long t_fit_many_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 namespace {
 
-struct Lds {
-    double *band, *rhs, *x, *rho, *dcw, *stage, *scal;
-    int *ws, *addr;
-    unsigned char *spf;
-};
-
-__device__ inline Lds carve(double *base, const FitManyShape &sh)
-{
-    Lds L;
-    L.band = base + sh.band;
-    L.rhs = base + sh.rhs;
-    L.x = base + sh.x;
-    L.rho = base + sh.rho;
-    L.dcw = base + sh.dcw;
-    L.stage = base + sh.stage;
-    L.scal = base + sh.scal;
-    L.ws = reinterpret_cast<int *>(base + sh.doubles);
-    L.addr = L.ws + FITMANY_CHUNK * sh.ndim;
-    L.spf = reinterpret_cast<unsigned char *>(L.addr + FITMANY_CHUNK);
-    return L;
-}
-
-// max that keeps a NaN
-__device__ inline double nanmax(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
-
-// sum / max of v over the NT threads of the workgroup in every thread: a fixed tree through `red` (the stage: 256 doubles at least)
-template <bool MAX, int NT>
-__device__ inline double block_reduce(double v, double *red)
-{
-    const int t = threadIdx.x;
-    __syncthreads();
-    red[t] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = MAX ? nanmax(red[t], red[t + s]) : red[t] + red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-template <int D>
-__device__ inline void node_of(const Grid &g, int i, int *in)
-{
-    if (D == 1) in[0] = i;
-    else { in[0] = i % g.nodes[0]; in[1] = i / g.nodes[0]; }
-}
-
-// A thread per staged point: window tables, w and w y (RES: the row's residual w y - w A x), histogram address.
-// A point of weight 0 gets window starts no row matches.
-template <int D, typename T, bool RES, int NT>
-__device__ inline void stage_chunk(const FitManyArgs &a, const Lds &L, const T *__restrict__ xd, const T *__restrict__ yd,
-                                   const T *__restrict__ wd, bool weighted, long long p0, int cnt, int &nrows, double &ssq)
-{
-    for (int t = threadIdx.x; t < FITMANY_CHUNK; t += NT) {
-        double *sb = L.stage + t * (4 * D + 2);
-        if (t >= cnt) {      // the padding of the owners' walk
-#pragma unroll
-            for (int d = 0; d < D; ++d) L.ws[t * D + d] = -1000000;
-            sb[4 * D] = 0.0;
-            L.addr[t] = -1;
-            continue;
-        }
-        const long long p = p0 + t;
-        const double w = weighted ? (double)wd[p] : 1.0;
-        if (w == 0.0) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) L.ws[t * D + d] = -1000000;
-            sb[4 * D] = 0.0;
-            sb[4 * D + 1] = 0.0;
-            L.addr[t] = -1;
-            continue;
-        }
-        double xr[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) xr[d] = (double)xd[p * a.l1xdat + d];
-        const double y = (double)yd[p];
-        int ws[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const double xv = (D == 2 && a.g.perm[d] == 1) ? xr[D - 1] : xr[0];
-            ws[d] = window_table(a.g, d, xv, 0, sb + 4 * d);
-            L.ws[t * D + d] = ws[d];
-        }
-        sb[4 * D] = w;
-        if (!RES) {
-            sb[4 * D + 1] = w * y;
-            L.addr[t] = a.xtrap != 0.0 ? nearest_node_address(a.g, xr) : -1;
-            ++nrows;
-        } else {
-            double acc = 0.0;
-            if (D == 1) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc += (w * sb[q]) * L.x[ws[0] + q];
-            } else {
-                const int n0 = a.g.nodes[0];
-                for (int q1 = 0; q1 < 4; ++q1)
-#pragma unroll
-                    for (int q0 = 0; q0 < 4; ++q0) acc += (w * (sb[q0] * sb[4 + q1])) * L.x[(ws[0] + q0) + (ws[D - 1] + q1) * n0];
-            }
-            const double e = w * y - acc;
-            sb[4 * D + 1] = e;
-            ssq += e * e;
-        }
-    }
-}
-
-// The owner of row i walks the staged points in order.  !RES: its band row, right-hand side and histogram word (thread 0 also
-// the total of the bumps); RES: its entry of the gradient.  The window starts and addresses of FITMANY_WALK points are read
-// together before any of them is looked at: a walk that asks for one point's words at a time waits a whole LDS round trip per
-// point, with only ncol of the 256 threads at work (the stage pads a chunk to a multiple of FITMANY_WALK with points no row meets).
-template <int D, bool RES, int NT>
-__device__ inline void owner_chunk(const FitManyArgs &a, const Lds &L, int cnt, double &tot)
-{
-    const int n0 = a.g.nodes[0], ld = a.sh.ld, ncol = a.sh.ncol;
-    const int cntw = (cnt + FITMANY_WALK - 1) / FITMANY_WALK * FITMANY_WALK;
-    for (int i = threadIdx.x; i < ncol; i += NT) {
-        int in[D];
-        node_of<D>(a.g, i, in);
-        double *row = L.band + (long long)i * ld;
-        double acc = RES ? L.rho[i] : L.rhs[i];
-        double h = RES ? 0.0 : L.dcw[i];
-        for (int pb = 0; pb < cntw; pb += FITMANY_WALK) {
-            int r0v[FITMANY_WALK], r1v[FITMANY_WALK], adv[FITMANY_WALK];
-#pragma unroll
-            for (int u = 0; u < FITMANY_WALK; ++u) {
-                r0v[u] = in[0] - L.ws[(pb + u) * D];
-                r1v[u] = D == 2 ? in[D - 1] - L.ws[(pb + u) * D + D - 1] : 0;
-                adv[u] = RES ? -1 : L.addr[pb + u];
-            }
-#pragma unroll
-            for (int u = 0; u < FITMANY_WALK; ++u) {
-                const double *sb = L.stage + (pb + u) * (4 * D + 2);
-                if (!RES) {
-                    if (adv[u] == i) h += sb[4 * D];
-                    if (i == 0 && adv[u] >= 0) tot += sb[4 * D];
-                }
-                const int r0 = r0v[u], r1 = r1v[u];
-                if ((unsigned)r0 > 3u || (unsigned)r1 > 3u) continue;
-                const double w = sb[4 * D];
-                const double ai = w * (D == 2 ? sb[r0] * sb[4 + r1] : sb[r0]);
-                acc += ai * sb[4 * D + 1];
-                if (!RES) {
-                    if (D == 1) {
-                        for (int q0 = 0; q0 <= r0; ++q0) row[r0 - q0] += ai * (w * sb[q0]);
-                    } else {
-                        for (int q1 = 0; q1 <= r1; ++q1) {
-                            const int q0end = q1 == r1 ? r0 : 3;
-                            for (int q0 = 0; q0 <= q0end; ++q0) row[(r0 - q0) + n0 * (r1 - q1)] += ai * (w * (sb[q0] * sb[4 + q1]));
-                        }
-                    }
-                }
-            }
-        }
-        if (RES) L.rho[i] = acc;
-        else { L.rhs[i] = acc; L.dcw[i] = h; }
-    }
-}
-
-// The derivative-constraint rows of the data-sparse nodes around row i, neighbours and rows in a fixed order.
-// !RES: band row i += (C^T C)(i, j <= i);  RES: rho[i] -= (C^T C x)_i, and ssq += (C x)^2 of the rows of node i itself.
-template <int D, bool RES, int NT>
-__device__ inline void constraint_rows(const FitManyArgs &a, const Lds &L, double &ssq)
-{
-    constexpr int NE = D == 1 ? 3 : 9;
-    const Grid &g = a.g;
-    const int ld = a.sh.ld, ncol = a.sh.ncol;
-    for (int i = threadIdx.x; i < ncol; i += NT) {
-        int in[D];
-        node_of<D>(g, i, in);
-        double *row = L.band + (long long)i * ld;
-        double acc = 0.0;
-        for (int ne = 0; ne < NE; ++ne) {
-            int nn[D], offi[D], t = ne, nl = 0;
-            bool ok = true;
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                const int o = t % 3 - 1;
-                t /= 3;
-                nn[d] = in[d] + o;
-                offi[d] = -o;
-                ok = ok && nn[d] >= 0 && nn[d] <= g.nodes[d] - 1;
-                nl += nn[d] * g.colstride[d];
-            }
-            if (!ok || !L.spf[nl]) continue;
-            const double dcwght = L.dcw[nl];
-            for (int idm = 0; idm < D; ++idm)
-                for (int jdm = idm; jdm < D; ++jdm) {
-                    int nder[D];
-                    const double rowwt = constraint_pattern<D>(g, nn, idm, jdm, dcwght, nder);
-                    const double ci = constraint_entry<D>(g, nullptr, nn, offi, nder, rowwt);
-                    if (!RES && ci == 0.0) continue;
-                    double dot = 0.0;
-                    for (int je = 0; je < NE; ++je) {
-                        int offj[D], tt = je, jl = 0;
-#pragma unroll
-                        for (int d = 0; d < D; ++d) {
-                            offj[d] = tt % 3 - 1;
-                            tt /= 3;
-                            jl += (nn[d] + offj[d]) * g.colstride[d];
-                        }
-                        const double cj = constraint_entry<D>(g, nullptr, nn, offj, nder, rowwt);      // 0 outside the grid
-                        if (cj == 0.0) continue;
-                        if (RES) dot += cj * L.x[jl];
-                        else if (jl <= i) row[i - jl] += ci * cj;
-                    }
-                    if (RES) {
-                        acc += ci * dot;
-                        if (nl == i) ssq += dot * dot;
-                    }
-                }
-        }
-        if (RES) L.rho[i] -= acc;
-    }
-}
-
-// v <- N^-1 v with the factor in the band; every thread of the workgroup calls it
-template <int D>
-__device__ inline void band_solve(const Lds &L, const FitManyShape &sh, double *v)
-{
-    const int n = sh.ncol, ld = sh.ld, hb = sh.hb;
-    __syncthreads();
-    if (D == 1) {
-        if (threadIdx.x == 0) {
-            double x1 = 0.0, x2 = 0.0, x3 = 0.0;
-            for (int i = 0; i < n; ++i) {
-                const double *r = L.band + (long long)i * 4;
-                const double xi = (((v[i] - r[1] * x1) - r[2] * x2) - r[3] * x3) / r[0];
-                v[i] = xi;
-                x3 = x2; x2 = x1; x1 = xi;
-            }
-            x1 = x2 = x3 = 0.0;      // x[i + 1], x[i + 2], x[i + 3]
-            for (int i = n - 1; i >= 0; --i) {
-                const double l1 = i + 1 < n ? L.band[(long long)(i + 1) * 4 + 1] : 0.0;
-                const double l2 = i + 2 < n ? L.band[(long long)(i + 2) * 4 + 2] : 0.0;
-                const double l3 = i + 3 < n ? L.band[(long long)(i + 3) * 4 + 3] : 0.0;
-                const double xi = (((v[i] - l1 * x1) - l2 * x2) - l3 * x3) / L.band[(long long)i * 4];
-                v[i] = xi;
-                x3 = x2; x2 = x1; x1 = xi;
-            }
-        }
-        __syncthreads();
-        return;
-    }
-    const int lane = threadIdx.x & 63;
-    for (int i = 0; i < n; ++i) {
-        if (threadIdx.x < 64) {
-            double s = 0.0;
-            for (int k = lane + 1; k <= hb; k += 64)
-                if (i - k >= 0) s += L.band[(long long)i * ld + k] * v[i - k];
-            s = wave_sum(s);
-            if (lane == 0) v[i] = (v[i] - s) / L.band[(long long)i * ld];
-        }
-        __syncthreads();
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        if (threadIdx.x < 64) {
-            double s = 0.0;
-            for (int k = lane + 1; k <= hb; k += 64)
-                if (i + k < n) s += L.band[(long long)(i + k) * ld + k] * v[i + k];
-            s = wave_sum(s);
-            if (lane == 0) v[i] = (v[i] - s) / L.band[(long long)i * ld];
-        }
-        __syncthreads();
-    }
-}
+using namespace fitmanydev;
 
 template <int D, typename T, int NT>
 __global__ void __launch_bounds__(NT)
@@ -304,159 +18,23 @@ fit_many_kernel(FitManyArgs a, const T *__restrict__ xd, const T *__restrict__ y
 {
     extern __shared__ double fit_many_lds[];
     const Lds L = carve(fit_many_lds, a.sh);
-    const Grid &g = a.g;
-    const int tid = threadIdx.x, n = a.sh.ncol, ld = a.sh.ld, hb = a.sh.hb;
-    const bool sparse_rule = a.xtrap != 0.0;
 
     for (int r = blockIdx.x; r < a.nrun; r += gridDim.x) {
         const int k = a.plist[r];
         const long long p0 = a.offsets[k] - a.base, np = a.offsets[k + 1] - a.offsets[k];
         const bool weighted = wd != nullptr && (double)wd[p0] >= 0.0;      // :581-588, :796
-        __syncthreads();
-        for (long long e = tid; e < (long long)n * ld; e += NT) L.band[e] = 0.0;
-        for (int i = tid; i < n; i += NT) { L.rhs[i] = 0.0; L.dcw[i] = 0.0; L.spf[i] = 0; }
-        __syncthreads();
-
-        // 1 assemble
-        int nrows = 0;
-        double tot = 0.0, unused = 0.0;
-        for (long long c0 = 0; c0 < np; c0 += FITMANY_CHUNK) {
-            const int cnt = (int)(np - c0 < FITMANY_CHUNK ? np - c0 : FITMANY_CHUNK);
-            stage_chunk<D, T, false, NT>(a, L, xd, yd, wd, weighted, p0 + c0, cnt, nrows, unused);
-            __syncthreads();
-            owner_chunk<D, false, NT>(a, L, cnt, tot);
-            __syncthreads();
-        }
-        const double rows = block_reduce<false, NT>((double)nrows, L.stage);
-
-        // 2 the data-sparse nodes and their constraint rows (:862-1046)
-        double crows = 0.0;
-        if (sparse_rule) {
-            if (tid == 0) L.scal[0] = tot;
-            __syncthreads();
-            const double totlwt = L.scal[0];
-            int nsparse = 0;
-            for (int i = tid; i < n; i += NT) {
-#pragma clang fp contract(off)
-                int in[D];
-                node_of<D>(g, i, in);
-                long long nrect = 1;
-                int refnode = 0;
-#pragma unroll
-                for (int d = 0; d < D; ++d) { nrect *= (g.nodes[d] - 1); refnode += in[d] * g.refstride[d]; }
-                double expect = totlwt / (double)nrect;                          // :910
-#pragma unroll
-                for (int d = 0; d < D; ++d)
-                    if (in[d] == 0 || in[d] == g.nodes[d] - 1) expect = 0.5 * expect;      // :928
-                const double have = L.dcw[refnode];
-                const bool sp = have < 0.75 * expect;                            // :696, :936
-                L.rho[i] = sp ? a.xtrap * (expect - have) : 0.0;                 // :938, :960
-                L.spf[i] = sp ? 1 : 0;
-                nsparse += sp ? 1 : 0;
-            }
-            __syncthreads();
-            for (int i = tid; i < n; i += NT) L.dcw[i] = L.rho[i];
-            __syncthreads();
-            constraint_rows<D, false, NT>(a, L, unused);
-            crows = block_reduce<false, NT>((double)nsparse, L.stage) * (double)(D * (D + 1) / 2);
-        }
-        __syncthreads();
-
-        // 3 factor
-        double minpiv = INFINITY;
-        bool ok = true;
-        for (int j = 0; j < n; ++j) {
-            const double piv = L.band[(long long)j * ld];
-            ok = piv > 0.0;                          // (false for a NaN)
-            if (!(minpiv <= piv)) minpiv = piv;
-            if (!ok) break;                          // the same in every thread
-            const double l = sqrt(piv);
-            const int m = hb < n - 1 - j ? hb : n - 1 - j;
-            for (int t = tid; t < m; t += NT) L.band[(long long)(j + 1 + t) * ld + (t + 1)] /= l;
-            __syncthreads();
-            if (tid == 0) L.band[(long long)j * ld] = l;
-            for (int e = tid; e < m * m; e += NT) {
-                const int ra = e / m + 1, rb = e % m + 1;      // rows j + ra >= j + rb
-                if (rb <= ra)
-                    L.band[(long long)(j + ra) * ld + (ra - rb)] -= L.band[(long long)(j + ra) * ld + ra] * L.band[(long long)(j + rb) * ld + rb];
-            }
-            __syncthreads();
-        }
-
-        // 4 solve, 5 refine
-        RefineRule rule;
-        double ssq = 0.0;
-        bool fail = !ok;
-        if (ok) {
-            for (int i = tid; i < n; i += NT) L.x[i] = L.rhs[i];
-            band_solve<D>(L, a.sh, L.x);
-            for (int it = 0; it < FITMANY_MAX_STEPS; ++it) {
-                for (int i = tid; i < n; i += NT) L.rho[i] = 0.0;
-                __syncthreads();
-                double ssqp = 0.0;
-                int nr = 0;
-                for (long long c0 = 0; c0 < np; c0 += FITMANY_CHUNK) {
-                    const int cnt = (int)(np - c0 < FITMANY_CHUNK ? np - c0 : FITMANY_CHUNK);
-                    stage_chunk<D, T, true, NT>(a, L, xd, yd, wd, weighted, p0 + c0, cnt, nr, ssqp);
-                    __syncthreads();
-                    owner_chunk<D, true, NT>(a, L, cnt, unused);
-                    __syncthreads();
-                }
-                if (sparse_rule) constraint_rows<D, true, NT>(a, L, ssqp);
-                ssq = block_reduce<false, NT>(ssqp, L.stage);
-                band_solve<D>(L, a.sh, L.rho);
-                double m0 = 0.0, m1 = 0.0;
-                for (int i = tid; i < n; i += NT) {
-                    const double dx = L.rho[i], xn = L.x[i] + dx;
-                    L.x[i] = xn;
-                    m0 = nanmax(m0, fabs(dx));
-                    m1 = nanmax(m1, fabs(xn));
-                }
-                double am[2];
-                am[0] = block_reduce<true, NT>(m0, L.stage);
-                am[1] = block_reduce<true, NT>(m1, L.stage);
-                if (rule.advance(it, am)) break;
-            }
-            fail = !rule.converged && !(rule.estimate() <= 1e-10);
-        }
-
         T *out = coef + (long long)(a.compact ? r : k) * a.ldcoef;
-        for (int i = tid; i < n; i += NT) {
-            int in[D], refnode = 0;
-            node_of<D>(g, i, in);
-#pragma unroll
-            for (int d = 0; d < D; ++d) refnode += in[d] * g.refstride[d];
-            out[refnode] = fail ? (T)0 : (T)L.x[i];
-        }
-        if (tid == 0) {
-            double *res = a.result + (long long)r * FM_RESULT;
-            res[FM_ROWS] = rows;
-            res[FM_CROWS] = crows;
-            res[FM_STEPS] = (double)rule.steps;
-            res[FM_LASTREL] = rule.last_rel;
-            res[FM_MINPIV] = minpiv;
-            res[FM_RESERR] = sqrt(ssq);
-            res[FM_STATUS] = fail ? 107.0 : 0.0;
-            res[FM_SPARE] = 0.0;
-        }
+        const FitOutcome o = fit_problem<D, T, NT, const T *__restrict__>(a, L, xd, yd, wd, weighted, p0, np, out);
+        if (threadIdx.x == 0) store_outcome(o, a.result + (long long)r * FM_RESULT);
     }
 }
-
-}  // namespace
-
-namespace {
 
 // one shape of the launch: as many workgroups as fit on the device at once, or one per problem if that is fewer
 template <int D, typename T, int NT>
 hipError_t launch_shape(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, int cus, hipStream_t st, unsigned *blocks)
 {
     const size_t lds = (size_t)a.sh.bytes;
-    int occ = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fit_many_kernel<D, T, NT>, NT, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    *blocks = (unsigned)std::max(1LL, std::min((long long)a.nrun, (long long)cus * occ));
+    *blocks = many_blocks(fit_many_kernel<D, T, NT>, NT, lds, a.nrun, cus);
     hipLaunchKernelGGL((fit_many_kernel<D, T, NT>), dim3(*blocks), dim3(NT), lds, st, a, xdata, ydata, wdata, coef);
     return hipGetLastError();
 }
@@ -466,37 +44,15 @@ hipError_t launch_shape(const FitManyArgs &a, const T *xdata, const T *ydata, co
 template <typename T>
 int fit_many_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, hipStream_t st, double *seconds)
 {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    SPLPAK_HIP_TRY(hipGetDevice(&dev), SPLPAK_E_NODEVICE);
-    SPLPAK_HIP_TRY(hipGetDeviceProperties(&prop, dev), SPLPAK_E_NODEVICE);
-    const int cus = prop.multiProcessorCount;
     // A grid of at most FITMANY_SMALL_NCOL nodes has no work for more than one wave (a thread per band row): its workgroups are
     // one wave, so that four times as many problems are in flight on a CU.  The shape depends on the grid alone.
     const bool small = a.sh.ncol <= FITMANY_SMALL_NCOL;
-    unsigned blocks = 1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    SPLPAK_HIP_TRY(hipEventCreate(&e0), SPLPAK_E_NODEVICE);
-    if (!hip_ok(hipEventCreate(&e1), "hipEventCreate")) { (void)hipEventDestroy(e0); return SPLPAK_E_NODEVICE; }
-    hipError_t rc = hipEventRecord(e0, st);
-    if (rc == hipSuccess) {
-        if (a.g.ndim == 1 && small) rc = launch_shape<1, T, 64>(a, xdata, ydata, wdata, coef, cus, st, &blocks);
-        else if (a.g.ndim == 1) rc = launch_shape<1, T, FITMANY_THREADS>(a, xdata, ydata, wdata, coef, cus, st, &blocks);
-        else if (small) rc = launch_shape<2, T, 64>(a, xdata, ydata, wdata, coef, cus, st, &blocks);
-        else rc = launch_shape<2, T, FITMANY_THREADS>(a, xdata, ydata, wdata, coef, cus, st, &blocks);
-    }
-    if (rc == hipSuccess) rc = hipEventRecord(e1, st);
-    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
-    float ms = 0.0f;
-    if (rc == hipSuccess) rc = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (!hip_ok(rc, "the launch of the batch of fits")) return SPLPAK_E_NODEVICE;
-    *seconds = (double)ms * 1e-3;
-    t_fit_many_stats[0] = blocks;
-    t_fit_many_stats[1] = (long long)a.sh.bytes;
-    t_fit_many_stats[2] = 1;
-    return 0;
+    return many_timed_launch(a.sh, st, seconds, [&](int cus, unsigned *blocks) {
+        if (a.g.ndim == 1 && small) return launch_shape<1, T, 64>(a, xdata, ydata, wdata, coef, cus, st, blocks);
+        if (a.g.ndim == 1) return launch_shape<1, T, FITMANY_THREADS>(a, xdata, ydata, wdata, coef, cus, st, blocks);
+        if (small) return launch_shape<2, T, 64>(a, xdata, ydata, wdata, coef, cus, st, blocks);
+        return launch_shape<2, T, FITMANY_THREADS>(a, xdata, ydata, wdata, coef, cus, st, blocks);
+    });
 }
 
 template int fit_many_launch<double>(const FitManyArgs &, const double *, const double *, const double *, double *, hipStream_t, double *);

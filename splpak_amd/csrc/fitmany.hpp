@@ -1,7 +1,9 @@
 // Many small independent fits on one node grid (include/splpak_hip.h: splpak_fit_many_*): what the entries (fitmanyapi.hip)
-// and the kernel with its driver (fitmany.hip) share.
+// and the kernel with its driver (fitmany.hip) share -- and the clipped fits (splpak_fit_many_clip_*: fitmanyclipapi.hip,
+// fitmanyclip.hip), which run the same fit inside a clipping loop.
 #pragma once
 #include "common.hpp"
+#include "../../include/splpak_hip.h"
 
 namespace splpak {
 
@@ -66,10 +68,67 @@ struct FitManyArgs {
     double *result;                // [nrun][FM_RESULT]
 };
 
+// The clipping loop around the fit (fitmanyclip.hip; the rule: include/splpak_hip.h, splpak_fit_many_clip_*).  Its result
+// block per problem: the FM_* slots of the LAST fit, FM_SPARE = the fits the problem ran, then the four clip numbers.
+enum { FMC_PASSES = FM_RESULT, FMC_REJECTED, FMC_COUNTED, FMC_V, FMC_RESULT };
+
+struct FitManyClipArgs {
+    FitManyArgs f;                 // f.result: [nrun][FMC_RESULT]
+    Grid gref;                     // the caller's order (build_grid without reorder): the residuals are evaluated in it
+    double klo2, khi2;             // klo^2, khi^2, formed once in double
+    int maxpass;
+};
+
 extern thread_local long long t_fit_many_stats[8];
 
 // The device part on device arrays: one launch.  0 or SPLPAK_E_*; *seconds = the launch's device time.
 template <typename T>
 int fit_many_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, hipStream_t st, double *seconds);
+// .. of the clipped fits: wout gets the weights each problem ended with (never the same array as wdata)
+template <typename T>
+int fit_many_clip_launch(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
+                         double *seconds);
+
+// workgroups of a batch launch: as many as fit on the device at once, or one per problem if that is fewer
+template <typename K>
+unsigned many_blocks(K kernel, int threads, size_t lds, int nrun, int cus)
+{
+    int occ = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds) != hipSuccess || occ < 1) {
+        (void)hipGetLastError();
+        occ = 1;
+    }
+    const long long most = (long long)cus * occ;
+    return (unsigned)(nrun < 1 ? 1 : ((long long)nrun < most ? (long long)nrun : most));
+}
+
+// The one launch of a batch between two events: launch(cus, &blocks) enqueues it on st; st is synchronised once.  Fills
+// t_fit_many_stats[0 .. 2] and *seconds (the launch's device time).  0 or SPLPAK_E_NODEVICE.
+template <typename F>
+int many_timed_launch(const FitManyShape &sh, hipStream_t st, double *seconds, F &&launch)
+{
+    int dev = 0;
+    hipDeviceProp_t prop;
+    SPLPAK_HIP_TRY(hipGetDevice(&dev), SPLPAK_E_NODEVICE);
+    SPLPAK_HIP_TRY(hipGetDeviceProperties(&prop, dev), SPLPAK_E_NODEVICE);
+    unsigned blocks = 1;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    SPLPAK_HIP_TRY(hipEventCreate(&e0), SPLPAK_E_NODEVICE);
+    if (!hip_ok(hipEventCreate(&e1), "hipEventCreate")) { (void)hipEventDestroy(e0); return SPLPAK_E_NODEVICE; }
+    hipError_t rc = hipEventRecord(e0, st);
+    if (rc == hipSuccess) rc = launch(prop.multiProcessorCount, &blocks);
+    if (rc == hipSuccess) rc = hipEventRecord(e1, st);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
+    float ms = 0.0f;
+    if (rc == hipSuccess) rc = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (!hip_ok(rc, "the launch of the batch of fits")) return SPLPAK_E_NODEVICE;
+    *seconds = (double)ms * 1e-3;
+    t_fit_many_stats[0] = blocks;
+    t_fit_many_stats[1] = (long long)sh.bytes;
+    t_fit_many_stats[2] = 1;
+    return 0;
+}
 
 }  // namespace splpak

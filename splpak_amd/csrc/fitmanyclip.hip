@@ -1,0 +1,193 @@
+// Sigma-clipped batch fits: splpak_fit_many_clip_* (include/splpak_hip.h states the rule).  The workgroup that owns a problem
+// runs the whole loop on it -- fit (fitmanydev.hpp: fit_problem), residuals, reject, fit again -- until a pass rejects nothing
+// or the pass limit is reached, and then moves on to its next problem: one launch for the batch, the launch shapes of
+// fit_many_kernel, no work queue, no atomics.  The bits are those of the loop splpak_fit_many_* -> splpak_residuals_many_* ->
+// the rule on the host -> splpak_fit_many_* ...:
+//   the fit        fit_problem on the weights in `wout`, exactly as fit_many_kernel runs it;
+//   the residuals  the factor tables and window_sum of evalcore.hpp on the grid in the CALLER's order (the fit's own grid is
+//                  reordered, which would change the order of the 2-D sum), the window rows read from LDS: after a fit L.rho is
+//                  free and gets (double)(T) x in the caller's node order, the very values eval_point loads from `coef`;
+//   S              all threads form t*t of a staged chunk of 128 points, then lane l of wave 0 adds entries l and l + 64 of
+//                  every chunk in ascending order -- p = l, l + 64, l + 128, .. as residuals_many_kernel's one wave adds them --
+//                  and the 64 lane sums go through wave_sum's butterfly: the same order whatever the workgroup size;
+//   the mask       written to `wout` in the reject step and read back by the next fit's stage_chunk: a global round trip inside
+//                  the workgroup, ordered by the barrier fit_problem opens with.  `wout` is therefore a plain pointer here and the
+//                  first-weight decision is taken once, from `wdata`, before the loop.
+// r is formed twice per pass (the reject step needs v first).
+#include "fitmanydev.hpp"
+#include "evalcore.hpp"
+
+namespace splpak {
+
+namespace {
+
+using namespace fitmanydev;
+
+// every operation of the rule below is rounded on its own (the fit and the factor tables come from the headers above)
+#pragma clang fp contract(off)
+
+// eval_point of evalmany.hip (value pattern) with the window rows read from cf in LDS: the coefficients as stored, widened
+template <int D, typename T>
+__device__ inline double eval_from_lds(const Grid &g, const T *__restrict__ x, const double *cf)
+{
+    double b[D][4];
+    int base = 0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        const double xd = (double)x[d];
+        const int ws = eval_table<true>(g, d, xd, 0, b[d]);
+        base += ws * g.colstride[d];
+    }
+    const int s1 = D > 1 ? g.colstride[1] : 0;
+    return window_sum<D>(b, [&](int k1, int, int, double (&c)[4]) {
+        const double *p = cf + base + k1 * s1;
+        c[0] = p[0]; c[1] = p[1]; c[2] = p[2]; c[3] = p[3];
+    });
+}
+
+// t = w r of point i (w != 0), each operation rounded on its own
+template <int D, typename T>
+__device__ inline double weighted_residual(const Grid &g, const T *__restrict__ xd, int l1xdat, const T *__restrict__ yd, long long i,
+                                           double w, const double *cf)
+{
+    const double f = eval_from_lds<D, T>(g, xd + i * l1xdat, cf);
+    const double r = (double)yd[i] - f;
+    return w * r;
+}
+
+// The waves per SIMD of fit_many_kernel are asked for (2-D: 2, 1-D: 4): the loop's state beside the fit's would otherwise take
+// 258 registers in the 2-D 256-thread shape (one workgroup per CU instead of two) and 158 in 1-D (3 waves per SIMD instead of
+// 4).  The compiler spills 2 registers (2-D) and 17 to 30 (1-D) for it; measured, 1-D: 10^5 problems in 64 ms instead of 80.
+template <int D, typename T, int NT>
+__global__ void __launch_bounds__(NT, D == 2 ? 2 : 4)
+fit_many_clip_kernel(FitManyClipArgs a, const T *__restrict__ xd, const T *__restrict__ yd, const T *__restrict__ wdata, T *wout,
+                     T *__restrict__ coef)
+{
+    extern __shared__ double fit_many_clip_lds[];
+    const Lds L = carve(fit_many_clip_lds, a.f.sh);
+    const Grid &g = a.f.g;
+    const int tid = threadIdx.x, n = a.f.sh.ncol, l1xdat = a.f.l1xdat;
+
+    for (int r = blockIdx.x; r < a.f.nrun; r += gridDim.x) {
+        const int k = a.f.plist[r];
+        const long long p0 = a.f.offsets[k] - a.f.base, np = a.f.offsets[k + 1] - a.f.offsets[k];
+        // the starting weights; the first-weight decision is taken here, from wdata, and never again
+        const bool weighted = wdata != nullptr && (double)wdata[p0] >= 0.0;
+        for (long long p = tid; p < np; p += NT) wout[p0 + p] = weighted ? wdata[p0 + p] : (T)1;
+        T *out = coef + (long long)(a.f.compact ? r : k) * a.f.ldcoef;
+
+        FitOutcome o;
+        int fits = 0, passes = 0;
+        double rejected = 0.0, v = 0.0;
+        for (int j = 0;; ++j) {
+            // (its opening barrier orders the stores to wout before its loads of them)
+            o = fit_problem<D, T, NT, const T *>(a.f, L, xd, yd, wout, true, p0, np, out);
+            ++fits;
+            if (o.fail || j == a.maxpass) break;
+
+            // the coefficients as stored: rounded to T, in the caller's node order
+            for (int i = tid; i < n; i += NT) {
+                int in[D], refnode = 0;
+                node_of<D>(g, i, in);
+#pragma unroll
+                for (int d = 0; d < D; ++d) refnode += in[d] * g.refstride[d];
+                L.rho[refnode] = (double)(T)L.x[i];
+            }
+            __syncthreads();
+
+            // cnt and S over the points of non-zero weight
+            double acc = 0.0;
+            int cnt = 0;
+            for (long long c0 = 0; c0 < np; c0 += FITMANY_CHUNK) {
+                const int cntc = (int)(np - c0 < FITMANY_CHUNK ? np - c0 : FITMANY_CHUNK);
+                for (int t = tid; t < FITMANY_CHUNK; t += NT) {
+                    double tt = 0.0;
+                    int counted = 0;
+                    if (t < cntc) {
+                        const long long i = p0 + c0 + t;
+                        const double w = (double)wout[i];
+                        if (w != 0.0) {      // a point of weight 0 is selected out, never multiplied
+                            const double tw = weighted_residual<D, T>(a.gref, xd, l1xdat, yd, i, w, L.rho);
+                            tt = tw * tw;
+                            counted = 1;
+                        }
+                    }
+                    L.stage[t] = tt;
+                    L.addr[t] = counted;
+                }
+                __syncthreads();
+                if (tid < 64) {
+                    for (int e = tid; e < FITMANY_CHUNK; e += 64)
+                        if (L.addr[e]) { acc = acc + L.stage[e]; ++cnt; }
+                }
+                __syncthreads();
+            }
+            if (tid < 64) {
+                const double s = wave_sum(acc);
+#pragma unroll
+                for (int q = 32; q > 0; q >>= 1) cnt += __shfl_xor(cnt, q, 64);
+                if (tid == 0) { L.scal[1] = s; L.scal[2] = (double)cnt; }
+            }
+            __syncthreads();
+            v = L.scal[1] / L.scal[2];
+            ++passes;
+
+            // reject; rejected points never return
+            const double hi = a.khi2 * v, lo = a.klo2 * v;
+            int nrej = 0;
+            for (long long p = tid; p < np; p += NT) {
+                const long long i = p0 + p;
+                const double w = (double)wout[i];
+                if (w == 0.0) continue;
+                const double tw = weighted_residual<D, T>(a.gref, xd, l1xdat, yd, i, w, L.rho);
+                const double tt = tw * tw;
+                if ((tw > 0.0 && tt > hi) || (tw < 0.0 && tt > lo)) { wout[i] = (T)0; ++nrej; }
+            }
+            const double rej = block_reduce<false, NT>((double)nrej, L.stage);
+            rejected += rej;
+            if (rej == 0.0) break;
+        }
+
+        if (tid == 0) {
+            double *res = a.f.result + (long long)r * FMC_RESULT;
+            store_outcome(o, res);
+            res[FM_SPARE] = (double)fits;
+            res[FMC_PASSES] = (double)passes;
+            res[FMC_REJECTED] = rejected;
+            res[FMC_COUNTED] = o.rows;
+            res[FMC_V] = v;
+        }
+    }
+}
+
+template <int D, typename T, int NT>
+hipError_t launch_shape(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, int cus, hipStream_t st,
+                        unsigned *blocks)
+{
+    const size_t lds = (size_t)a.f.sh.bytes;
+    *blocks = many_blocks(fit_many_clip_kernel<D, T, NT>, NT, lds, a.f.nrun, cus);
+    hipLaunchKernelGGL((fit_many_clip_kernel<D, T, NT>), dim3(*blocks), dim3(NT), lds, st, a, xdata, ydata, wdata, wout, coef);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+template <typename T>
+int fit_many_clip_launch(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
+                         double *seconds)
+{
+    const bool small = a.f.sh.ncol <= FITMANY_SMALL_NCOL;      // fit_many_launch's shapes
+    return many_timed_launch(a.f.sh, st, seconds, [&](int cus, unsigned *blocks) {
+        if (a.f.g.ndim == 1 && small) return launch_shape<1, T, 64>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
+        if (a.f.g.ndim == 1) return launch_shape<1, T, FITMANY_THREADS>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
+        if (small) return launch_shape<2, T, 64>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
+        return launch_shape<2, T, FITMANY_THREADS>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
+    });
+}
+
+template int fit_many_clip_launch<double>(const FitManyClipArgs &, const double *, const double *, const double *, double *, double *,
+                                          hipStream_t, double *);
+template int fit_many_clip_launch<float>(const FitManyClipArgs &, const float *, const float *, const float *, float *, float *, hipStream_t,
+                                         double *);
+
+}  // namespace splpak

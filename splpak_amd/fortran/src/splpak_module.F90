@@ -25,6 +25,7 @@
 !!    `evaluate_fields` evaluates several coefficient sets (what `refit` returns) at the same batch of points in one call,
 !!    `evaluate_each` evaluates the fits of `initialize_many`, each at its own points, and `residuals_each` forms their residuals
 !!    and per-problem sums, one launch each,
+!!    `initialize_many_clipped` runs the sigma-clipping loop of those two around `initialize_many` inside the one launch,
 !!    `evaluate_grid` evaluates every point of a tensor-product grid of points from its axes alone,
 !!    `evaluate_grid_derivatives` value + gradient (+ Hessian) on such a grid, one plane per entry, in one pass,
 !!    `integrate_grid` integrates the fit over the cells of a tensor grid (cell integrals, projections), `integrate` over one box,
@@ -76,7 +77,8 @@ module splpak_module
         procedure,public :: initialize_grid => splpak_fit_grid      !! fit of samples on a tensor-product grid of points (additive)
         procedure,public :: initialize_grid_weighted => splpak_fit_grid_weighted   !! the same with a weight per sample (additive)
         procedure,public :: initialize_many => splpak_fit_many      !! many small independent fits on one node grid in one launch (additive)
-        procedure,public :: evaluate_each => splpak_eval_each       !! the fits of initialize_many, each at its own points, in one launch (additive)
+        procedure,public :: initialize_many_clipped => splpak_fit_many_clipped !! .. with sigma clipping, the loop in the same launch (additive)
+        procedure,public :: evaluate_each => splpak_eval_each      !! the fits of initialize_many, each at its own points, in one launch (additive)
         procedure,public :: residuals_each => splpak_residuals_each !! their residuals and per-problem sums in one launch (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
@@ -218,6 +220,19 @@ module splpak_module
             type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, status, info
             real(wp),value :: xtrap
         end function c_fit_many
+#ifdef REAL32
+        integer(c_int32_t) function c_fit_many_clip(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,klo,khi, &
+                                                    maxpass,wout,coef,ldcoef,status,info,clip) bind(C,name='splpak_fit_many_clip_f32')
+#else
+        integer(c_int32_t) function c_fit_many_clip(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,klo,khi, &
+                                                    maxpass,wout,coef,ldcoef,status,info,clip) bind(C,name='splpak_fit_many_clip_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr, wp
+            integer(c_int32_t),value :: ndim, nbatch, l1xdat, maxpass
+            integer(c_int64_t),value :: ldcoef
+            type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, wout, coef, status, info, clip
+            real(wp),value :: xtrap, klo, khi
+        end function c_fit_many_clip
 #ifdef REAL32
         integer(c_int32_t) function c_eval_many(ndim,nbatch,offsets,xq,ldxq,nderiv,coef,ldcoef,xmin,xmax,nodes,out) &
                                                 bind(C,name='splpak_eval_many_f32')
@@ -789,6 +804,57 @@ module splpak_module
         end if
 #endif
     end subroutine splpak_fit_many
+
+    !> `initialize_many` with sigma clipping, the whole loop in one launch (include/splpak_hip.h, splpak_fit_many_clip_f64,
+    !! which states the rule): every problem is fitted, its points whose weighted residual lies more than `khi` (above) or
+    !! `klo` (below) times the rms of the counted weighted residuals from the fit are rejected, and it is fitted again, until a
+    !! pass rejects nothing or `maxpass` passes have run -- bit for bit the loop initialize_many -> residuals_each -> zero the
+    !! rejected weights -> initialize_many.  Arguments as `initialize_many`, and: klo, khi >= 1 (huge(1.0_wp) never rejects; an
+    !! infinity switches the side off); maxpass >= 0; wout(*) the weights every problem ended with, indexed like ydata (0 where a
+    !! point was rejected; never the array passed as wdata); the optional clip(4,nbatch) = [ residual passes, points rejected,
+    !! points counted by the last fit, S / cnt of the last pass ].  ierrors and ierror as `initialize_many`, -3 also for a bad
+    !! klo, khi or maxpass; refused with -4 under set_host, set_gpus(n > 1) and in the -DREAL128 build, exactly as it is.
+    subroutine splpak_fit_many_clipped(me,ndim,nbatch,offsets,xdata,l1xdat,ydata,xmin,xmax,nodes,xtrap,klo,khi,maxpass,wout, &
+                                       coef,ldcoef,ierrors,ierror,wdata,clip)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, l1xdat, ldcoef, maxpass
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: xdata(l1xdat,*), ydata(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(in) :: xtrap, klo, khi
+        real(wp),intent(inout),target :: wout(*)
+        real(wp),intent(inout),target :: coef(ldcoef,*)
+        integer,intent(out),target :: ierrors(*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: wdata(*)
+        real(c_double),intent(out),optional,target :: clip(4,*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pw, pc
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' initialize_many_clipped - not available in the -DREAL128 build')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' initialize_many_clipped - not available under set_host or set_gpus(n > 1)')
+            return
+        end if
+        pw = c_null_ptr
+        if (present(wdata)) pw = c_loc(wdata)
+        pc = c_null_ptr
+        if (present(clip)) pc = c_loc(clip)
+        rc = c_fit_many_clip(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
+                             c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, klo, khi, int(maxpass,c_int32_t), &
+                             c_loc(wout), c_loc(coef), int(ldcoef,c_int64_t), c_loc(ierrors), c_null_ptr, pc)
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'initialize_many_clipped')
+        end if
+#endif
+    end subroutine splpak_fit_many_clipped
 
     !> The fits of `initialize_many`, each at its own points, in one launch (include/splpak_hip.h, splpak_eval_many_f64): problem
     !! k owns the points offsets(k)+1 .. offsets(k+1) of x(ldx,*) and f, and has its coefficients in coef(:,k), where
