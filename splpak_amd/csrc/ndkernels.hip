@@ -4,6 +4,7 @@
 #include "chol_device.hpp"
 #include <hip/hip_ext.h>
 #include <cmath>
+#include <type_traits>
 
 namespace splpak {
 namespace nd {
@@ -137,6 +138,13 @@ nd_whoami_kernel(unsigned *__restrict__ map)
 // The trailing update of the multifrontal factorisation: one wave = one 64x64 item of C -= P_i P_j^T, in the
 // register-streaming form of bandchol.hip's syrk64_kernel (operands loaded in MFMA fragment shape ahead of
 // their use, 16 independent v_mfma_f64_16x16x4_f64 accumulators that start as the C tile; no LDS, no barriers).
+// The operands wait in a rotating queue of SD slots, one k-step each: the MFMAs of k-step s read slot s % SD, and the slot
+// is refilled with k-step s + SD right behind them.  That the queue stays in flight is a property of the ASSEMBLY, not
+// of this source: the wait in front of a k-step must be a counted vmcnt(N) that leaves the younger slots' loads pending
+// (vmcnt(27) ... vmcnt(24) at SD = 4: three refills of 8 loads).  It is, because the operands are addressed as global
+// memory, A is negated by the MFMA and the prologue is retired in front of the loop (below); until then every wait was
+// vmcnt(0) and the queue was drained once per SD k-steps (DESIGN 4a "The queue that never was").  After a change here,
+// read the loop in `make asm` again.
 // P and C have their own base pointers and leading dimensions: P is a block column of a front's panel (kb
 // consecutive 256-column blocks of it per pass: K = 256 kb, the C tile is read and written once per pass),
 // C the panel right of it or the front's Schur buffer.  SCHUR only names the instantiation: the Schur-buffer
@@ -242,11 +250,33 @@ nd_syrk_kernel(const SyrkJob *__restrict__ jobs, int njobs, int nitems, int marg
     const bool diag = ti == tj;
     if (SPLIT == 16 && diag && n0 < m0) return;      // a 16 x 16 tile above the diagonal
     const int lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
-    const double *__restrict__ pJ = j.P + (long long)(tj * 64 + 16 * m0 + l15) + (long long)q * j.ldp;
-    const double *__restrict__ pI = j.P + (long long)(ti * 64 + 16 * n0 + l15) + (long long)q * j.ldp;
+    // Operands and the C tile are addressed as GLOBAL memory.  The pointers come out of a job struct read from memory, so the
+    // compiler would otherwise use flat accesses, and with a flat access pending it cannot count its waits: every wait becomes
+    // vmcnt(0) lgkmcnt(0) and the operand queue below is drained at each of them (DESIGN 4a "The queue that never was").
+    // COUNTED = false keeps the earlier form (flat accesses, A negated as it is loaded, no stated wait) for the one instantiation
+    // whose registers do not take the new one without spilling more: <16, 2, true, 4, 1>, one launch per fit at 64^3.
+    constexpr bool COUNTED = !(SCHUR && SPLIT == 4);
+    typedef __attribute__((address_space(1))) double gdouble;
+    typedef __attribute__((address_space(1))) const int gint;
+    typedef typename std::conditional<COUNTED, __attribute__((address_space(1))) const double, const double>::type opnd_t;
+    typedef typename std::conditional<COUNTED, gdouble, double>::type ctile_t;
+    opnd_t *__restrict__ pJ = (opnd_t *)(j.P + (long long)(tj * 64 + 16 * m0 + l15) + (long long)q * j.ldp);
+    opnd_t *__restrict__ pI = (opnd_t *)(j.P + (long long)(ti * 64 + 16 * n0 + l15) + (long long)q * j.ldp);
     long long ldc;
-    double *__restrict__ C = schur_tile(j.C, j.ldc, ti, tj, ldc);
+    ctile_t *__restrict__ C = (ctile_t *)schur_tile(j.C, j.ldc, ti, tj, ldc);
     const long long ldp = j.ldp;
+    // SPLIT = 4 (80 loads in flight, 256 registers): the operand address is written as a wave-uniform base (tile, k-step) plus
+    // one 32-bit byte offset per lane (row in the tile, column in the k-step: 3 ldp + 15 doubles at the most) instead of a 64-bit
+    // pointer per lane and operand -- with that the panel form takes 212 registers and no scratch (it had 256 and 28 bytes)
+    constexpr bool SBASE = COUNTED && SPLIT == 4;
+    typedef __attribute__((address_space(1))) const char gcchar;
+    auto uniform = [](const double *p) {
+        const unsigned long long a = (unsigned long long)p;
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+        return (gcchar *)(((unsigned long long)hi << 32) | lo);
+    };
+    gcchar *bJ = uniform(j.P + (tj * 64 + 16 * m0)), *bI = uniform(j.P + (ti * 64 + 16 * n0));
+    const unsigned lob = ((unsigned)l15 + (unsigned)q * (unsigned)ldp) * 8u;
     d4_t acc[M][N];
 #pragma unroll
     for (int m = 0; m < M; ++m)
@@ -259,13 +289,26 @@ nd_syrk_kernel(const SyrkJob *__restrict__ jobs, int njobs, int nitems, int marg
     double qa[SD][M], qb[SD][N];
     auto fetch = [&](int slot, int step) {
         const long long off = (long long)(4 * step) * ldp;
+        if constexpr (SBASE) {
 #pragma unroll
-        for (int m = 0; m < M; ++m) qa[slot][m] = -pJ[off + 16 * m];
+            for (int m = 0; m < M; ++m) qa[slot][m] = *(opnd_t *)(bJ + (off + 16 * m) * 8 + lob);
 #pragma unroll
-        for (int n = 0; n < N; ++n) qb[slot][n] = pI[off + 16 * n];
+            for (int n = 0; n < N; ++n) qb[slot][n] = *(opnd_t *)(bI + (off + 16 * n) * 8 + lob);
+        } else {
+            // A is negated by the MFMA (neg:[1,0,0]), not here: a negation at the load is a VALU instruction the compiler sinks
+            // to the use, behind a wait for the load
+#pragma unroll
+            for (int m = 0; m < M; ++m) qa[slot][m] = COUNTED ? pJ[off + 16 * m] : -pJ[off + 16 * m];
+#pragma unroll
+            for (int n = 0; n < N; ++n) qb[slot][n] = pI[off + 16 * n];
+        }
     };
 #pragma unroll
     for (int d = 0; d < SD; ++d) fetch(d, d);
+    // the prologue is retired here, stated: the scheduler issues it in no particular order (slot 0 last), and a loop header that
+    // inherits its pending loads makes the wait in front of the first k-step -- which both paths into the loop share -- a
+    // vmcnt(0) for every trip.  With nothing pending at entry the waits inside the loop are counted.
+    if constexpr (COUNTED) __builtin_amdgcn_s_waitcnt(0x0f70);      // gfx9 encoding of vmcnt(0) alone
     constexpr int NSTEP = NBLK / 4;
     static_assert(NSTEP % SD == 0, "queue depth must divide the k-steps");
     const int last = j.kb * NSTEP - 1;               // last k-step of the pass
@@ -284,7 +327,7 @@ nd_syrk_kernel(const SyrkJob *__restrict__ jobs, int njobs, int nitems, int marg
                         // (a diagonal item stores its lower triangle only: the 6 of its 16 tiles above the diagonal are skipped --
                         // 1 % of the items of the root, 12 % of those of a front of 16 tile rows; wave-uniform branch)
                         if (SPLIT == 1 && skipu && m > n) continue;
-                        acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[d][m], qb[d][n], acc[m][n], 0, 0, 0);
+                        acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[d][m], qb[d][n], acc[m][n], 0, 0, COUNTED ? 1 : 0);      // blgp = 1: neg:[1,0,0], -a b
                     }
                 if (ks + d + SD < NSTEP) fetch(d, base + ks + d + SD);
                 else {                               // the first steps of the next block (clamped: re-reads in the last one)
@@ -304,8 +347,6 @@ nd_syrk_kernel(const SyrkJob *__restrict__ jobs, int njobs, int nitems, int marg
         // which the wave would sit through without issuing an MFMA.  The operand queue is dead here: its registers hold the
         // batch.  Targets are addressed as global memory (one 64-bit address per column, panel or Schur buffer), and an
         // entry without a target (padding: -1; above the diagonal of a diagonal item) is neither loaded nor stored.
-        typedef __attribute__((address_space(1))) double gdouble;
-        typedef __attribute__((address_space(1))) const int gint;
         constexpr int BM = M < 2 ? M : 2;            // m's per batch
         gint *pm = (gint *)j.pm;
         const int hl = j.h - 1;
@@ -1136,9 +1177,12 @@ void launch_syrk(NdState *s, const JobTable<SyrkJob> &tab, const Launch &l, hipS
         margin = 256 * s->nres;
     }
     const SyrkJob *jobs = tab.dev + l.first;
-    // SD = 4 k-steps of operand look-ahead, two waves per SIMD (244 registers): measured at 64^3 against the 16-deep
-    // queue / one wave per SIMD form the band's bulk update uses -- 257.6 against 282.2 ms per factorisation, because
-    // the queue is carried across the block loop of a K = 1024 pass and then has to live in registers (256 + 180)
+    // SD = 4 k-steps of operand look-ahead, two waves per SIMD (246 registers).  The measurement that chose it -- at 64^3
+    // against the 16-deep queue / one wave per SIMD form the band's bulk update uses, 257.6 against 282.2 ms per
+    // factorisation -- compared two forms that both drained their queue at every wait (vmcnt(0), see nd_syrk_kernel): it
+    // showed that two waves per SIMD hide a drained queue better than one, not what a queue of either depth is worth.
+    // What stands of it: a queue carried across the block loop of a K = 1024 pass has to live in registers, and 16 slots
+    // beside 128 accumulator registers leave room for one wave only.  SD has not been retuned with the queue working.
     // Launches of a few hundred items leave most SIMDs idle while one wave per item works through its MFMAs: they are split
     // over 4 / 16 waves per item (SPLIT above; same arithmetic order, bitwise the same result)
     // (beside a bulk update that fills every wave slot -- `pinned` -- the waves of this launch are placed as slots retire,
@@ -1151,7 +1195,8 @@ void launch_syrk(NdState *s, const JobTable<SyrkJob> &tab, const Launch &l, hipS
     if (s->xmode && schur && split == 1 && !wg4 && !queue) gx = (gx + 7u) / 8u * 8u;      // eight equal slices
     const dim3 grid(gx + (unsigned)margin);
     // operand look-ahead in k-steps: a split wave issues 1 (4) MFMA per step, so 4 steps cover 256 (1 024) cycles -- less than
-    // one memory round trip: 77 us per K = 256 launch of the root's look-ahead block.  32 (16) steps in flight instead.
+    // one memory round trip: 77 us per K = 256 launch of the root's look-ahead block.  32 (16) steps in flight instead
+    // (as measured then, fetched as a batch and drained once per 32 (16) steps; in flight throughout only with counted waits).
 #define ND_SD(SPL) ((SPL) == 16 ? 32 : ((SPL) == 4 ? 16 : 4))
 #define ND_SYRK_GO(SCH, SPL, WW)                                                                                               \
     do {                                                                                                                       \
