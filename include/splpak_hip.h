@@ -279,7 +279,8 @@ int32_t splpak_plan_get_option(const splpak_plan *plan, const char *name, char *
  * has no factorisation returns 107 with an explanatory message.
  * out6: [0] iterations of the last fit over all its solves, [1] solves, [2] iterations of the last solve, [3] its final
  * preconditioned residual (relative), [4] [5] the preconditioner's two moments (density of w^2, mean squared constraint weight);
- * zeros for a plan without the iteration. */
+ * zeros for a plan without the iteration, and after a fit that did not iterate (it went to the factorisation without an
+ * attempt, or failed before the solve): never the numbers of an earlier fit. */
 void splpak_plan_pcg_stats(const splpak_plan *plan, double *out6);
 
 /* Per-kernel accounting of the last splpak_plan_fit_dev call, measured with HIP

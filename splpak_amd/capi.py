@@ -1200,6 +1200,17 @@ class Plan:
     def hist_ptr(self):
         return self._L.splpak_plan_hist_dev(self._h)
 
+    def histogram(self):
+        """The histogram of the last fit (splpak_plan_hist_dev) copied to the host, (ncol,) as the device holds it; waits for
+        the device."""
+        import torch
+
+        class _Raw:
+            __cuda_array_interface__ = {"shape": (self.ncol,), "typestr": "<f8", "data": (int(self.hist_ptr()), False), "version": 2}
+
+        torch.cuda.synchronize()
+        return torch.as_tensor(_Raw(), device="cuda").cpu().numpy().copy()
+
     def normal_equations(self):
         """What the last fit assembled (diagnostics) -> (N, rhs): N the half stencil (ncol, (7^ndim + 1) // 2) in the caller's
         column numbering (include/splpak_hip.h splpak_debug_plan_normal_equations)."""

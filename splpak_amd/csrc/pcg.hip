@@ -719,6 +719,7 @@ size_t pcg_bytes(const PcgState *s) { return s ? s->bytes : 0; }
 double *pcg_scratch(PcgState *s, int which) { return which == 0 ? s->t1 : s->t2; }
 bool pcg_singular(const PcgState *s) { return s->singular; }
 void pcg_restart_counts(PcgState *s) { s->total_iters = 0; s->solves = 0; s->failed = false; }
+void pcg_forget_fit(PcgState *s) { pcg_restart_counts(s); s->last_iters = 0; s->last_rel = 0.0; s->rho = 0.0; s->lambda = 0.0; }
 bool pcg_boxes_from_rows(const PcgState *s) { return s->bj_have && s->ddiag != nullptr; }
 
 void pcg_stats(const PcgState *s, double *out6)

@@ -236,6 +236,7 @@ hipError_t pcg_prepare(splpak_plan *p, PcgState *s, double sumw2, bool smooth, b
 bool pcg_boxes_from_rows(const PcgState *s);      // the state can build its boxes from the rows (4-D: the fit may leave the normal equations unassembled)
 int pcg_solve(splpak_plan *p, PcgState *s, double *v, double tol, bool smooth, hipStream_t st);
 void pcg_restart_counts(PcgState *s);             // a refit solves again on the prepared preconditioner: the counters pcg_stats reports start over
+void pcg_forget_fit(PcgState *s);                 // a fit begins: pcg_stats reports zeros until -- unless -- this fit iterates (not the numbers of an earlier fit)
 // diagnostics (splpak_debug_plan_precondition / _pcg_tables / _pcg_diagonal): host vectors in the plan's INTERNAL column order.
 // part: 0 the whole preconditioner, 1 its separable part, 2 its boxes (zero when the fit dropped them)
 int pcg_debug_precondition(PcgState *s, int part, const double *r_host, double *z_host);

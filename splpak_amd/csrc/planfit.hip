@@ -686,6 +686,7 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
     p->pcg_prepared = false;
     p->geom_valid = false;
     p->factor_valid = false;
+    if (p->pcg) pcg_forget_fit(p->pcg);
     hipStream_t st = (hipStream_t)stream;
     if (lerr == 0 && w && ndata > 0) {
         // a negative first weight means "no weights" (:796, :890), as in the host entry points: one value read back
@@ -769,11 +770,15 @@ int32_t splpak_plan_fit_dev(splpak_plan *p, const double *x, int32_t l1xdat, con
         info[5] = std::chrono::duration<double>(a.t1 - t0).count();
     }
     // suprls error 33 "array has too few rows" (:1650-1654) -> 107 (:1053-1058)
-    if (rows_data + rows_cons < (double)g.ncol) return fit_fails_107(g, coef_dev, st, "fewer rows than coefficients (suprls 33)");
+    if (rows_data + rows_cons < (double)g.ncol) {
+        p->ne_valid = false;
+        return fit_fails_107(g, coef_dev, st, "fewer rows than coefficients (suprls 33)");
+    }
     a.rows_cons = rows_cons;
     a.sumw2 = hs[SC_COUNT + SC_SUMW2];
     a.rows_fit = rows_fit;
     const int rc = plan_solve_stage(p, st, coef_dev, info, a);
+    if (rc != 0) p->ne_valid = false;      // (a failed fit: splpak_debug_plan_normal_equations and _gram_shape refuse, as the header says)
     // what a refit continues from (splpak_plan_refit_dev)
     p->geom_valid = rc == 0 && p->fit_valid;
     p->fit_ndata = ndata;

@@ -779,6 +779,7 @@ def test_plan_reuse_gives_identical_fits():
         coefs.append(coef.cpu().numpy())
         assert relmax(coefs[-1], gold["coef"]) < COEF_TOL
     plan.close()
+    assert np.array_equal(coefs[1], coefs[0]) and np.array_equal(coefs[2], coefs[0])
 
 
 def test_large_grid_repeated_fit_properties():
