@@ -809,6 +809,90 @@ int32_t splpak_fit_many_clip_dev_f32(int32_t ndim, int32_t nbatch, const int64_t
                                      int32_t maxpass, float *wout_dev, float *coef_dev, int64_t ldcoef, int32_t *status /* host */,
                                      double *info /* host */, double *clip /* host */, void *stream);
 
+/* splpak_fit_many_* with the uncertainty of the fit: the entries of Z = (A^T W^2 A + C^T C)^-1, the inverse of the matrix the
+ * fit factors, that a prediction variance a(x)^T Z a(x) can touch.  The arguments are those of splpak_fit_many_* with cov, ldcov
+ * after ldcoef.
+ *   Meaning.  With w_i = 1 / sigma_i (wdata holds the reciprocal standard deviations) and no constraint rows (xtrap == 0, or no
+ *            data-sparse node: info[1] == 0), Z is the covariance of the coefficients.  With constraint rows, those rows act as
+ *            unit-variance pseudo-observations and Z never understates: the sandwich covariance is Z - Z C^T C Z, which is no
+ *            larger than Z (the sandwich form is not computed).  Where the weights are only relative, the caller scales Z by the
+ *            reduced chi-square info[8]^2 / (info[0] + info[1] - ncol), which it forms itself.
+ *   Layout.  Problem k's stencil is at cov + k*ldcov, ldcov >= splpak_fit_many_cov_len(ndim, nodes) = ncol * hst with
+ *            hst = (7^ndim + 1) / 2: 4 words per node in 1-D, 25 in 2-D.  Entry [i*hst + code] = Z[i, i + o], where i is the
+ *            coefficient's index in coef (the caller's node order, dimension 0 fastest), o_d in -3 .. 3 the offset of the column's
+ *            node in dimension d, and code = sum_d (o_d + 3) 7^d <= the centre (7^ndim - 1) / 2, i.e. the column is not after the
+ *            row: the lower half of the stencil, the diagonal in its last slot.  A cubic tensor B-spline row has a 4^ndim window,
+ *            so every pair of coefficients a window holds is in it.  A slot whose column i + o lies outside the grid holds 0;
+ *            words between the length and ldcov are not written.  (The internal band order, smaller dimension fastest, does not
+ *            show.)
+ *   Results. coef, status and info are bit for bit those of splpak_fit_many_* on the same problem.  A problem of status 107 gets
+ *            cov = 0 as it gets coef = 0; a problem of status 105 has its cov untouched.
+ * Algorithm.  The workgroup that fitted the problem still holds the band Cholesky factor L in LDS (refinement does not change
+ * it).  Takahashi's recurrence forms the entries of Z inside the band from it, column by column from the last one up, in place:
+ *   Z[j,i] = (delta_ij / L_ii - sum_{k=i+1..min(i+hb,ncol-1)} Z[j,k] L[k,i]) / L_ii,  j = i .. min(i+hb, ncol-1)
+ * (the divisions by L_ii are multiplications by its reciprocal, formed once per column).  No LDS beyond the fit's:
+ * splpak_fit_many_lds_bytes stays the rule, 12 x 12 nodes run.  1-D: one thread with the live 3 x 3 block in registers; 2-D: lane
+ * t of one wave owns Z[i+t,i] and walks k in ascending order, the diagonal's sum is a fixed butterfly over the lanes.  Every sum
+ * has one owner and a fixed order, there are no floating-point atomics: the bits of a problem's cov depend on its own points,
+ * values, weights and the grid alone (not on nbatch, its position, the workgroup or the host / _dev entry).
+ * Status: the ladder of splpak_fit_many_* in its order, with ldcov < the length on the 104 rung (beside ldcoef < ncol) and
+ * cov == NULL in the last SPLPAK_E_BADARG group (beside coef == NULL).  The LDS rule is unchanged.
+ * Not offered by the clipped entry: run splpak_fit_many_clip_* first and this entry with its wout as the weights. */
+int32_t splpak_fit_many_cov_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xdata,
+                                int32_t l1xdat, const double *ydata, const double *wdata /* may be NULL */, const double *xmin,
+                                const double *xmax, const int32_t *nodes, double xtrap, double *coef, int64_t ldcoef, double *cov,
+                                int64_t ldcov, int32_t *status /* nbatch, may be NULL */, double *info /* 10 per problem, may be NULL */);
+/* REAL32 storage, arithmetic in double, one rounding at the store of coef and of cov */
+int32_t splpak_fit_many_cov_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xdata, int32_t l1xdat,
+                                const float *ydata, const float *wdata /* may be NULL */, const float *xmin, const float *xmax,
+                                const int32_t *nodes, float xtrap, float *coef, int64_t ldcoef, float *cov, int64_t ldcov,
+                                int32_t *status /* nbatch, may be NULL */, double *info /* 10 per problem, may be NULL */);
+/* the same on resident data, like splpak_fit_many_dev_*: xdata, ydata, wdata, coef and cov are device arrays, the rest host
+ * arrays.  One launch; `stream` is synchronised once, for the statuses; no hipMalloc / hipFree once the calling thread's scratch
+ * holds the batch.  (The host entries stage cov, compact, through device memory of the call.) */
+int32_t splpak_fit_many_cov_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xdata_dev,
+                                    int32_t l1xdat, const double *ydata_dev, const double *wdata_dev /* may be NULL */,
+                                    const double *xmin, const double *xmax, const int32_t *nodes, double xtrap, double *coef_dev,
+                                    int64_t ldcoef, double *cov_dev, int64_t ldcov, int32_t *status /* host */, double *info /* host */,
+                                    void *stream);
+int32_t splpak_fit_many_cov_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xdata_dev,
+                                    int32_t l1xdat, const float *ydata_dev, const float *wdata_dev /* may be NULL */, const float *xmin,
+                                    const float *xmax, const int32_t *nodes, float xtrap, float *coef_dev, int64_t ldcoef,
+                                    float *cov_dev, int64_t ldcov, int32_t *status /* host */, double *info /* host */, void *stream);
+/* words of one problem's cov: ncol (7^ndim + 1) / 2.  Needs no device; SPLPAK_E_BADARG where splpak_fit_many_lds_bytes says it
+ * (nodes null, ndim other than 1 or 2, fewer than 4 nodes). */
+int64_t splpak_fit_many_cov_len(int32_t ndim, const int32_t *nodes);
+
+/* The prediction variance of a batch of small fits at each problem's own points, one launch: the arguments of splpak_eval_many_*
+ * with cov, ldcov (as splpak_fit_many_cov_* wrote them) in the place of coef, ldcoef.
+ *   out[i] = a^T Z a, where a is the window row splpak_eval_many_* forms for query i with the same nderiv -- the 4^ndim products
+ *   of its factor tables -- and Z comes from the stencil of the problem that owns i.  With a derivative pattern this is the
+ *   variance of that derivative.  It is the variance, not its root, and it is not clamped (rounding may leave a tiny negative
+ *   number where a row vanishes).  The _f32 entries read cov as float, widen it, sum in double and round once at the store.
+ * ndim is 1 or 2 and any grid is accepted (there is no LDS rule).
+ * Algorithm.  One thread per query over the concatenated list, the owner search of splpak_eval_many_*.  The window entries are
+ * numbered e = q0 + 4 q1 (dimension 0 fastest); the order of the double sum is part of the contract: acc = 0; for e = 0 ..
+ * 4^ndim - 1: r = (0.5 a_e) Z[p_e,p_e], then r = fma(a_f, Z[p_e,p_f], r) for f = 0 .. e-1 ascending, then acc = fma(a_e, r, acc);
+ * out = 2 acc.  Every symmetric pair is read once, from the row of the later node: 4 words per node in 1-D (10 in all), 136
+ * distinct words of 16 stencil rows in 2-D, from global memory.  The bits depend on the query and its problem's cov alone.
+ * Status: the ladder of splpak_eval_many_* in its order with three changes: ndim > 2 gives SPLPAK_E_UNSUPPORTED where ndim > 4
+ * does there; ldcov < splpak_fit_many_cov_len is where ldcoef < ncol is; cov null is where coef null is.  The zeroing of out on
+ * 101 / 102 / 103 and the clamped 104 are the same. */
+int32_t splpak_eval_many_var_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xq, int32_t ldxq,
+                                 const int32_t *nderiv /* may be NULL */, const double *cov, int64_t ldcov, const double *xmin,
+                                 const double *xmax, const int32_t *nodes, double *out);
+int32_t splpak_eval_many_var_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xq, int32_t ldxq,
+                                 const int32_t *nderiv /* may be NULL */, const float *cov, int64_t ldcov, const float *xmin,
+                                 const float *xmax, const int32_t *nodes, float *out);
+/* the same on resident data: xq, cov and out are device arrays.  Asynchronous on `stream` exactly as splpak_eval_many_dev_*: the
+ * call only enqueues, and the one thing it uploads is `offsets`, into the calling thread's scratch. */
+int32_t splpak_eval_many_var_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xq_dev, int32_t ldxq,
+                                     const int32_t *nderiv /* host, may be NULL */, const double *cov_dev, int64_t ldcov,
+                                     const double *xmin, const double *xmax, const int32_t *nodes, double *out_dev, void *stream);
+int32_t splpak_eval_many_var_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xq_dev, int32_t ldxq,
+                                     const int32_t *nderiv /* host, may be NULL */, const float *cov_dev, int64_t ldcov,
+                                     const float *xmin, const float *xmax, const int32_t *nodes, float *out_dev, void *stream);
+
 /* The evaluation side of splpak_fit_many_*: problem k's coefficients at problem k's own points, one launch whatever nbatch is
  * (a spline per spectrum resampled on its own abscissa).  splpak_eval_fields_* evaluates every set at ONE shared batch of points
  * and splpak_eval_* takes one set per call; a host loop of nbatch such calls is latency bound.  The layouts are those of
@@ -901,10 +985,10 @@ int32_t splpak_residuals_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_
                                       const float *coef_dev, int64_t ldcoef, const float *xmin, const float *xmax,
                                       const int32_t *nodes, float *resid_dev /* may be NULL */, double *stats_dev /* may be NULL */,
                                       void *stream);
-/* host counters of the calling thread's last splpak_eval_many_* or splpak_residuals_many_* call (nothing is waited for):
+/* host counters of the calling thread's last splpak_eval_many_*, splpak_eval_many_var_* or splpak_residuals_many_* call (nothing is waited for):
  * [0] workgroups launched, [1] launches of the call, [2] queries / points sent, [3] problems, [4] eval_many: the queries one
  * sweep of the launch covers (the launch strides over the rest); residuals_many: 0 (a sweep covers [0] problems, one wave
- * each), [5] 1 for eval_many, 2 for residuals_many, [6] [7] 0.  All 0 after a call its ladder refused. */
+ * each), [5] 1 for eval_many, 2 for residuals_many, 3 for eval_many_var (the other slots as eval_many), [6] [7] 0.  All 0 after a call its ladder refused. */
 int32_t splpak_debug_eval_many_stats(int64_t out8[8]);
 
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev

@@ -45,7 +45,9 @@ SYMBOLS = [
     "splpak_fit_many_f64", "splpak_fit_many_f32", "splpak_fit_many_dev_f64", "splpak_fit_many_dev_f32", "splpak_fit_many_lds_bytes",
     "splpak_debug_fit_many_stats",
     "splpak_fit_many_clip_f64", "splpak_fit_many_clip_f32", "splpak_fit_many_clip_dev_f64", "splpak_fit_many_clip_dev_f32",
+    "splpak_fit_many_cov_f64", "splpak_fit_many_cov_f32", "splpak_fit_many_cov_dev_f64", "splpak_fit_many_cov_dev_f32", "splpak_fit_many_cov_len",
     "splpak_eval_many_f64", "splpak_eval_many_f32", "splpak_eval_many_dev_f64", "splpak_eval_many_dev_f32",
+    "splpak_eval_many_var_f64", "splpak_eval_many_var_f32", "splpak_eval_many_var_dev_f64", "splpak_eval_many_var_dev_f32",
     "splpak_residuals_many_f64", "splpak_residuals_many_f32", "splpak_residuals_many_dev_f64", "splpak_residuals_many_dev_f32",
     "splpak_debug_eval_many_stats",
     "splpak_eval_fields_f64", "splpak_eval_fields_f32", "splpak_eval_fields_dev_f64", "splpak_eval_fields_dev_f32",
@@ -233,6 +235,24 @@ def lib() -> C.CDLL:
     L.splpak_fit_many_clip_dev_f64.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _dp, _dp, _ip, dbl, dbl, dbl, i32, vp, vp, i64, _ip, _dp, _dp, vp]
     L.splpak_fit_many_clip_dev_f32.restype = i32
     L.splpak_fit_many_clip_dev_f32.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _fp, _fp, _ip, flt, flt, flt, i32, vp, vp, i64, _ip, _dp, _dp, vp]
+    L.splpak_fit_many_cov_f64.restype = i32
+    L.splpak_fit_many_cov_f64.argtypes = [i32, i32, _lp, _dp, i32, _dp, _dp, _dp, _dp, _ip, dbl, _dp, i64, _dp, i64, _ip, _dp]
+    L.splpak_fit_many_cov_f32.restype = i32
+    L.splpak_fit_many_cov_f32.argtypes = [i32, i32, _lp, _fp, i32, _fp, _fp, _fp, _fp, _ip, flt, _fp, i64, _fp, i64, _ip, _dp]
+    L.splpak_fit_many_cov_dev_f64.restype = i32
+    L.splpak_fit_many_cov_dev_f64.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _dp, _dp, _ip, dbl, vp, i64, vp, i64, _ip, _dp, vp]
+    L.splpak_fit_many_cov_dev_f32.restype = i32
+    L.splpak_fit_many_cov_dev_f32.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _fp, _fp, _ip, flt, vp, i64, vp, i64, _ip, _dp, vp]
+    L.splpak_fit_many_cov_len.restype = i64
+    L.splpak_fit_many_cov_len.argtypes = [i32, _ip]
+    L.splpak_eval_many_var_f64.restype = i32
+    L.splpak_eval_many_var_f64.argtypes = [i32, i32, _lp, _dp, i32, _ip, _dp, i64, _dp, _dp, _ip, _dp]
+    L.splpak_eval_many_var_f32.restype = i32
+    L.splpak_eval_many_var_f32.argtypes = [i32, i32, _lp, _fp, i32, _ip, _fp, i64, _fp, _fp, _ip, _fp]
+    L.splpak_eval_many_var_dev_f64.restype = i32
+    L.splpak_eval_many_var_dev_f64.argtypes = [i32, i32, _lp, vp, i32, _ip, vp, i64, _dp, _dp, _ip, vp, vp]
+    L.splpak_eval_many_var_dev_f32.restype = i32
+    L.splpak_eval_many_var_dev_f32.argtypes = [i32, i32, _lp, vp, i32, _ip, vp, i64, _fp, _fp, _ip, vp, vp]
     L.splpak_eval_many_f64.restype = i32
     L.splpak_eval_many_f64.argtypes = [i32, i32, _lp, _dp, i32, _ip, _dp, i64, _dp, _dp, _ip, _dp]
     L.splpak_eval_many_f32.restype = i32
@@ -886,6 +906,69 @@ def fit_many_clip_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coe
     return rc, status, info, clip
 
 
+def fit_many_cov_len(ndim, nodes) -> int:
+    """Words of one problem's `cov` in fit_many_cov: ncol (7^ndim + 1) / 2 (host only; splpak_fit_many_cov_len); raises for a
+    shape fit_many_lds_bytes rejects."""
+    nodes = np.ascontiguousarray(np.atleast_1d(nodes), dtype=np.int32)
+    return int(_check(lib().splpak_fit_many_cov_len(int(ndim), _p(nodes, _ip))))
+
+
+def fit_many_cov(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, real32=False, ldcoef=None, coef=None, l1xdat=None,
+                 ldcov=None, cov=None):
+    """fit_many with the covariance of the coefficients (splpak_fit_many_cov_*): beside `coef`, row k of `cov` (nbatch, ldcov)
+    gets the half stencil of Z = (A^T W^2 A + C^T C)^-1 of problem k: cov[k, i * hst + code] = Z[i, i + o], hst = (7^ndim + 1) / 2,
+    code = sum_d (o_d + 3) 7^d <= the centre, 0 where i + o is outside the grid -- the layout of Port.normal_equations' N.
+    With wdata = 1 / sigma and no constraint rows Z is the covariance of the coefficients.
+    -> (coef, cov, ierror, status (nbatch), info (nbatch, 10)); a problem of status 105 keeps its rows of coef and cov, one of
+    status 107 has both zeroed."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
+    ydata = np.ascontiguousarray(ydata, dtype=dt)
+    if wdata is not None:
+        wdata = np.ascontiguousarray(wdata, dtype=dt)
+    if l1xdat is None:
+        l1xdat = xdata.shape[1]
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
+    ldc = ncol if ldcoef is None else int(ldcoef)
+    ldv = ncol * ((7 ** max(int(ndim), 0) + 1) // 2) if ldcov is None else int(ldcov)
+    if coef is None:
+        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
+    if cov is None:
+        cov = np.zeros((max(nbatch, 1), max(ldv, 1)), dtype=dt)
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    fn = lib().splpak_fit_many_cov_f32 if real32 else lib().splpak_fit_many_cov_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(cov, rp), ldv, _p(status, _ip), _p(info, _dp)))
+    return coef, cov, rc, status, info
+
+
+def fit_many_cov_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, cov, xtrap=0.0, l1xdat=None, ldcoef=None, ldcov=None,
+                     stream=0):
+    """fit_many_cov on torch device tensors: xdata, ydata, wdata (or None), coef and cov on the device, offsets on the host.
+    -> (ierror, status (nbatch), info (nbatch, 10))."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nbatch = offsets.size - 1
+    real32 = str(xdata.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    if l1xdat is None:
+        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
+    if ldcov is None:
+        ldcov = cov.stride(0) if cov.dim() > 1 else cov.shape[0]
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    fn = lib().splpak_fit_many_cov_dev_f32 if real32 else lib().splpak_fit_many_cov_dev_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
+                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap),
+                   coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), cov.data_ptr(), int(ldcov), _p(status, _ip), _p(info, _dp),
+                   C.c_void_p(stream)))
+    return rc, status, info
+
+
 def fit_many_lds_bytes(ndim, nodes) -> int:
     """LDS bytes a problem of this grid takes in fit_many (host only; splpak_fit_many_lds_bytes); raises for a shape the
     entry's ladder rejects."""
@@ -932,6 +1015,26 @@ def evaluate_many(ndim, offsets, xq, nderiv, coef, xmin, xmax, nodes, real32=Fal
     return out, rc
 
 
+def evaluate_many_var(ndim, offsets, xq, nderiv, cov, xmin, xmax, nodes, real32=False, ldxq=None, ldcov=None, out=None):
+    """The prediction variance of a batch of small fits at each problem's own points in one launch (splpak_eval_many_var_*):
+    out[i] = a^T Z a, a the window row evaluate_many forms for query i with the same nderiv (the variance of that derivative),
+    Z from row k of `cov` (nbatch, ldcov) as fit_many_cov wrote it.  The variance, not its root, not clamped.
+    -> (out, ierror), `out` written at the batch's indices only."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets, nbatch, xq = _many_host(offsets, xq, dt)
+    cov = np.ascontiguousarray(cov, dtype=dt)
+    ldv = int(ldcov) if ldcov is not None else (cov.shape[1] if cov.ndim > 1 else cov.size)
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    if out is None:
+        out = np.zeros(max(xq.shape[0], int(offsets[-1]) if offsets.size else 0, 1), dtype=dt)
+    rc = _check((lib().splpak_eval_many_var_f32 if real32 else lib().splpak_eval_many_var_f64)(
+        ndim, nbatch, _p(offsets, _lp), _p(xq, rp), int(xq.shape[1] if ldxq is None else ldxq), _p(nd, _ip), _p(cov, rp), ldv,
+        _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), _p(out, rp)))
+    return out, rc
+
+
 def residuals_many(ndim, offsets, xdata, ydata, wdata, coef, xmin, xmax, nodes, real32=False, l1xdat=None, ldcoef=None,
                    want_resid=True, want_stats=True):
     """Residuals and per-problem statistics of a batch of small fits in one launch (splpak_residuals_many_*): the pass between two
@@ -957,8 +1060,8 @@ def residuals_many(ndim, offsets, xdata, ydata, wdata, coef, xmin, xmax, nodes, 
 
 def debug_eval_many_stats():
     """Host counters of this thread's last evaluate_many / residuals_many call: (workgroups launched, launches, queries / points
-    sent, problems, queries one sweep of an evaluate_many launch covers (residuals_many: 0), 1 evaluate_many / 2 residuals_many,
-    0, 0)."""
+    sent, problems, queries one sweep of an evaluate_many launch covers (residuals_many: 0), 1 evaluate_many / 2 residuals_many /
+    3 evaluate_many_var, 0, 0)."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_eval_many_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)
@@ -1328,6 +1431,23 @@ def evaluate_many_dev(ndim, offsets, xq, nderiv, coef, xmin, xmax, nodes, out, l
         ldcoef = coef.stride(0) if coef.dim() > 1 else coef.shape[0]
     fn = lib().splpak_eval_many_dev_f32 if real32 else lib().splpak_eval_many_dev_f64
     return _check(fn(ndim, offsets.size - 1, _p(offsets, _lp), xq.data_ptr(), int(ldxq), _p(nd, _ip), coef.data_ptr(), int(ldcoef),
+                     _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
+
+
+def evaluate_many_var_dev(ndim, offsets, xq, nderiv, cov, xmin, xmax, nodes, out, ldxq=None, ldcov=None, stream=0):
+    """evaluate_many_var on torch device tensors (asynchronous on `stream`): xq (nqueries, ldxq), cov (nbatch, ldcov) and out on
+    the device, offsets and nderiv on the host.  float32 tensors take the REAL32 entry.  -> ierror."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    real32 = str(xq.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    nd = None if nderiv is None else np.ascontiguousarray(nderiv, dtype=np.int32)
+    if ldxq is None:
+        ldxq = xq.shape[1] if xq.dim() > 1 else 1
+    if ldcov is None:
+        ldcov = cov.stride(0) if cov.dim() > 1 else cov.shape[0]
+    fn = lib().splpak_eval_many_var_dev_f32 if real32 else lib().splpak_eval_many_var_dev_f64
+    return _check(fn(ndim, offsets.size - 1, _p(offsets, _lp), xq.data_ptr(), int(ldxq), _p(nd, _ip), cov.data_ptr(), int(ldcov),
                      _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), out.data_ptr(), C.c_void_p(stream)))
 
 

@@ -16,6 +16,10 @@
 //                 a problem are a fixed sequence of IEEE double operations on its own data: no atomics, no dependence on the
 //                 batch, the position or the launch shape.  A problem of very many points is walked by its one wave.
 //
+// eval_many_var  eval_many's sweep and owner search (wave_owners, lane_owner) with, per query, the quadratic form a^T Z a of its
+//                 window row in the half stencil of its problem's covariance (var_point): 4 (1-D) or 16 (2-D) stencil rows of
+//                 the problem's `cov`, 10 or 136 words of them, read from global memory once each.
+//
 // The coefficient sets are not staged in LDS: a 16-node set is 128 bytes and a wave's gathers stay in L1 / L2.
 //
 // The file also holds the per-thread device scratch of the batch entries' tables (manyhost.hpp).
@@ -68,6 +72,24 @@ __device__ inline double eval_point(const Grid &g, const T *__restrict__ x, cons
     });
 }
 
+// The owners of a wave's queries i0 .. i1 (consecutive, i0 in a scalar register): the wave looks up the owner of i0 once; where
+// i1 has the same owner every lane takes it, otherwise lane_owner searches between the two.
+struct WaveOwners {
+    int k0;
+    bool one_owner;
+};
+__device__ inline WaveOwners wave_owners(const long long *__restrict__ offsets, int nbatch, long long i0, long long i1)
+{
+    const int k0 = owner_of(offsets, i0, 0, nbatch);
+    return {k0, offsets[k0 + 1] > i1};
+}
+__device__ inline int lane_owner(const long long *__restrict__ offsets, int nbatch, const WaveOwners &w, long long i, long long i1)
+{
+    if (w.one_owner) return w.k0;
+    const int k1 = owner_of(offsets, i1, w.k0, nbatch);
+    return owner_of(offsets, i, w.k0, k1 + 1);
+}
+
 template <int D, typename T, bool VAL>
 __global__ void __launch_bounds__(EVALMANY_THREADS)
 eval_many_kernel(Grid g, int nbatch, const long long *__restrict__ offsets, long long first, long long nq, long long base,
@@ -78,18 +100,71 @@ eval_many_kernel(Grid g, int nbatch, const long long *__restrict__ offsets, long
     // jw: the wave's first query of this sweep, counted from `first`
     for (long long jw = wave_uniform((long long)blockIdx.x * EVALMANY_THREADS + (threadIdx.x - lane)); jw < nq; jw += stride) {
         const long long i0 = first + jw, i1 = first + (jw + 63 < nq ? jw + 63 : nq - 1);
-        const int k0 = owner_of(offsets, i0, 0, nbatch);
-        const bool one_owner = offsets[k0 + 1] > i1;
+        const WaveOwners w = wave_owners(offsets, nbatch, i0, i1);
         const long long j = jw + lane;
         if (j < nq) {
             const long long i = first + j;
-            int k = k0;
-            if (!one_owner) {
-                const int k1 = owner_of(offsets, i1, k0, nbatch);
-                k = owner_of(offsets, i, k0, k1 + 1);
-            }
+            const int k = lane_owner(offsets, nbatch, w, i, i1);
             const double sum = eval_point<D, T, VAL>(g, xq + (i - base) * ldxq, nd, coef + (long long)k * ldcoef);
             out[i - base] = (T)sum;
+        }
+    }
+}
+
+// a^T Z a for the window row a of the point at x (the products of the factors eval_point contracts the coefficients with) and
+// the half stencil cv of its problem: cv[p * HST + code] = Z(p, p + o) (include/splpak_hip.h, splpak_fit_many_cov_*).  The
+// window entries are numbered e = q0 (+ 4 q1), dimension 0 fastest, node p_e = base + q0 (+ q1 nodes[0]).  Order of the sum,
+// part of the contract: acc = 0; for e = 0 .. 4^D - 1: r = (0.5 a_e) Z(p_e, p_e), then r = fma(a_f, Z(p_e, p_f), r) for
+// f = 0 .. e - 1 ascending, then acc = fma(a_e, r, acc); the result is 2 acc.  Every symmetric pair is read once (p_f < p_e: the
+// lower triangle the stencil holds).
+template <int D, typename T, bool VAL>
+__device__ inline double var_point(const Grid &g, const T *__restrict__ x, const NDeriv &nd, const T *__restrict__ cv)
+{
+    constexpr int HST = D == 1 ? 4 : 25, NB = D == 1 ? 4 : 16;
+    double b[D][4];
+    int base = 0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        const int ws = eval_table<VAL>(g, d, (double)x[d], nd.v[d], b[d]);
+        base += ws * g.colstride[d];
+    }
+    const int s1 = D > 1 ? g.colstride[1] : 0;
+    double a[NB];
+#pragma unroll
+    for (int e = 0; e < NB; ++e) a[e] = D == 1 ? b[0][e] : b[0][e & 3] * b[D - 1][e >> 2];
+    double acc = 0.0;
+#pragma unroll
+    for (int e = 0; e < NB; ++e) {
+        const int e0 = e & 3, e1 = e >> 2;
+        const T *row = cv + (long long)(base + e0 + e1 * s1) * HST;
+        double r = (0.5 * a[e]) * (double)row[HST - 1];
+#pragma unroll
+        for (int f = 0; f < e; ++f) {
+            const int code = D == 1 ? (f - e) + 3 : ((f & 3) - e0 + 3) + 7 * ((f >> 2) - e1 + 3);
+            r = fma(a[f], (double)row[code], r);
+        }
+        acc = fma(a[e], r, acc);
+    }
+    return 2.0 * acc;
+}
+
+template <int D, typename T, bool VAL>
+__global__ void __launch_bounds__(EVALMANY_THREADS)
+eval_many_var_kernel(Grid g, int nbatch, const long long *__restrict__ offsets, long long first, long long nq, long long base,
+                     const T *__restrict__ xq, int ldxq, NDeriv nd, const T *__restrict__ cov, long long ldcov, T *__restrict__ out)
+{
+    // eval_many_kernel's sweep and owner search
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * EVALMANY_THREADS;
+    for (long long jw = wave_uniform((long long)blockIdx.x * EVALMANY_THREADS + (threadIdx.x - lane)); jw < nq; jw += stride) {
+        const long long i0 = first + jw, i1 = first + (jw + 63 < nq ? jw + 63 : nq - 1);
+        const WaveOwners w = wave_owners(offsets, nbatch, i0, i1);
+        const long long j = jw + lane;
+        if (j < nq) {
+            const long long i = first + j;
+            const int k = lane_owner(offsets, nbatch, w, i, i1);
+            const double v = var_point<D, T, VAL>(g, xq + (i - base) * ldxq, nd, cov + (long long)k * ldcov);
+            out[i - base] = (T)v;
         }
     }
 }
@@ -181,6 +256,32 @@ template hipError_t launch_eval_many<double>(const Grid &, int, const long long 
                                              const int *, const double *, long long, double *, hipStream_t);
 template hipError_t launch_eval_many<float>(const Grid &, int, const long long *, long long, long long, long long, const float *, int,
                                             const int *, const float *, long long, float *, hipStream_t);
+
+template <typename T>
+hipError_t launch_eval_many_var(const Grid &g, int nbatch, const long long *offsets_dev, long long first, long long nq, long long base,
+                                const T *xq, int ldxq, const int *nderiv, const T *cov, long long ldcov, T *out, hipStream_t st)
+{
+    if (nq <= 0) return hipSuccess;
+    const NDeriv nd = clamp_nderiv(nderiv, g.ndim);
+    long long blocks = (nq + EVALMANY_THREADS - 1) / EVALMANY_THREADS;
+    if (blocks > EVALMANY_BLOCKS) blocks = EVALMANY_BLOCKS;      // grid-stride the rest
+    const dim3 gr((unsigned)blocks), bl(EVALMANY_THREADS);
+    const bool plain = value_only(nd);
+    if (g.ndim == 1)
+        hipLaunchKernelGGL((plain ? eval_many_var_kernel<1, T, true> : eval_many_var_kernel<1, T, false>), gr, bl, 0, st, g, nbatch, offsets_dev,
+                           first, nq, base, xq, ldxq, nd, cov, ldcov, out);
+    else
+        hipLaunchKernelGGL((plain ? eval_many_var_kernel<2, T, true> : eval_many_var_kernel<2, T, false>), gr, bl, 0, st, g, nbatch, offsets_dev,
+                           first, nq, base, xq, ldxq, nd, cov, ldcov, out);
+    t_eval_many_stats[0] = blocks;
+    t_eval_many_stats[1] = 1;
+    t_eval_many_stats[4] = blocks * EVALMANY_THREADS;
+    return hipGetLastError();
+}
+template hipError_t launch_eval_many_var<double>(const Grid &, int, const long long *, long long, long long, long long, const double *, int,
+                                                 const int *, const double *, long long, double *, hipStream_t);
+template hipError_t launch_eval_many_var<float>(const Grid &, int, const long long *, long long, long long, long long, const float *, int,
+                                                const int *, const float *, long long, float *, hipStream_t);
 
 template <typename T>
 hipError_t launch_residuals_many(const Grid &g, int nbatch, const long long *offsets_dev, long long base, const T *xdata, int l1xdat,

@@ -22,6 +22,12 @@ template <typename T>
 hipError_t launch_eval_many(const Grid &g, int nbatch, const long long *offsets_dev, long long first, long long nq, long long base,
                             const T *xq, int ldxq, const int *nderiv, const T *coef, long long ldcoef, T *out, hipStream_t st);
 
+// out[i - base] = a^T Z a for every query i, a the window row launch_eval_many contracts with the coefficients, Z from the half
+// stencil of the owner's covariance at cov + k*ldcov (splpak_fit_many_cov_*); g.ndim is 1 or 2; one launch.
+template <typename T>
+hipError_t launch_eval_many_var(const Grid &g, int nbatch, const long long *offsets_dev, long long first, long long nq, long long base,
+                                const T *xq, int ldxq, const int *nderiv, const T *cov, long long ldcov, T *out, hipStream_t st);
+
 // resid[i - base] = (T)(y_i - f_i) and stats[4k .. 4k+3] = {points counted, sum (w r)^2, max |w r|, first local index of the max}
 // of every problem (either may be null); one launch, a wave per problem.
 template <typename T>

@@ -1,4 +1,5 @@
-// The entries of the batch evaluation at each problem's own points (include/splpak_hip.h): splpak_eval_many_* and
+// The entries of the batch evaluation at each problem's own points (include/splpak_hip.h): splpak_eval_many_*,
+// splpak_eval_many_var_* (the prediction variance from the stencils of splpak_fit_many_cov_*) and
 // splpak_residuals_many_* on host and device pointers, and their counters.  Each family has one ladder of checks, in the order
 // the header gives, all on the host; then evalmany.hip.  The _dev entries only enqueue: the one thing they upload is the
 // offsets, into the calling thread's scratch (manyhost.hpp: many_offsets_upload, held by a ScratchUse to the end of the
@@ -16,10 +17,10 @@ using namespace splpak;
 namespace {
 
 // The rungs both ladders open with.  True: the grid is built (rc = 0); false: rc is the status, and `zero` says whether it is
-// one of 101 / 102 / 103 (eval_many zeroes its results on these).
+// one of 101 / 102 / 103 (eval_many zeroes its results on these).  maxdim: the dimensions the family takes.
 template <typename T>
 bool many_open(int32_t ndim, int32_t nbatch, const int64_t *offsets, const T *xmin_t, const T *xmax_t, const int32_t *nodes, Grid &g, int &rc,
-               bool &zero)
+               bool &zero, int maxdim = MAXD)
 {
     zero = false;
     if (!offsets || !nodes || !xmin_t || !xmax_t) { set_error("null argument"); rc = SPLPAK_E_BADARG; return false; }
@@ -27,7 +28,11 @@ bool many_open(int32_t ndim, int32_t nbatch, const int64_t *offsets, const T *xm
     for (int k = 0; ok && k < nbatch; ++k) ok = offsets[k + 1] >= offsets[k];
     if (!ok) { set_error("nbatch < 1 or offsets that decrease"); rc = SPLPAK_E_BADARG; return false; }
     if (ndim < 1) { rc = 101; zero = true; return false; }
-    if (ndim > MAXD) { set_error("more than 4 dimensions are not supported"); rc = SPLPAK_E_UNSUPPORTED; return false; }
+    if (ndim > maxdim) {
+        set_error(maxdim == MAXD ? "more than 4 dimensions are not supported" : "splpak_eval_many_var_* takes 1-D and 2-D grids, as splpak_fit_many_cov_*");
+        rc = SPLPAK_E_UNSUPPORTED;
+        return false;
+    }
     double xmin[MAXD], xmax[MAXD];
     for (int d = 0; d < ndim; ++d) { xmin[d] = (double)xmin_t[d]; xmax[d] = (double)xmax_t[d]; }
     rc = build_grid(ndim, nodes, xmin, xmax, g, nullptr);      // 102, 103
@@ -92,6 +97,59 @@ int32_t eval_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *o
     if (e == hipSuccess && !cs.get(&od, (size_t)nq)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) e = many_offsets_upload(offsets, nbatch, nullptr, &off_dev);
     if (e == hipSuccess) e = launch_eval_many<T>(g, nbatch, off_dev, lo, nq, lo, xs, ldxq, nderiv, cd, ldcoef, od, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(res.data(), od, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        for (long long i = 0; i < nq; ++i) out[lo + i] = res[(size_t)i];
+    return many_status(e, what, rc);
+}
+
+// ---- splpak_eval_many_var_* ----
+// eval_many_entry with the half stencils of splpak_fit_many_cov_* in the place of the coefficients
+template <typename T>
+int32_t eval_many_var_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *offsets, const T *xq, int32_t ldxq, const int32_t *nderiv,
+                            const T *cov, int64_t ldcov, const T *xmin, const T *xmax, const int32_t *nodes, T *out, hipStream_t st)
+{
+    for (int j = 0; j < 8; ++j) t_eval_many_stats[j] = 0;
+    Grid g;
+    int rc = 0;
+    bool zero = false;
+    if (!many_open(ndim, nbatch, offsets, xmin, xmax, nodes, g, rc, zero, 2)) {
+        if (zero && out) {
+            const ManySpan sp = many_span(offsets, nbatch);
+            if (dev) { if (sp.n > 0) (void)hipMemsetAsync(out + sp.lo, 0, sizeof(T) * (size_t)sp.n, st); }
+            else for (long long i = 0; i < sp.n; ++i) out[sp.lo + i] = (T)0;
+        }
+        return rc;
+    }
+    const long long len = (long long)g.ncol * g.hstencil;
+    if (ldxq < ndim || ldcov < len) { set_error("ldxq smaller than ndim or ldcov smaller than splpak_fit_many_cov_len"); return SPLPAK_E_BADARG; }
+    if (nderiv)
+        for (int d = 0; d < ndim; ++d)
+            if (nderiv[d] < 0 || nderiv[d] > 2) rc = 104;      // reported; evaluated with the orders clamped
+    const ManySpan sp = many_span(offsets, nbatch);
+    const long long lo = sp.lo, nq = sp.n;
+    many_counters(3, nq, nbatch);
+    if (nq == 0) return rc;
+    if (!xq || !cov || !out) { set_error("null argument"); return SPLPAK_E_BADARG; }
+    if (int r = device_ready()) return r;
+
+    const char *what = "prediction variance of a batch of fits";
+    const ScratchUse<1> use{t_many_offsets, st};
+    const long long *off_dev = nullptr;
+    if (dev) {
+        hipError_t e = many_offsets_upload(offsets, nbatch, st, &off_dev);
+        if (e == hipSuccess) e = launch_eval_many_var<T>(g, nbatch, off_dev, lo, nq, 0, xq, ldxq, nderiv, cov, ldcov, out, st);
+        return many_status(e, what, rc);
+    }
+    std::vector<T> res((size_t)nq);
+    CallStage cs;
+    const T *xs = nullptr, *cd = nullptr;
+    T *od = nullptr;
+    hipError_t e = stage_span<T>(cs, sp, xq, ldxq, nullptr, nullptr, &xs, nullptr, nullptr);
+    if (e == hipSuccess) e = stage_copy(cs, cov, coef_block_len(nbatch, ldcov, len), &cd);
+    if (e == hipSuccess && !cs.get(&od, (size_t)nq)) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = many_offsets_upload(offsets, nbatch, nullptr, &off_dev);
+    if (e == hipSuccess) e = launch_eval_many_var<T>(g, nbatch, off_dev, lo, nq, lo, xs, ldxq, nderiv, cd, ldcov, od, nullptr);
     if (e == hipSuccess) e = hipMemcpy(res.data(), od, sizeof(T) * (size_t)nq, hipMemcpyDeviceToHost);
     if (e == hipSuccess)
         for (long long i = 0; i < nq; ++i) out[lo + i] = res[(size_t)i];
@@ -180,6 +238,34 @@ int32_t splpak_eval_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *of
 {
     return eval_many_entry<float>(true, ndim, nbatch, offsets, xq_dev, ldxq, nderiv, coef_dev, ldcoef, xmin, xmax, nodes, out_dev,
                                   (hipStream_t)stream);
+}
+
+int32_t splpak_eval_many_var_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xq, int32_t ldxq, const int32_t *nderiv,
+                                 const double *cov, int64_t ldcov, const double *xmin, const double *xmax, const int32_t *nodes, double *out)
+{
+    return eval_many_var_entry<double>(false, ndim, nbatch, offsets, xq, ldxq, nderiv, cov, ldcov, xmin, xmax, nodes, out, nullptr);
+}
+
+int32_t splpak_eval_many_var_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xq, int32_t ldxq, const int32_t *nderiv,
+                                 const float *cov, int64_t ldcov, const float *xmin, const float *xmax, const int32_t *nodes, float *out)
+{
+    return eval_many_var_entry<float>(false, ndim, nbatch, offsets, xq, ldxq, nderiv, cov, ldcov, xmin, xmax, nodes, out, nullptr);
+}
+
+int32_t splpak_eval_many_var_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xq_dev, int32_t ldxq,
+                                     const int32_t *nderiv, const double *cov_dev, int64_t ldcov, const double *xmin, const double *xmax,
+                                     const int32_t *nodes, double *out_dev, void *stream)
+{
+    return eval_many_var_entry<double>(true, ndim, nbatch, offsets, xq_dev, ldxq, nderiv, cov_dev, ldcov, xmin, xmax, nodes, out_dev,
+                                       (hipStream_t)stream);
+}
+
+int32_t splpak_eval_many_var_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xq_dev, int32_t ldxq,
+                                     const int32_t *nderiv, const float *cov_dev, int64_t ldcov, const float *xmin, const float *xmax,
+                                     const int32_t *nodes, float *out_dev, void *stream)
+{
+    return eval_many_var_entry<float>(true, ndim, nbatch, offsets, xq_dev, ldxq, nderiv, cov_dev, ldcov, xmin, xmax, nodes, out_dev,
+                                      (hipStream_t)stream);
 }
 
 int32_t splpak_residuals_many_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata, int32_t l1xdat, const double *ydata,

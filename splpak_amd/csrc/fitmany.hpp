@@ -1,6 +1,7 @@
 // Many small independent fits on one node grid (include/splpak_hip.h: splpak_fit_many_*): what the entries (fitmanyapi.hip)
 // and the kernel with its driver (fitmany.hip) share -- and the clipped fits (splpak_fit_many_clip_*: fitmanyclipapi.hip,
-// fitmanyclip.hip), which run the same fit inside a clipping loop.
+// fitmanyclip.hip), which run the same fit inside a clipping loop, and the fits with their covariance (splpak_fit_many_cov_*:
+// fitmanycovapi.hip, fitmanycov.hip), which turn the band factor into the band of its inverse afterwards.
 #pragma once
 #include "common.hpp"
 #include "../../include/splpak_hip.h"
@@ -51,6 +52,9 @@ inline FitManyShape fit_many_shape(int ndim, const int *nodes)
     return s;
 }
 
+// Words of one problem's `cov` (splpak_fit_many_cov_*): the half stencil of (7^ndim + 1) / 2 slots of every node
+inline long long fit_many_cov_len(int ndim, long long ncol) { return ncol * (ndim == 2 ? 25 : 4); }
+
 // What the kernel leaves per problem that ran (doubles).
 enum { FM_ROWS = 0, FM_CROWS, FM_STEPS, FM_LASTREL, FM_MINPIV, FM_RESERR, FM_STATUS, FM_SPARE, FM_RESULT };
 
@@ -84,6 +88,10 @@ extern thread_local long long t_fit_many_stats[8];
 // The device part on device arrays: one launch.  0 or SPLPAK_E_*; *seconds = the launch's device time.
 template <typename T>
 int fit_many_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, hipStream_t st, double *seconds);
+// .. with the selected inverse (fitmanycov.hip): cov of a problem at its coefficients' slot times ldcov, fit_many_cov_len words
+template <typename T>
+int fit_many_cov_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, T *cov, long long ldcov, hipStream_t st,
+                        double *seconds);
 // .. of the clipped fits: wout gets the weights each problem ended with (never the same array as wdata)
 template <typename T>
 int fit_many_clip_launch(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,

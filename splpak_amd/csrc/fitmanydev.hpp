@@ -15,6 +15,8 @@
 //                one lane per band entry of the row, summed by the fixed butterfly of wave_sum).
 //   5 refine     RefineRule of fitgriddev.hpp: the gradient A^T W (W y - W A x) - C^T C x is recomputed from the rows
 //                (points staged again, owners walk them in index order), solved, added.
+//   6 inverse    (splpak_fit_many_cov_* alone: fitmanycov.hip) the band of N^-1 from the factor, in place, and its half stencils
+//                to global memory (selected_inverse below).
 // Determinism: every sum has one owner and a fixed order -- the point order of the problem, the neighbour order of a node,
 // the lane tree of a reduction -- none of which depends on the batch, the position in it or the workgroup.  No atomics.
 #pragma once
@@ -316,12 +318,125 @@ __device__ inline void store_outcome(const FitOutcome &o, double *res)
     res[FM_SPARE] = 0.0;
 }
 
+// 6 selected inverse (splpak_fit_many_cov_*): the entries of Z = N^-1 inside the band, by Takahashi's recurrence on the factor,
+// in place.  The band holds L (L L^T = N) as band[i * ld + k] = L(i, i - k); column i of Z, for i = ncol-1 .. 0 and
+// m = min(hb, ncol-1-i), is
+//     Z(j, i) = -(sum_{k = i+1 .. i+m} Z(j, k) L(k, i)) / L(i, i)                      j = i+1 .. i+m
+//     Z(i, i) = (1 / L(i, i) - sum_{k = i+1 .. i+m} Z(k, i) L(k, i)) / L(i, i)
+// where Z(j, k) = Z(k, j) lies in a column after i, which the band already holds: Z(j, k) at band[max * ld + |j - k|].  Column i
+// of Z goes where column i of L was, so that column is copied out first: 1-D into registers, 2-D into the stage.
+//   1-D  (hb = 3) one thread, with the six entries of the live 3 x 3 block of Z in registers, as the 1-D solve keeps its last
+//        three unknowns: the chain per column is three fused sums, a division, a fourth sum and a division.
+//   2-D  lane t of wave 0 owns Z(i + t, i): it walks k in ascending order, then the diagonal's sum over the lanes is the fixed
+//        butterfly of wave_sum (hb + 1 <= 40 lanes are live: a grid inside the LDS rule has min(nodes) <= 12).  The stage is two
+//        buffers of 64: while column i is worked from one, the same lanes copy column i - 1 of L, which nobody writes before
+//        step i - 1, into the other -- one barrier per column.
+// Every sum has one owner and a fixed order; no atomics.  Then the half stencil of every node goes to global memory in the
+// caller's node order: cov[i * hst + code] = Z(i, i + o), code = sum_d (o_d + 3) 7^d <= centre, 0 where i + o is outside the
+// grid (include/splpak_hip.h) -- all zeros where the fit failed.  Every thread of the workgroup calls it, after fit_problem.
+template <int D, typename T, int NT>
+__device__ inline void selected_inverse(const FitManyArgs &a, const Lds &L, bool fail, T *__restrict__ cov)
+{
+    const Grid &g = a.g;
+    const int tid = threadIdx.x, n = a.sh.ncol, ld = a.sh.ld, hb = a.sh.hb;
+    constexpr int HST = D == 1 ? 4 : 25;
+    if (fail) {
+        for (long long e = tid; e < (long long)n * HST; e += NT) cov[e] = (T)0;
+        return;
+    }
+    __syncthreads();
+    if constexpr (D == 1) {
+        if (tid == 0) {
+            double *b = L.band;
+            // the block of Z on rows / columns i+1 .. i+3 (0 beyond the grid)
+            double z11 = 0.0, z21 = 0.0, z31 = 0.0, z22 = 0.0, z32 = 0.0, z33 = 0.0;
+            double l0 = b[(long long)(n - 1) * 4], l1 = 0.0, l2 = 0.0, l3 = 0.0;
+            for (int i = n - 1; i >= 0; --i) {
+                // column i - 1 of L, read before column i of Z is stored (the two never share a word)
+                double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+                if (i > 0) {
+                    m0 = b[(long long)(i - 1) * 4];
+                    m1 = b[(long long)i * 4 + 1];
+                    m2 = i + 1 < n ? b[(long long)(i + 1) * 4 + 2] : 0.0;
+                    m3 = i + 2 < n ? b[(long long)(i + 2) * 4 + 3] : 0.0;
+                }
+                const double r = 1.0 / l0;
+                const double y1 = -(((z11 * l1) + z21 * l2) + z31 * l3) * r;
+                const double y2 = -(((z21 * l1) + z22 * l2) + z32 * l3) * r;
+                const double y3 = -(((z31 * l1) + z32 * l2) + z33 * l3) * r;
+                const double y0 = (r - (((y1 * l1) + y2 * l2) + y3 * l3)) * r;
+                b[(long long)i * 4] = y0;
+                if (i + 1 < n) b[(long long)(i + 1) * 4 + 1] = y1;
+                if (i + 2 < n) b[(long long)(i + 2) * 4 + 2] = y2;
+                if (i + 3 < n) b[(long long)(i + 3) * 4 + 3] = y3;
+                z33 = z22; z32 = z21; z22 = z11;
+                z11 = y0; z21 = y1; z31 = y2;
+                l0 = m0; l1 = m1; l2 = m2; l3 = m3;
+            }
+        }
+    } else {
+        double *buf = L.stage;      // [2][64]
+        if (tid < 64) buf[((n - 1) & 1) * 64 + tid] = tid == 0 ? L.band[(long long)(n - 1) * ld] : 0.0;
+        __syncthreads();
+        for (int i = n - 1; i >= 0; --i) {
+            if (tid < 64) {
+                const int m = hb < n - 1 - i ? hb : n - 1 - i;
+                const double *lc = buf + (i & 1) * 64;      // lc[t] = L(i + t, i), t = 0 .. m
+                const double r = 1.0 / lc[0];
+                const int j = i + tid;
+                double z = 0.0;
+                if (tid >= 1 && tid <= m) {
+                    double s = 0.0;
+                    for (int k = i + 1; k <= i + m; ++k) {
+                        const int hi = k > j ? k : j, lo = k > j ? j : k;
+                        s += L.band[(long long)hi * ld + (hi - lo)] * lc[k - i];
+                    }
+                    z = -s * r;
+                }
+                // column i - 1 of L into the other buffer (rows i - 1 .. i - 1 + min(hb, n - i))
+                if (i > 0) {
+                    const int mp = hb < n - i ? hb : n - i;
+                    buf[((i - 1) & 1) * 64 + tid] = tid <= mp ? L.band[(long long)(i - 1 + tid) * ld + tid] : 0.0;
+                }
+                const double sd = wave_sum(tid >= 1 && tid <= m ? z * lc[tid] : 0.0);
+                if (tid == 0) L.band[(long long)i * ld] = (r - sd) * r;
+                else if (tid <= m) L.band[(long long)j * ld + tid] = z;
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+
+    for (long long e = tid; e < (long long)n * HST; e += NT) {
+        const int iref = (int)(e / HST), code = (int)(e % HST);
+        double v = 0.0;
+        if constexpr (D == 1) {
+            const int j = iref - 3 + code;     // o = code - 3 <= 0
+            if (j >= 0) v = L.band[(long long)iref * 4 + (iref - j)];
+        } else {
+            // the caller's node (r0, r1) and its neighbour at o; internal dimension d is the caller's perm[d]
+            const int n0r = g.ref_nodes[0], n1r = g.ref_nodes[1];
+            int ir[2], jr[2];
+            ir[0] = iref % n0r; ir[1] = iref / n0r;
+            jr[0] = ir[0] + code % 7 - 3; jr[1] = ir[1] + code / 7 - 3;
+            if (jr[0] >= 0 && jr[0] < n0r && jr[1] >= 0 && jr[1] < n1r) {
+                const int ii = ir[g.perm[0]] * g.colstride[0] + ir[g.perm[1]] * g.colstride[1];
+                const int jj = jr[g.perm[0]] * g.colstride[0] + jr[g.perm[1]] * g.colstride[1];
+                const int hi = ii > jj ? ii : jj, lo = ii > jj ? jj : ii;
+                v = L.band[(long long)hi * ld + (hi - lo)];
+            }
+        }
+        cov[e] = (T)v;
+    }
+}
+
 // One problem from its points (the np points from p0 on of xd, yd and, where `weighted`, wd) to its coefficients: zeroing,
 // phases 1 to 5, and the store of the ncol coefficients (0 where the fit failed) to `out` in the caller's node order.  Every
 // thread of the workgroup calls it; L.x keeps the coefficients in the internal order, and L.rho and the stage are free on return.
-template <int D, typename T, int NT, typename WP>
+// COV (off in fit_many_kernel and fit_many_clip_kernel, whose code it does not touch): phase 6 after the store, into `cov`.
+template <int D, typename T, int NT, typename WP, bool COV = false>
 __device__ inline FitOutcome fit_problem(const FitManyArgs &a, const Lds &L, const T *__restrict__ xd, const T *__restrict__ yd, WP wd,
-                                         bool weighted, long long p0, long long np, T *__restrict__ out)
+                                         bool weighted, long long p0, long long np, T *__restrict__ out, T *__restrict__ cov = nullptr)
 {
     const Grid &g = a.g;
     const int tid = threadIdx.x, n = a.sh.ncol, ld = a.sh.ld, hb = a.sh.hb;
@@ -441,6 +556,7 @@ __device__ inline FitOutcome fit_problem(const FitManyArgs &a, const Lds &L, con
         for (int d = 0; d < D; ++d) refnode += in[d] * g.refstride[d];
         out[refnode] = o.fail ? (T)0 : (T)L.x[i];
     }
+    if constexpr (COV) selected_inverse<D, T, NT>(a, L, o.fail, cov);
     return o;
 }
 

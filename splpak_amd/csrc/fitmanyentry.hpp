@@ -1,5 +1,5 @@
-// The host side of a batch of small fits, shared by splpak_fit_many_* (fitmanyapi.hip) and splpak_fit_many_clip_*
-// (fitmanyclipapi.hip): the ladder of checks in the order the header gives, all on the host; then the one launch
+// The host side of a batch of small fits, shared by splpak_fit_many_* (fitmanyapi.hip), splpak_fit_many_clip_*
+// (fitmanyclipapi.hip) and splpak_fit_many_cov_* (fitmanycovapi.hip; its cov is staged and scattered like coef): the ladder of checks in the order the header gives, all on the host; then the one launch
 // (fitmany.hip / fitmanyclip.hip) and the scatter of its results.  The tables of a call -- offsets, problem list, results --
 // live in the calling thread's scratch (manyhost.hpp), each held by a ScratchUse to the end of the call: a _dev call whose
 // scratch is large enough allocates and frees nothing.  The host entries stage the span of the batch's points and the compact
@@ -23,10 +23,17 @@ struct ClipSpec {
     double *clip;      // 4 per problem, may be null
 };
 
+// What the covariance entries (splpak_fit_many_cov_*) add (null: no covariance)
+template <typename T>
+struct CovSpec {
+    T *cov;
+    int64_t ldcov;
+};
+
 template <typename T>
 int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *offsets, const T *xdata, int32_t l1xdat, const T *ydata,
                        const T *wdata, const T *xmin_t, const T *xmax_t, const int32_t *nodes, double xtrap, T *coef, int64_t ldcoef,
-                       int32_t *status, double *info, hipStream_t st, const ClipSpec<T> *clip = nullptr)
+                       int32_t *status, double *info, hipStream_t st, const ClipSpec<T> *clip = nullptr, const CovSpec<T> *covs = nullptr)
 {
     for (int j = 0; j < 8; ++j) t_fit_many_stats[j] = 0;
     if (!offsets || !nodes || !xmin_t || !xmax_t) { set_error("null argument"); return SPLPAK_E_BADARG; }
@@ -43,11 +50,12 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
         if (rc == SPLPAK_E_UNSUPPORTED) set_error("more than 2^30 nodes is not supported");
         return rc;
     }
-    if (ldcoef < a.g.ncol) return 104;
-    bool ok = nbatch >= 1 && l1xdat >= ndim && xdata && ydata && coef;
+    const long long covlen = fit_many_cov_len(ndim, a.g.ncol);
+    if (ldcoef < a.g.ncol || (covs && covs->ldcov < covlen)) return 104;
+    bool ok = nbatch >= 1 && l1xdat >= ndim && xdata && ydata && coef && (!covs || covs->cov);
     for (int k = 0; ok && k < nbatch; ++k) ok = offsets[k + 1] >= offsets[k] && offsets[k + 1] - offsets[k] < (1LL << 31);
     if (!ok) {
-        set_error("nbatch < 1, offsets that decrease, a problem of 2^31 points or more, l1xdat < ndim or a null pointer");
+        set_error("nbatch < 1, offsets that decrease, a problem of 2^31 points or more, l1xdat < ndim or a null pointer");      // (cov included)
         return SPLPAK_E_BADARG;
     }
     if (clip && (!clip->wout || clip->wout == wdata || clip->maxpass < 0 || !(clip->klo >= 1.0) || !(clip->khi >= 1.0))) {
@@ -78,11 +86,12 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
         if (nrun == 0) return 105;
 
         if (int r = device_ready()) return r;
-        const char *what = clip ? "a batch of clipped fits" : "a batch of fits";
+        const char *what = clip ? "a batch of clipped fits" : (covs ? "a batch of fits with their covariance" : "a batch of fits");
         const ManySpan sp = many_span(offsets, nbatch);
         std::vector<double> res((size_t)nrun * nres);
         std::vector<T> ch(dev ? 0 : (size_t)nrun * (size_t)ncol);
         std::vector<T> wh(dev || !clip ? 0 : (size_t)sp.n);
+        std::vector<T> covh(dev || !covs ? 0 : (size_t)nrun * (size_t)covlen);
         const long long allocs_before = t_many_offsets.allocs + t_fit_many_tables.allocs;
         const ScratchUse<1> use_offsets{t_many_offsets, st};
         const ScratchUse<2> use_tables{t_fit_many_tables, st};
@@ -101,12 +110,15 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
         a.ldcoef = ldcoef;
         a.compact = 0;
         const T *xd = xdata, *yd = ydata, *wd = wdata;
-        T *cd = coef, *wo = clip ? clip->wout : nullptr;
+        T *cd = coef, *wo = clip ? clip->wout : nullptr, *cvd = covs ? covs->cov : nullptr;
+        long long ldcov = covs ? covs->ldcov : 0;
         if (!dev) {
             // the span of the batch's points alone, the coefficients of the problems that run back to back
             if (e == hipSuccess) e = stage_span(cs, sp, xdata, l1xdat, ydata, wdata, &xd, &yd, &wd);
             if (e == hipSuccess && !cs.get(&cd, ch.size())) e = hipErrorOutOfMemory;
             if (e == hipSuccess && clip && !cs.get(&wo, wh.size())) e = hipErrorOutOfMemory;
+            if (e == hipSuccess && covs && !cs.get(&cvd, covh.size())) e = hipErrorOutOfMemory;
+            ldcov = covlen;
             a.base = sp.lo;
             a.ldcoef = ncol;
             a.compact = 1;
@@ -121,12 +133,15 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
             ca.khi2 = clip->khi * clip->khi;
             ca.maxpass = clip->maxpass;
             if (int r = fit_many_clip_launch<T>(ca, xd, yd, wd, wo, cd, st, &seconds)) return r;
+        } else if (covs) {
+            if (int r = fit_many_cov_launch<T>(a, xd, yd, wd, cd, cvd, ldcov, st, &seconds)) return r;
         } else {
             if (int r = fit_many_launch<T>(a, xd, yd, wd, cd, st, &seconds)) return r;
         }
 
         e = hipMemcpyAsync(res.data(), a.result, sizeof(double) * res.size(), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && !dev) e = hipMemcpyAsync(ch.data(), cd, sizeof(T) * ch.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && !covh.empty()) e = hipMemcpyAsync(covh.data(), cvd, sizeof(T) * covh.size(), hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && !wh.empty()) e = hipMemcpyAsync(wh.data(), wo, sizeof(T) * wh.size(), hipMemcpyDeviceToHost, st);
         const hipError_t waited = hipStreamSynchronize(st);      // (also after a failed copy: the one before it may still write `res`)
         if (e == hipSuccess) e = waited;
@@ -156,6 +171,10 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
             if (!dev) {
                 T *ck = coef + (long long)k * ldcoef;
                 for (int i = 0; i < ncol; ++i) ck[i] = ch[(size_t)r * (size_t)ncol + (size_t)i];
+                if (covs) {
+                    T *vk = covs->cov + (long long)k * covs->ldcov;
+                    for (long long i = 0; i < covlen; ++i) vk[i] = covh[(size_t)r * (size_t)covlen + (size_t)i];
+                }
             }
         }
         // (every point of the span belongs to a problem that ran)

@@ -26,6 +26,8 @@
 !!    `evaluate_each` evaluates the fits of `initialize_many`, each at its own points, and `residuals_each` forms their residuals
 !!    and per-problem sums, one launch each,
 !!    `initialize_many_clipped` runs the sigma-clipping loop of those two around `initialize_many` inside the one launch,
+!!    `initialize_many_cov` is `initialize_many` with the covariance of the coefficients, and `variance_each` the prediction
+!!    variance of those fits, each at its own points,
 !!    `evaluate_grid` evaluates every point of a tensor-product grid of points from its axes alone,
 !!    `evaluate_grid_derivatives` value + gradient (+ Hessian) on such a grid, one plane per entry, in one pass,
 !!    `integrate_grid` integrates the fit over the cells of a tensor grid (cell integrals, projections), `integrate` over one box,
@@ -78,6 +80,8 @@ module splpak_module
         procedure,public :: initialize_grid_weighted => splpak_fit_grid_weighted   !! the same with a weight per sample (additive)
         procedure,public :: initialize_many => splpak_fit_many      !! many small independent fits on one node grid in one launch (additive)
         procedure,public :: initialize_many_clipped => splpak_fit_many_clipped !! .. with sigma clipping, the loop in the same launch (additive)
+        procedure,public :: initialize_many_cov => splpak_fit_many_cov !! initialize_many with the covariance of the coefficients (additive)
+        procedure,public :: variance_each => splpak_variance_each !! the prediction variance of those fits, each at its own points (additive)
         procedure,public :: evaluate_each => splpak_eval_each      !! the fits of initialize_many, each at its own points, in one launch (additive)
         procedure,public :: residuals_each => splpak_residuals_each !! their residuals and per-problem sums in one launch (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
@@ -245,6 +249,31 @@ module splpak_module
             integer(c_int64_t),value :: ldcoef
             type(c_ptr),value :: offsets, xq, nderiv, coef, xmin, xmax, nodes, out
         end function c_eval_many
+#ifdef REAL32
+        integer(c_int32_t) function c_fit_many_cov(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,coef,ldcoef, &
+                                                   cov,ldcov,status,info) bind(C,name='splpak_fit_many_cov_f32')
+#else
+        integer(c_int32_t) function c_fit_many_cov(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,coef,ldcoef, &
+                                                   cov,ldcov,status,info) bind(C,name='splpak_fit_many_cov_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr, wp
+            integer(c_int32_t),value :: ndim, nbatch, l1xdat
+            integer(c_int64_t),value :: ldcoef, ldcov
+            type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, cov, status, info
+            real(wp),value :: xtrap
+        end function c_fit_many_cov
+#ifdef REAL32
+        integer(c_int32_t) function c_eval_many_var(ndim,nbatch,offsets,xq,ldxq,nderiv,cov,ldcov,xmin,xmax,nodes,out) &
+                                                    bind(C,name='splpak_eval_many_var_f32')
+#else
+        integer(c_int32_t) function c_eval_many_var(ndim,nbatch,offsets,xq,ldxq,nderiv,cov,ldcov,xmin,xmax,nodes,out) &
+                                                    bind(C,name='splpak_eval_many_var_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr
+            integer(c_int32_t),value :: ndim, nbatch, ldxq
+            integer(c_int64_t),value :: ldcov
+            type(c_ptr),value :: offsets, xq, nderiv, cov, xmin, xmax, nodes, out
+        end function c_eval_many_var
 #ifdef REAL32
         integer(c_int32_t) function c_residuals_many(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,coef,ldcoef,xmin,xmax,nodes, &
                                                      resid,stats) bind(C,name='splpak_residuals_many_f32')
@@ -902,6 +931,95 @@ module splpak_module
         end select
 #endif
     end subroutine splpak_eval_each
+
+    !> `initialize_many` with the covariance of the coefficients (include/splpak_hip.h, splpak_fit_many_cov_f64): beside
+    !! coef(:,k), cov(:,k) (`ldcov` apart, ldcov >= ncol (7**ndim + 1) / 2) gets the half stencil of
+    !! Z = (A^T W^2 A + C^T C)^-1 of problem k: cov((i-1)*hst + code + 1, k) = Z(i, i + o) for node i (one based, dimension 1
+    !! fastest), hst = (7**ndim + 1) / 2 and code = sum_d (o_d + 3) 7**(d-1) <= hst - 1; 0 where i + o is outside the grid.
+    !! With wdata = 1 / sigma and no constraint rows Z is the covariance of the coefficients; with constraint rows it never
+    !! understates it.  coef, ierrors and ierror are exactly those of `initialize_many`; a problem of status 105 keeps its
+    !! cov, one of 107 has it zeroed; ldcov too small is 104.  Refused with -4 where `initialize_many` is.
+    subroutine splpak_fit_many_cov(me,ndim,nbatch,offsets,xdata,l1xdat,ydata,xmin,xmax,nodes,xtrap,coef,ldcoef,cov,ldcov, &
+                                   ierrors,ierror,wdata)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, l1xdat, ldcoef, ldcov
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: xdata(l1xdat,*), ydata(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(in) :: xtrap
+        real(wp),intent(inout),target :: coef(ldcoef,*)
+        real(wp),intent(inout),target :: cov(ldcov,*)
+        integer,intent(out),target :: ierrors(*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: wdata(*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pw
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' initialize_many_cov - not available in the -DREAL128 build')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' initialize_many_cov - not available under set_host or set_gpus(n > 1)')
+            return
+        end if
+        pw = c_null_ptr
+        if (present(wdata)) pw = c_loc(wdata)
+        rc = c_fit_many_cov(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
+                            c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, c_loc(coef), int(ldcoef,c_int64_t), &
+                            c_loc(cov), int(ldcov,c_int64_t), c_loc(ierrors), c_null_ptr)
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'initialize_many_cov')
+        end if
+#endif
+    end subroutine splpak_fit_many_cov
+
+    !> The prediction variance of the fits of `initialize_many_cov`, each at its own points, in one launch
+    !! (splpak_eval_many_var_f64): v(i) = a^T Z a, a the window row `evaluate_each` forms for x(:,i) with the same `nderiv` (the
+    !! variance of that derivative), Z from cov(:,k) of the problem k that owns i.  The variance, not its root, not clamped.
+    !! Arguments and ierror as `evaluate_each` with cov, ldcov in the place of coef, ldcoef; ndim is 1 or 2 (-4 otherwise).
+    subroutine splpak_variance_each(me,ndim,nbatch,offsets,x,ldx,cov,ldcov,xmin,xmax,nodes,v,ierror,nderiv)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, ldx, ldcov
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: x(ldx,*)
+        real(wp),intent(in),target :: cov(ldcov,*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(inout),target :: v(*)
+        integer,intent(out) :: ierror
+        integer,intent(in),optional,target :: nderiv(*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pd
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' variance_each - not available in the -DREAL128 build')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' variance_each - not available under set_host or set_gpus(n > 1)')
+            return
+        end if
+        pd = c_null_ptr
+        if (present(nderiv)) pd = c_loc(nderiv)
+        rc = c_eval_many_var(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(x), int(ldx,c_int32_t), pd, &
+                             c_loc(cov), int(ldcov,c_int64_t), c_loc(xmin), c_loc(xmax), c_loc(nodes), c_loc(v))
+        ierror = int(rc)
+        select case (ierror)
+        case (0)
+        case (101); call report(ierror,' splfe or splde - NDIM is less than 1')
+        case (102); call report(ierror,' splfe or splde - NODES(IDIM) is less than  4for some IDIM')
+        case (103); call report(ierror,' splfe or splde - XMIN(IDIM) = XMAX(IDIM) for some IDIM')
+        case (104); call report(ierror,' splde - NDERIV(IDIM) IS less than 0 or greater than 2 for some IDIM')
+        case default
+            if (ierror < 0) call report_library_failure(ierror,'variance_each')
+        end select
+#endif
+    end subroutine splpak_variance_each
 
     !> Residuals and per-problem sums of the fits of `initialize_many` in one launch (splpak_residuals_many_f64): the pass
     !! between two `initialize_many` calls of a clipping loop.  resid(i) = ydata(i) - f(i) for every point, a weight of 0
