@@ -745,7 +745,7 @@ int64_t splpak_fit_many_lds_bytes(int32_t ndim, const int32_t *nodes);
 /* host counters of the calling thread's last splpak_fit_many_* call (nothing is waited for): [0] workgroups launched, [1] LDS
  * bytes per workgroup, [2] launches of the call, [3] problems sent to the device, [4] problems refused with 105, [5] the
  * largest number of refinement steps over the problems, [6] device allocations (hipMalloc) the call made: 0 for a _dev call
- * whose scratch was large enough, [7] 0.  After a splpak_fit_many_clip_* call the same slots ([5] over the LAST fits), and
+ * whose scratch was large enough, [7] 0.  After a splpak_fit_many_clip_* or splpak_fit_many_clip_mad_* call the same slots ([5] over the LAST fits), and
  * [7] the largest number of fits any problem ran. */
 int32_t splpak_debug_fit_many_stats(int64_t out8[8]);
 
@@ -808,6 +808,72 @@ int32_t splpak_fit_many_clip_dev_f32(int32_t ndim, int32_t nbatch, const int64_t
                                      const float *xmin, const float *xmax, const int32_t *nodes, float xtrap, float klo, float khi,
                                      int32_t maxpass, float *wout_dev, float *coef_dev, int64_t ldcoef, int32_t *status /* host */,
                                      double *info /* host */, double *clip /* host */, void *stream);
+
+/* Robustly clipped batch fits: the clipping loop on a median / MAD scale, with rejected points allowed to return, run to its end
+ * for every problem in ONE launch.  The rms of splpak_fit_many_clip_* is inflated by the outliers it is meant to find, and a run
+ * of neighbouring outliers drags the first fit so that good points beside it are rejected in pass 0 and, there, lost for good.
+ * Here the centre is the median of the weighted residuals, the scale 1.4826 times their MAD, and with regrow != 0 every point
+ * is judged again in every pass against its ORIGINAL weight.  The arguments are those of splpak_fit_many_clip_* with regrow
+ * after maxpass and 6 numbers per problem in clip.
+ * The rule, per problem, is part of the contract; T is the storage type and all arithmetic is in double, every operation
+ * rounded on its own (no contraction):
+ *   1 start    as step 1 of splpak_fit_many_clip_*: w0_i = 1 for every point when wdata == NULL or the problem's first weight is
+ *              negative, else (double) wdata[i]; wout[i] = (T) w0_i.  The first-weight decision is taken once, from wdata.
+ *   2 fit      (pass j = 0, 1, ..) exactly splpak_fit_many_* with wout as the weights.  If that is 107: stop; the coefficients
+ *              are 0 and wout stays as that fit saw it.
+ *   3 limit    if j == maxpass: stop.
+ *   4 scale    t_i = w0_i r_i for every point with w0_i != 0, r_i = (double) y_i - f_i with f_i the window sum of
+ *              splpak_eval_many_* on the coefficients as stored (rounded to T, the caller's node order): what the rms rule uses.
+ *              med and MAD as splpak_mad_many_* defines them over the t_i of the points with wout[i] != 0.
+ *              s = 1.482602218505602 MAD.  If s == 0: stop (an exact fit of more than half the points rejects nothing).
+ *   5 decide   e_i = t_i - med; hi = khi s and lo = klo s, each formed once (the _f32 entries widen klo and khi first).  A
+ *              candidate is out where e_i > hi or -e_i > lo.  The candidates are the points with wout[i] != 0 when
+ *              regrow == 0, and the points with w0_i != 0 when regrow != 0.  wout[i] = (T) 0 for an out candidate, (T) w0_i for
+ *              every other candidate.  If no weight changed between zero and non-zero: stop.  Otherwise step 2 with j + 1.
+ * klo >= 1 and khi >= 1 are required (+inf switches a side off).  When s > 0 at least ceil(cnt / 2) of the counted points have
+ * |e| <= MAD < s, so a pass keeps at least half and a problem cannot clip itself empty; it can still end in 107 by becoming
+ * rank-deficient at xtrap = 0.  With regrow the loop may oscillate: maxpass bounds it, and clip[0] == maxpass shows it.  The
+ * coefficients returned always belong to the wout returned.  maxpass = 0 is splpak_fit_many_* plus step 1.
+ *   clip + 6k  [0] residual passes that ran, [1] points with w0 != 0 and wout == 0 at the end, [2] points counted by the last
+ *              fit, [3] s of the last residual pass, [4] its med, [5] points returned in total (a weight that went from zero back
+ *              to w0; 0 when regrow == 0); all 0 for status 105.
+ *   info       as splpak_fit_many_clip_*: the LAST fit of the problem.
+ * The result is bit for bit the loop splpak_fit_many_* -> splpak_residuals_many_* (resid) -> t = w0 resid on the host ->
+ * splpak_mad_many_* with wsel = the current weights -> steps 4 and 5 on the host -> splpak_fit_many_* ... (REAL32: where no
+ * decision hinges on the rounding of resid to float, which the entry does not do).
+ * Shapes: exactly those of splpak_fit_many_* (splpak_fit_many_lds_bytes is the rule; the selection counts in the stage area of
+ * the fit's LDS and needs no byte beyond it).  The t_i of a pass live in the calling thread's device scratch, a double per
+ * point of the batch.
+ * Status: the ladder of splpak_fit_many_clip_* in its order (wout null, wout == wdata, maxpass < 0, klo or khi below 1 or NaN
+ * in the SPLPAK_E_BADARG group of the null data pointers; any regrow is valid).  A problem without points: 105, never sent to the
+ * device, coef and wout untouched.
+ * Determinism as splpak_fit_many_*: the bits of problem k depend on its own points, values, weights, the grid and (klo, khi,
+ * maxpass, regrow) alone: not on the batch, its position, the workgroup, or the host / _dev entry.  No floating-point atomics
+ * (the selection's integer counts: splpak_mad_many_*). */
+int32_t splpak_fit_many_clip_mad_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *xdata,
+                                     int32_t l1xdat, const double *ydata, const double *wdata /* may be NULL */, const double *xmin,
+                                     const double *xmax, const int32_t *nodes, double xtrap, double klo, double khi, int32_t maxpass,
+                                     int32_t regrow, double *wout, double *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
+                                     double *info /* 10 per problem, may be NULL */, double *clip /* 6 per problem, may be NULL */);
+/* REAL32 storage, arithmetic in double */
+int32_t splpak_fit_many_clip_mad_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *xdata,
+                                     int32_t l1xdat, const float *ydata, const float *wdata /* may be NULL */, const float *xmin,
+                                     const float *xmax, const int32_t *nodes, float xtrap, float klo, float khi, int32_t maxpass,
+                                     int32_t regrow, float *wout, float *coef, int64_t ldcoef, int32_t *status /* nbatch, may be NULL */,
+                                     double *info /* 10 per problem, may be NULL */, double *clip /* 6 per problem, may be NULL */);
+/* the same on resident data, like splpak_fit_many_clip_dev_*: xdata, ydata, wdata, wout and coef are device arrays, the rest
+ * host arrays.  One launch; `stream` is synchronised once, for the statuses; no hipMalloc / hipFree once the calling thread's
+ * scratch holds the batch. */
+int32_t splpak_fit_many_clip_mad_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const double *xdata_dev,
+                                         int32_t l1xdat, const double *ydata_dev, const double *wdata_dev /* may be NULL */,
+                                         const double *xmin, const double *xmax, const int32_t *nodes, double xtrap, double klo,
+                                         double khi, int32_t maxpass, int32_t regrow, double *wout_dev, double *coef_dev, int64_t ldcoef,
+                                         int32_t *status /* host */, double *info /* host */, double *clip /* host */, void *stream);
+int32_t splpak_fit_many_clip_mad_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets /* host */, const float *xdata_dev,
+                                         int32_t l1xdat, const float *ydata_dev, const float *wdata_dev /* may be NULL */,
+                                         const float *xmin, const float *xmax, const int32_t *nodes, float xtrap, float klo, float khi,
+                                         int32_t maxpass, int32_t regrow, float *wout_dev, float *coef_dev, int64_t ldcoef,
+                                         int32_t *status /* host */, double *info /* host */, double *clip /* host */, void *stream);
 
 /* splpak_fit_many_* with the uncertainty of the fit: the entries of Z = (A^T W^2 A + C^T C)^-1, the inverse of the matrix the
  * fit factors, that a prediction variance a(x)^T Z a(x) can touch.  The arguments are those of splpak_fit_many_* with cov, ldcov
@@ -985,10 +1051,44 @@ int32_t splpak_residuals_many_dev_f32(int32_t ndim, int32_t nbatch, const int64_
                                       const float *coef_dev, int64_t ldcoef, const float *xmin, const float *xmax,
                                       const int32_t *nodes, float *resid_dev /* may be NULL */, double *stats_dev /* may be NULL */,
                                       void *stream);
-/* host counters of the calling thread's last splpak_eval_many_*, splpak_eval_many_var_* or splpak_residuals_many_* call (nothing is waited for):
+/* Robust batch clipping, the selection: the median and the MAD (median of the absolute deviations from the median) of every
+ * problem's segment of `values`, in one launch.  values is addressed by the global point index (problem k owns
+ * offsets[k] .. offsets[k+1]-1), wsel likewise and may be NULL: a point is counted where wsel[i] != 0, every point when wsel is
+ * NULL.  A value under a zero of wsel is never read as a number and may be NaN.  Definitions, all in double, part of the
+ * contract:
+ *   key      k_i = (double) values[i] + 0.0, so -0 counts as +0;
+ *   sort     the cnt counted keys ascending into s[0 .. cnt);
+ *   med      s[(cnt-1)/2] for odd cnt, else 0.5 (s[cnt/2 - 1] + s[cnt/2]): one addition, one multiplication, each rounded on its
+ *            own -- the bits of numpy.median;
+ *   MAD      d_i = |k_i - med| (one rounded subtraction), and the same median over the d_i;
+ *   stats + 4k   [0] cnt, [1] med, [2] MAD, [3] 0; all 0 when nothing is counted.
+ * A NaN among the counted values gives unspecified med and MAD.
+ * Determinism: med and MAD are exact order statistics.  Their bits depend on the multiset of the problem's counted values alone:
+ * not on the order of the values, nbatch, the problem's position, its neighbours, the launch shape or the host / _dev entry.
+ * There are no floating-point atomics; the counts of the selection are integers added with LDS atomics, whose result does not
+ * depend on the order.
+ * Algorithm.  One wave per problem, the waves stride over the problems.  A double is mapped to a 64-bit key of the same order
+ * and the key of the middle rank is found most significant byte first: 8 sweeps over the problem's values with a 256-bin
+ * histogram in LDS (16 sweeps for med and MAD, one more each where an even count needs the next key above).  No scratch: the
+ * values are read from the caller's array and widened on load.  The entry is for many SMALL problems.
+ * Status, decided on the host before any device work, nothing written on a failure: SPLPAK_E_BADARG for offsets null,
+ * nbatch < 1, offsets that decrease, values null, stats null.  A batch without points returns 0 with zeros. */
+int32_t splpak_mad_many_f64(int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const double *values,
+                            const double *wsel /* may be NULL */, double *stats /* 4 per problem */);
+/* REAL32 storage: values and wsel are float, the keys and stats double */
+int32_t splpak_mad_many_f32(int32_t nbatch, const int64_t *offsets /* nbatch + 1 */, const float *values,
+                            const float *wsel /* may be NULL */, double *stats /* 4 per problem */);
+/* the same on resident data: values, wsel and stats are device arrays, offsets a host array.  Asynchronous on `stream` exactly
+ * as splpak_residuals_many_dev_*: stats stays in the caller's device memory. */
+int32_t splpak_mad_many_dev_f64(int32_t nbatch, const int64_t *offsets /* host */, const double *values_dev,
+                                const double *wsel_dev /* may be NULL */, double *stats_dev, void *stream);
+int32_t splpak_mad_many_dev_f32(int32_t nbatch, const int64_t *offsets /* host */, const float *values_dev,
+                                const float *wsel_dev /* may be NULL */, double *stats_dev, void *stream);
+/* host counters of the calling thread's last splpak_eval_many_*, splpak_eval_many_var_* splpak_residuals_many_* or splpak_mad_many_* call (nothing is waited for):
  * [0] workgroups launched, [1] launches of the call, [2] queries / points sent, [3] problems, [4] eval_many: the queries one
  * sweep of the launch covers (the launch strides over the rest); residuals_many: 0 (a sweep covers [0] problems, one wave
- * each), [5] 1 for eval_many, 2 for residuals_many, 3 for eval_many_var (the other slots as eval_many), [6] [7] 0.  All 0 after a call its ladder refused. */
+ * each), [5] 1 for eval_many, 2 for residuals_many, 3 for eval_many_var (the other slots as eval_many), 4 for mad_many (the other slots as
+ * residuals_many), [6] [7] 0.  All 0 after a call its ladder refused. */
 int32_t splpak_debug_eval_many_stats(int64_t out8[8]);
 
 /* Several coefficient sets at the same points in one call: the evaluation half of splpak_refit_* / splpak_plan_refit_dev

@@ -45,6 +45,8 @@ SYMBOLS = [
     "splpak_fit_many_f64", "splpak_fit_many_f32", "splpak_fit_many_dev_f64", "splpak_fit_many_dev_f32", "splpak_fit_many_lds_bytes",
     "splpak_debug_fit_many_stats",
     "splpak_fit_many_clip_f64", "splpak_fit_many_clip_f32", "splpak_fit_many_clip_dev_f64", "splpak_fit_many_clip_dev_f32",
+    "splpak_fit_many_clip_mad_f64", "splpak_fit_many_clip_mad_f32", "splpak_fit_many_clip_mad_dev_f64", "splpak_fit_many_clip_mad_dev_f32",
+    "splpak_mad_many_f64", "splpak_mad_many_f32", "splpak_mad_many_dev_f64", "splpak_mad_many_dev_f32",
     "splpak_fit_many_cov_f64", "splpak_fit_many_cov_f32", "splpak_fit_many_cov_dev_f64", "splpak_fit_many_cov_dev_f32", "splpak_fit_many_cov_len",
     "splpak_eval_many_f64", "splpak_eval_many_f32", "splpak_eval_many_dev_f64", "splpak_eval_many_dev_f32",
     "splpak_eval_many_var_f64", "splpak_eval_many_var_f32", "splpak_eval_many_var_dev_f64", "splpak_eval_many_var_dev_f32",
@@ -261,6 +263,22 @@ def lib() -> C.CDLL:
     L.splpak_eval_many_dev_f64.argtypes = [i32, i32, _lp, vp, i32, _ip, vp, i64, _dp, _dp, _ip, vp, vp]
     L.splpak_eval_many_dev_f32.restype = i32
     L.splpak_eval_many_dev_f32.argtypes = [i32, i32, _lp, vp, i32, _ip, vp, i64, _fp, _fp, _ip, vp, vp]
+    L.splpak_fit_many_clip_mad_f64.restype = i32
+    L.splpak_fit_many_clip_mad_f64.argtypes = [i32, i32, _lp, _dp, i32, _dp, _dp, _dp, _dp, _ip, dbl, dbl, dbl, i32, i32, _dp, _dp, i64, _ip, _dp, _dp]
+    L.splpak_fit_many_clip_mad_f32.restype = i32
+    L.splpak_fit_many_clip_mad_f32.argtypes = [i32, i32, _lp, _fp, i32, _fp, _fp, _fp, _fp, _ip, flt, flt, flt, i32, i32, _fp, _fp, i64, _ip, _dp, _dp]
+    L.splpak_fit_many_clip_mad_dev_f64.restype = i32
+    L.splpak_fit_many_clip_mad_dev_f64.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _dp, _dp, _ip, dbl, dbl, dbl, i32, i32, vp, vp, i64, _ip, _dp, _dp, vp]
+    L.splpak_fit_many_clip_mad_dev_f32.restype = i32
+    L.splpak_fit_many_clip_mad_dev_f32.argtypes = [i32, i32, _lp, vp, i32, vp, vp, _fp, _fp, _ip, flt, flt, flt, i32, i32, vp, vp, i64, _ip, _dp, _dp, vp]
+    L.splpak_mad_many_f64.restype = i32
+    L.splpak_mad_many_f64.argtypes = [i32, _lp, _dp, _dp, _dp]
+    L.splpak_mad_many_f32.restype = i32
+    L.splpak_mad_many_f32.argtypes = [i32, _lp, _fp, _fp, _dp]
+    L.splpak_mad_many_dev_f64.restype = i32
+    L.splpak_mad_many_dev_f64.argtypes = [i32, _lp, vp, vp, vp, vp]
+    L.splpak_mad_many_dev_f32.restype = i32
+    L.splpak_mad_many_dev_f32.argtypes = [i32, _lp, vp, vp, vp, vp]
     L.splpak_residuals_many_f64.restype = i32
     L.splpak_residuals_many_f64.argtypes = [i32, i32, _lp, _dp, i32, _dp, _dp, _dp, i64, _dp, _dp, _ip, _dp, _dp]
     L.splpak_residuals_many_f32.restype = i32
@@ -906,6 +924,88 @@ def fit_many_clip_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coe
     return rc, status, info, clip
 
 
+def fit_many_clip_mad(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, regrow=0, real32=False,
+                      ldcoef=None, coef=None, l1xdat=None, wout=None):
+    """Robustly clipped batch fits in one launch (splpak_fit_many_clip_mad_*): fit_many_clip's loop with the median of t = w0 r as
+    the centre, 1.4826 MAD as the scale and, with regrow != 0, rejected points judged again in every pass against their original
+    weight; bit for bit the loop fit_many -> residuals_many -> mad_many -> the rule -> fit_many.  Layouts as fit_many.
+    -> (coef, wout, ierror, status (nbatch), info (nbatch, 10) of the last fit, clip (nbatch, 6) = (residual passes, points out
+    at the end, points counted by the last fit, s and med of the last pass, points returned in total))."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
+    ydata = np.ascontiguousarray(ydata, dtype=dt)
+    if wdata is not None:
+        wdata = np.ascontiguousarray(wdata, dtype=dt)
+    if l1xdat is None:
+        l1xdat = xdata.shape[1]
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
+    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
+    ldc = ncol if ldcoef is None else int(ldcoef)
+    if coef is None:
+        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
+    if wout is None:
+        wout = np.zeros(max(ydata.size, 1), dtype=dt)
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    clip = np.zeros((max(nbatch, 1), 6))
+    fn = lib().splpak_fit_many_clip_mad_f32 if real32 else lib().splpak_fit_many_clip_mad_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
+                   _p(nodes, _ip), float(xtrap), float(klo), float(khi), int(maxpass), int(regrow), _p(wout, rp), _p(coef, rp), ldc,
+                   _p(status, _ip), _p(info, _dp), _p(clip, _dp)))
+    return coef, wout, rc, status, info, clip
+
+
+def fit_many_clip_mad_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, wout, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5,
+                          regrow=0, l1xdat=None, ldcoef=None, stream=0):
+    """fit_many_clip_mad on torch device tensors: xdata, ydata, wdata (or None), coef and wout on the device, offsets on the host.
+    -> (ierror, status (nbatch), info (nbatch, 10), clip (nbatch, 6))."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nbatch = offsets.size - 1
+    real32 = str(xdata.dtype).endswith("float32")
+    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
+    rp = _fp if real32 else _dp
+    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
+    if l1xdat is None:
+        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
+    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
+    info = np.zeros((max(nbatch, 1), 10))
+    clip = np.zeros((max(nbatch, 1), 6))
+    fn = lib().splpak_fit_many_clip_mad_dev_f32 if real32 else lib().splpak_fit_many_clip_mad_dev_f64
+    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
+                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap), float(klo),
+                   float(khi), int(maxpass), int(regrow), wout.data_ptr(), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef),
+                   _p(status, _ip), _p(info, _dp), _p(clip, _dp), C.c_void_p(stream)))
+    return rc, status, info, clip
+
+
+def mad_many(offsets, values, wsel=None, real32=False):
+    """The median and the MAD of every problem's segment of `values` in one launch (splpak_mad_many_*): problem k owns the global
+    indices offsets[k] .. offsets[k+1]-1; a point is counted where wsel is not 0 (None: every point).  Exact order statistics,
+    numpy.median's bits.  -> (stats (nbatch, 4) = (points counted, median, MAD, 0), ierror)."""
+    dt = np.float32 if real32 else np.float64
+    rp = _fp if real32 else _dp
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    nbatch = offsets.size - 1
+    values = np.ascontiguousarray(values, dtype=dt)
+    if wsel is not None:
+        wsel = np.ascontiguousarray(wsel, dtype=dt)
+    stats = np.full((max(nbatch, 1), 4), -999.0)
+    rc = _check((lib().splpak_mad_many_f32 if real32 else lib().splpak_mad_many_f64)(nbatch, _p(offsets, _lp), _p(values, rp), _p(wsel, rp),
+                                                                                  _p(stats, _dp)))
+    return stats, rc
+
+
+def mad_many_dev(offsets, values, wsel, stats, stream=0):
+    """mad_many on torch device tensors (asynchronous on `stream`): values, wsel (or None) and stats (nbatch, 4) float64 on the
+    device, offsets on the host.  float32 values take the REAL32 entry.  -> ierror."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    real32 = str(values.dtype).endswith("float32")
+    fn = lib().splpak_mad_many_dev_f32 if real32 else lib().splpak_mad_many_dev_f64
+    return _check(fn(offsets.size - 1, _p(offsets, _lp), values.data_ptr(), None if wsel is None else wsel.data_ptr(), stats.data_ptr(),
+                     C.c_void_p(stream)))
+
+
 def fit_many_cov_len(ndim, nodes) -> int:
     """Words of one problem's `cov` in fit_many_cov: ncol (7^ndim + 1) / 2 (host only; splpak_fit_many_cov_len); raises for a
     shape fit_many_lds_bytes rejects."""
@@ -1061,7 +1161,7 @@ def residuals_many(ndim, offsets, xdata, ydata, wdata, coef, xmin, xmax, nodes, 
 def debug_eval_many_stats():
     """Host counters of this thread's last evaluate_many / residuals_many call: (workgroups launched, launches, queries / points
     sent, problems, queries one sweep of an evaluate_many launch covers (residuals_many: 0), 1 evaluate_many / 2 residuals_many /
-    3 evaluate_many_var, 0, 0)."""
+    3 evaluate_many_var / 4 mad_many, 0, 0)."""
     v = np.zeros(8, dtype=np.int64)
     _check(lib().splpak_debug_eval_many_stats(_p(v, _lp)))
     return tuple(int(t) for t in v)

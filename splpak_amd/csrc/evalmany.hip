@@ -228,11 +228,13 @@ residuals_many_kernel(Grid g, int nbatch, const long long *__restrict__ offsets,
 // the per-thread scratch of the batch entries (manyhost.hpp)
 thread_local DevScratch<1> t_many_offsets;
 thread_local DevScratch<2> t_fit_many_tables;
+thread_local DevScratch<1> t_fit_many_mad_t;
 
 void many_scratch_shutdown()
 {
     t_many_offsets.release();
     t_fit_many_tables.release();
+    t_fit_many_mad_t.release();
 }
 
 template <typename T>

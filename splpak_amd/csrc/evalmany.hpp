@@ -34,4 +34,10 @@ template <typename T>
 hipError_t launch_residuals_many(const Grid &g, int nbatch, const long long *offsets_dev, long long base, const T *xdata, int l1xdat,
                                  const T *ydata, const T *wdata, const T *coef, long long ldcoef, T *resid, double *stats, hipStream_t st);
 
+// stats[4k .. 4k+3] = {points counted, median, MAD, 0} of values[offsets[k] - base .. offsets[k+1] - base) where wsel (may be
+// null: all) is not 0 (madmany.hip; the definitions: include/splpak_hip.h, splpak_mad_many_*); one launch, a wave per problem.
+template <typename T>
+hipError_t launch_mad_many(int nbatch, const long long *offsets_dev, long long base, const T *values, const T *wsel, double *stats,
+                           hipStream_t st);
+
 }  // namespace splpak

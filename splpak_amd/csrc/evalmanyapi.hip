@@ -1,6 +1,6 @@
 // The entries of the batch evaluation at each problem's own points (include/splpak_hip.h): splpak_eval_many_*,
-// splpak_eval_many_var_* (the prediction variance from the stencils of splpak_fit_many_cov_*) and
-// splpak_residuals_many_* on host and device pointers, and their counters.  Each family has one ladder of checks, in the order
+// splpak_eval_many_var_* (the prediction variance from the stencils of splpak_fit_many_cov_*),
+// splpak_residuals_many_* and splpak_mad_many_* (madmany.hip) on host and device pointers, and their counters.  Each family has one ladder of checks, in the order
 // the header gives, all on the host; then evalmany.hip.  The _dev entries only enqueue: the one thing they upload is the
 // offsets, into the calling thread's scratch (manyhost.hpp: many_offsets_upload, held by a ScratchUse to the end of the
 // call).  The host entries stage the span of the batch's points and (nbatch-1)*ldcoef + ncol coefficients through device
@@ -208,9 +208,70 @@ int32_t residuals_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64
     return many_status(e, what, 0);
 }
 
+// ---- splpak_mad_many_* ----
+template <typename T>
+int32_t mad_many_entry(bool dev, int32_t nbatch, const int64_t *offsets, const T *values, const T *wsel, double *stats, hipStream_t st)
+{
+    for (int j = 0; j < 8; ++j) t_eval_many_stats[j] = 0;
+    bool ok = offsets && nbatch >= 1;
+    for (int k = 0; ok && k < nbatch; ++k) ok = offsets[k + 1] >= offsets[k];
+    if (!ok || !values || !stats) {
+        set_error("offsets null, nbatch < 1, offsets that decrease, or values or stats null");
+        return SPLPAK_E_BADARG;
+    }
+    const ManySpan sp = many_span(offsets, nbatch);
+    many_counters(4, sp.n, nbatch);
+    if (sp.n == 0 && !dev) {      // nothing for a device to do
+        for (size_t j = 0; j < 4 * (size_t)nbatch; ++j) stats[j] = 0.0;
+        return 0;
+    }
+    if (int r = device_ready()) return r;
+
+    const char *what = "medians of a batch of segments";
+    const ScratchUse<1> use{t_many_offsets, st};
+    const long long *off_dev = nullptr;
+    if (dev) {
+        hipError_t e = many_offsets_upload(offsets, nbatch, st, &off_dev);
+        if (e == hipSuccess) e = launch_mad_many<T>(nbatch, off_dev, 0, values, wsel, stats, st);
+        return many_status(e, what, 0);
+    }
+    CallStage cs;
+    const T *vs = nullptr, *wsd = nullptr;
+    double *sd = nullptr;
+    hipError_t e = stage_copy(cs, values + sp.lo, (size_t)sp.n, &vs);
+    if (e == hipSuccess && wsel) e = stage_copy(cs, wsel + sp.lo, (size_t)sp.n, &wsd);
+    if (e == hipSuccess && !cs.get(&sd, 4 * (size_t)nbatch)) e = hipErrorOutOfMemory;
+    if (e == hipSuccess) e = many_offsets_upload(offsets, nbatch, nullptr, &off_dev);
+    if (e == hipSuccess) e = launch_mad_many<T>(nbatch, off_dev, sp.lo, vs, wsd, sd, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(stats, sd, sizeof(double) * 4 * (size_t)nbatch, hipMemcpyDeviceToHost);
+    return many_status(e, what, 0);
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t splpak_mad_many_f64(int32_t nbatch, const int64_t *offsets, const double *values, const double *wsel, double *stats)
+{
+    return mad_many_entry<double>(false, nbatch, offsets, values, wsel, stats, nullptr);
+}
+
+int32_t splpak_mad_many_f32(int32_t nbatch, const int64_t *offsets, const float *values, const float *wsel, double *stats)
+{
+    return mad_many_entry<float>(false, nbatch, offsets, values, wsel, stats, nullptr);
+}
+
+int32_t splpak_mad_many_dev_f64(int32_t nbatch, const int64_t *offsets, const double *values_dev, const double *wsel_dev, double *stats_dev,
+                                void *stream)
+{
+    return mad_many_entry<double>(true, nbatch, offsets, values_dev, wsel_dev, stats_dev, (hipStream_t)stream);
+}
+
+int32_t splpak_mad_many_dev_f32(int32_t nbatch, const int64_t *offsets, const float *values_dev, const float *wsel_dev, double *stats_dev,
+                                void *stream)
+{
+    return mad_many_entry<float>(true, nbatch, offsets, values_dev, wsel_dev, stats_dev, (hipStream_t)stream);
+}
 
 int32_t splpak_eval_many_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xq, int32_t ldxq, const int32_t *nderiv,
                              const double *coef, int64_t ldcoef, const double *xmin, const double *xmax, const int32_t *nodes, double *out)

@@ -1,7 +1,8 @@
 // Many small independent fits on one node grid (include/splpak_hip.h: splpak_fit_many_*): what the entries (fitmanyapi.hip)
 // and the kernel with its driver (fitmany.hip) share -- and the clipped fits (splpak_fit_many_clip_*: fitmanyclipapi.hip,
 // fitmanyclip.hip), which run the same fit inside a clipping loop, and the fits with their covariance (splpak_fit_many_cov_*:
-// fitmanycovapi.hip, fitmanycov.hip), which turn the band factor into the band of its inverse afterwards.
+// fitmanycovapi.hip, fitmanycov.hip), which turn the band factor into the band of its inverse afterwards, and the robustly
+// clipped fits (splpak_fit_many_clip_mad_*: fitmanymadapi.hip, fitmanymad.hip): the loop on a median / MAD scale.
 #pragma once
 #include "common.hpp"
 #include "../../include/splpak_hip.h"
@@ -83,6 +84,19 @@ struct FitManyClipArgs {
     int maxpass;
 };
 
+// The robust clipping loop (fitmanymad.hip; the rule: include/splpak_hip.h, splpak_fit_many_clip_mad_*).  Its result block per
+// problem: the FM_* slots of the LAST fit, FM_SPARE = the fits the problem ran, then the six clip numbers.
+enum { FMM_PASSES = FM_RESULT, FMM_OUT, FMM_COUNTED, FMM_S, FMM_MED, FMM_RETURNED, FMM_RESULT };
+
+struct FitManyMadArgs {
+    FitManyArgs f;                 // f.result: [nrun][FMM_RESULT]
+    Grid gref;                     // the caller's order, as FitManyClipArgs
+    double klo, khi;
+    int maxpass, regrow;
+    double *t;                     // the weighted residuals of a pass, one per point of the batch's span (the calling thread's scratch)
+    long long tbase;               // point i of the arrays (global index minus f.base) has t[i - tbase]
+};
+
 extern thread_local long long t_fit_many_stats[8];
 
 // The device part on device arrays: one launch.  0 or SPLPAK_E_*; *seconds = the launch's device time.
@@ -96,6 +110,11 @@ int fit_many_cov_launch(const FitManyArgs &a, const T *xdata, const T *ydata, co
 template <typename T>
 int fit_many_clip_launch(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
                          double *seconds);
+
+// .. of the robustly clipped fits
+template <typename T>
+int fit_many_mad_launch(const FitManyMadArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
+                        double *seconds);
 
 // workgroups of a batch launch: as many as fit on the device at once, or one per problem if that is fewer
 template <typename K>

@@ -15,7 +15,7 @@
 //                  first-weight decision is taken once, from `wdata`, before the loop.
 // r is formed twice per pass (the reject step needs v first).
 #include "fitmanydev.hpp"
-#include "evalcore.hpp"
+#include "fitmanyresid.hpp"
 
 namespace splpak {
 
@@ -25,35 +25,6 @@ using namespace fitmanydev;
 
 // every operation of the rule below is rounded on its own (the fit and the factor tables come from the headers above)
 #pragma clang fp contract(off)
-
-// eval_point of evalmany.hip (value pattern) with the window rows read from cf in LDS: the coefficients as stored, widened
-template <int D, typename T>
-__device__ inline double eval_from_lds(const Grid &g, const T *__restrict__ x, const double *cf)
-{
-    double b[D][4];
-    int base = 0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const double xd = (double)x[d];
-        const int ws = eval_table<true>(g, d, xd, 0, b[d]);
-        base += ws * g.colstride[d];
-    }
-    const int s1 = D > 1 ? g.colstride[1] : 0;
-    return window_sum<D>(b, [&](int k1, int, int, double (&c)[4]) {
-        const double *p = cf + base + k1 * s1;
-        c[0] = p[0]; c[1] = p[1]; c[2] = p[2]; c[3] = p[3];
-    });
-}
-
-// t = w r of point i (w != 0), each operation rounded on its own
-template <int D, typename T>
-__device__ inline double weighted_residual(const Grid &g, const T *__restrict__ xd, int l1xdat, const T *__restrict__ yd, long long i,
-                                           double w, const double *cf)
-{
-    const double f = eval_from_lds<D, T>(g, xd + i * l1xdat, cf);
-    const double r = (double)yd[i] - f;
-    return w * r;
-}
 
 // The waves per SIMD of fit_many_kernel are asked for (2-D: 2, 1-D: 4): the loop's state beside the fit's would otherwise take
 // 258 registers in the 2-D 256-thread shape (one workgroup per CU instead of two) and 158 in 1-D (3 waves per SIMD instead of

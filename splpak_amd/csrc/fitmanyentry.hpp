@@ -1,6 +1,6 @@
 // The host side of a batch of small fits, shared by splpak_fit_many_* (fitmanyapi.hip), splpak_fit_many_clip_*
-// (fitmanyclipapi.hip) and splpak_fit_many_cov_* (fitmanycovapi.hip; its cov is staged and scattered like coef): the ladder of checks in the order the header gives, all on the host; then the one launch
-// (fitmany.hip / fitmanyclip.hip) and the scatter of its results.  The tables of a call -- offsets, problem list, results --
+// (fitmanyclipapi.hip), splpak_fit_many_clip_mad_* (fitmanymadapi.hip) and splpak_fit_many_cov_* (fitmanycovapi.hip; its cov is staged and scattered like coef): the ladder of checks in the order the header gives, all on the host; then the one launch
+// (fitmany.hip / fitmanyclip.hip / fitmanymad.hip) and the scatter of its results.  The tables of a call -- offsets, problem list, results --
 // live in the calling thread's scratch (manyhost.hpp), each held by a ScratchUse to the end of the call: a _dev call whose
 // scratch is large enough allocates and frees nothing.  The host entries stage the span of the batch's points and the compact
 // coefficients through device memory of the call.
@@ -20,7 +20,10 @@ struct ClipSpec {
     double klo, khi;
     int32_t maxpass;
     T *wout;
-    double *clip;      // 4 per problem, may be null
+    double *clip;      // nclip per problem, may be null
+    int nclip = 4;     // the numbers after the FM_* slots of a problem's result block
+    bool mad = false;  // the median / MAD rule of splpak_fit_many_clip_mad_* (6 clip numbers) instead of the rms rule
+    int32_t regrow = 0;
 };
 
 // What the covariance entries (splpak_fit_many_cov_*) add (null: no covariance)
@@ -70,14 +73,15 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
 
     try {
         const int ncol = a.g.ncol;
-        const size_t nres = clip ? FMC_RESULT : FM_RESULT;
+        const size_t nclip = clip ? (size_t)clip->nclip : 0;
+        const size_t nres = FM_RESULT + nclip;
         std::vector<int> plist;
         for (int k = 0; k < nbatch; ++k) {
             const bool empty = offsets[k + 1] == offsets[k];
             if (!empty) plist.push_back(k);
             if (status) status[k] = empty ? 105 : 0;
             if (info) for (int j = 0; j < 10; ++j) info[(size_t)k * 10 + j] = 0.0;
-            if (clip && clip->clip) for (int j = 0; j < 4; ++j) clip->clip[(size_t)k * 4 + j] = 0.0;
+            if (clip && clip->clip) for (size_t j = 0; j < nclip; ++j) clip->clip[(size_t)k * nclip + j] = 0.0;
         }
         const int nrun = (int)plist.size();
         t_fit_many_stats[1] = a.sh.bytes;
@@ -92,13 +96,21 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
         std::vector<T> ch(dev ? 0 : (size_t)nrun * (size_t)ncol);
         std::vector<T> wh(dev || !clip ? 0 : (size_t)sp.n);
         std::vector<T> covh(dev || !covs ? 0 : (size_t)nrun * (size_t)covlen);
-        const long long allocs_before = t_many_offsets.allocs + t_fit_many_tables.allocs;
+        const bool mad = clip && clip->mad;
+        const long long allocs_before = t_many_offsets.allocs + t_fit_many_tables.allocs + t_fit_many_mad_t.allocs;
         const ScratchUse<1> use_offsets{t_many_offsets, st};
         const ScratchUse<2> use_tables{t_fit_many_tables, st};
+        struct MadUse {      // ScratchUse of the robust rule's residuals, for the calls that use them
+            bool on;
+            hipStream_t st;
+            ~MadUse() { if (on && t_fit_many_mad_t.last) (void)t_fit_many_mad_t.mark_used(st); }
+        } const use_t{mad, st};
         CallStage cs;      // (the host entries alone)
         const size_t need[2] = {sizeof(int) * (size_t)nrun, sizeof(double) * res.size()};
         hipError_t e = many_offsets_upload(offsets, nbatch, st, &a.offsets);
         if (e == hipSuccess) e = scratch_begin(t_fit_many_tables, need, st);
+        const size_t need_t[1] = {sizeof(double) * (size_t)sp.n};
+        if (e == hipSuccess && mad) e = scratch_begin(t_fit_many_mad_t, need_t, st);
         // (pageable memory: the copy has left `plist` when the call returns)
         if (e == hipSuccess) e = hipMemcpyAsync(t_fit_many_tables.buf[0], plist.data(), need[0], hipMemcpyHostToDevice, st);
         a.nrun = nrun;
@@ -123,10 +135,21 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
             a.ldcoef = ncol;
             a.compact = 1;
         }
-        t_fit_many_stats[6] = t_many_offsets.allocs + t_fit_many_tables.allocs - allocs_before + (long long)cs.held.size();
+        t_fit_many_stats[6] = t_many_offsets.allocs + t_fit_many_tables.allocs + t_fit_many_mad_t.allocs - allocs_before + (long long)cs.held.size();
         if (e != hipSuccess) return many_status(e, what, 0);
         double seconds = 0.0;
-        if (clip) {
+        if (mad) {
+            FitManyMadArgs ma{};
+            ma.f = a;
+            if (int r = build_grid(ndim, nodes, xmin, xmax, ma.gref, nullptr)) return r;
+            ma.klo = clip->klo;
+            ma.khi = clip->khi;
+            ma.maxpass = clip->maxpass;
+            ma.regrow = clip->regrow != 0;
+            ma.t = t_fit_many_mad_t.as<double>(0);
+            ma.tbase = sp.lo - a.base;
+            if (int r = fit_many_mad_launch<T>(ma, xd, yd, wd, wo, cd, st, &seconds)) return r;
+        } else if (clip) {
             // the residuals are evaluated on the grid in the caller's order (it was valid above)
             if (int r = build_grid(ndim, nodes, xmin, xmax, ca.gref, nullptr)) return r;
             ca.klo2 = clip->klo * clip->klo;
@@ -167,7 +190,7 @@ int32_t fit_many_entry(bool dev, int32_t ndim, int32_t nbatch, const int64_t *of
                 ik[8] = v[FM_RESERR];
             }
             if (clip && clip->clip)
-                for (int j = 0; j < 4; ++j) clip->clip[(size_t)k * 4 + j] = v[FMC_PASSES + j];
+                for (size_t j = 0; j < nclip; ++j) clip->clip[(size_t)k * nclip + j] = v[FM_RESULT + j];
             if (!dev) {
                 T *ck = coef + (long long)k * ldcoef;
                 for (int i = 0; i < ncol; ++i) ck[i] = ch[(size_t)r * (size_t)ncol + (size_t)i];

@@ -44,6 +44,9 @@ hipError_t stage_span(CallStage &cs, ManySpan sp, const T *x, int ld, const T *y
 // [nrun][FM_RESULT].  Two scratches, so that a regrow of one leaves the other alone.
 extern thread_local DevScratch<1> t_many_offsets;
 extern thread_local DevScratch<2> t_fit_many_tables;
+// .. and the weighted residuals of splpak_fit_many_clip_mad_*: a double per point of the batch's span (fitmanymad.hip selects
+// its medians from them)
+extern thread_local DevScratch<1> t_fit_many_mad_t;
 void many_scratch_shutdown();
 
 // The scratch holds `need` on the current device and st waits for the previous use of it (which may have been on another

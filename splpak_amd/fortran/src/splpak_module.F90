@@ -26,6 +26,7 @@
 !!    `evaluate_each` evaluates the fits of `initialize_many`, each at its own points, and `residuals_each` forms their residuals
 !!    and per-problem sums, one launch each,
 !!    `initialize_many_clipped` runs the sigma-clipping loop of those two around `initialize_many` inside the one launch,
+!!    `initialize_many_robust` is that loop on a median / MAD scale with returning points, and `mad_each` its selection alone,
 !!    `initialize_many_cov` is `initialize_many` with the covariance of the coefficients, and `variance_each` the prediction
 !!    variance of those fits, each at its own points,
 !!    `evaluate_grid` evaluates every point of a tensor-product grid of points from its axes alone,
@@ -83,6 +84,8 @@ module splpak_module
         procedure,public :: initialize_many_cov => splpak_fit_many_cov !! initialize_many with the covariance of the coefficients (additive)
         procedure,public :: variance_each => splpak_variance_each !! the prediction variance of those fits, each at its own points (additive)
         procedure,public :: evaluate_each => splpak_eval_each      !! the fits of initialize_many, each at its own points, in one launch (additive)
+        procedure,public :: initialize_many_robust => splpak_fit_many_robust !! .. clipped on a median / MAD scale, points may return (additive)
+        procedure,public :: mad_each => splpak_mad_each !! the median and the MAD of every problem's values in one launch (additive)
         procedure,public :: residuals_each => splpak_residuals_each !! their residuals and per-problem sums in one launch (additive)
         generic,public   :: evaluate      => splfe, splde        !! one point
         generic,public   :: evaluate_many => splfe_many, splde_many  !! batch of points (additive)
@@ -237,6 +240,30 @@ module splpak_module
             type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, wout, coef, status, info, clip
             real(wp),value :: xtrap, klo, khi
         end function c_fit_many_clip
+#ifdef REAL32
+        integer(c_int32_t) function c_fit_many_clip_mad(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,klo,khi, &
+                                                        maxpass,regrow,wout,coef,ldcoef,status,info,clip) &
+                                                        bind(C,name='splpak_fit_many_clip_mad_f32')
+#else
+        integer(c_int32_t) function c_fit_many_clip_mad(ndim,nbatch,offsets,xdata,l1xdat,ydata,wdata,xmin,xmax,nodes,xtrap,klo,khi, &
+                                                        maxpass,regrow,wout,coef,ldcoef,status,info,clip) &
+                                                        bind(C,name='splpak_fit_many_clip_mad_f64')
+#endif
+            import :: c_int32_t, c_int64_t, c_ptr, wp
+            integer(c_int32_t),value :: ndim, nbatch, l1xdat, maxpass, regrow
+            integer(c_int64_t),value :: ldcoef
+            type(c_ptr),value :: offsets, xdata, ydata, wdata, xmin, xmax, nodes, wout, coef, status, info, clip
+            real(wp),value :: xtrap, klo, khi
+        end function c_fit_many_clip_mad
+#ifdef REAL32
+        integer(c_int32_t) function c_mad_many(nbatch,offsets,values,wsel,stats) bind(C,name='splpak_mad_many_f32')
+#else
+        integer(c_int32_t) function c_mad_many(nbatch,offsets,values,wsel,stats) bind(C,name='splpak_mad_many_f64')
+#endif
+            import :: c_int32_t, c_ptr
+            integer(c_int32_t),value :: nbatch
+            type(c_ptr),value :: offsets, values, wsel, stats
+        end function c_mad_many
 #ifdef REAL32
         integer(c_int32_t) function c_eval_many(ndim,nbatch,offsets,xq,ldxq,nderiv,coef,ldcoef,xmin,xmax,nodes,out) &
                                                 bind(C,name='splpak_eval_many_f32')
@@ -884,6 +911,87 @@ module splpak_module
         end if
 #endif
     end subroutine splpak_fit_many_clipped
+
+    !> `initialize_many_clipped` on a robust scale (include/splpak_hip.h, splpak_fit_many_clip_mad_f64, which states the rule):
+    !! the centre is the median of the weighted residuals, the scale 1.4826 times their MAD, and with regrow /= 0 every point of
+    !! non-zero starting weight is judged again in every pass, so a good point rejected beside a run of outliers returns.  The
+    !! whole loop runs in one launch, bit for bit the loop initialize_many -> residuals_each -> mad_each -> the rule ->
+    !! initialize_many.  Arguments as `initialize_many_clipped` with regrow after maxpass; the optional clip(6,nbatch) =
+    !! [ residual passes, points out at the end, points counted by the last fit, s and med of the last pass, points returned in
+    !! total ].  ierrors and ierror as `initialize_many_clipped`; refused with -4 under set_host, set_gpus(n > 1) and in the
+    !! -DREAL128 build, exactly as it is.
+    subroutine splpak_fit_many_robust(me,ndim,nbatch,offsets,xdata,l1xdat,ydata,xmin,xmax,nodes,xtrap,klo,khi,maxpass,regrow,wout, &
+                                      coef,ldcoef,ierrors,ierror,wdata,clip)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: ndim, nbatch, l1xdat, ldcoef, maxpass, regrow
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: xdata(l1xdat,*), ydata(*)
+        real(wp),intent(in),target :: xmin(*), xmax(*)
+        integer,intent(in),target :: nodes(*)
+        real(wp),intent(in) :: xtrap, klo, khi
+        real(wp),intent(inout),target :: wout(*)
+        real(wp),intent(inout),target :: coef(ldcoef,*)
+        integer,intent(out),target :: ierrors(*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: wdata(*)
+        real(c_double),intent(out),optional,target :: clip(6,*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pw, pc
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' initialize_many_robust - not available in the -DREAL128 build')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' initialize_many_robust - not available under set_host or set_gpus(n > 1)')
+            return
+        end if
+        pw = c_null_ptr
+        if (present(wdata)) pw = c_loc(wdata)
+        pc = c_null_ptr
+        if (present(clip)) pc = c_loc(clip)
+        rc = c_fit_many_clip_mad(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
+                                 c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, klo, khi, int(maxpass,c_int32_t), &
+                                 int(regrow,c_int32_t), c_loc(wout), c_loc(coef), int(ldcoef,c_int64_t), c_loc(ierrors), c_null_ptr, pc)
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,'initialize_many_robust')
+        end if
+#endif
+    end subroutine splpak_fit_many_robust
+
+    !> The median and the MAD of every problem's values in one launch (splpak_mad_many_f64): stats(:,k) = [ points counted,
+    !! median, MAD, 0 ] of values(offsets(k)+1 : offsets(k+1)) where the optional wsel is not 0 (without it: every point) -- exact
+    !! order statistics, all 0 when nothing is counted.  ierror: -3 for a bad offset.  Refused with -4 under set_host,
+    !! set_gpus(n > 1) and in the -DREAL128 build, exactly as `residuals_each` is.
+    subroutine splpak_mad_each(me,nbatch,offsets,values,stats,ierror,wsel)
+        class(splpak_type),intent(inout),target :: me
+        integer,intent(in) :: nbatch
+        integer(c_int64_t),intent(in),target :: offsets(*)
+        real(wp),intent(in),target :: values(*)
+        real(c_double),intent(inout),target :: stats(4,*)
+        integer,intent(out) :: ierror
+        real(wp),intent(in),optional,target :: wsel(*)
+        integer(c_int32_t) :: rc
+        type(c_ptr) :: pw
+#ifdef REAL128
+        ierror = -4
+        call report(ierror,' mad_each - not available in the -DREAL128 build')
+#else
+        if (me%host .or. me%ngpus > 1) then
+            ierror = -4
+            call report(ierror,' mad_each - not available under set_host or set_gpus(n > 1)')
+            return
+        end if
+        pw = c_null_ptr
+        if (present(wsel)) pw = c_loc(wsel)
+        rc = c_mad_many(int(nbatch,c_int32_t), c_loc(offsets), c_loc(values), pw, c_loc(stats))
+        ierror = int(rc)
+        if (rc < 0) call report_library_failure(ierror,'mad_each')
+#endif
+    end subroutine splpak_mad_each
 
     !> The fits of `initialize_many`, each at its own points, in one launch (include/splpak_hip.h, splpak_eval_many_f64): problem
     !! k owns the points offsets(k)+1 .. offsets(k+1) of x(ldx,*) and f, and has its coefficients in coef(:,k), where
