@@ -823,13 +823,20 @@ def fit_many(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, r
     offsets[k] .. offsets[k+1]-1 of xdata (npoints, l1xdat), ydata and wdata (None: splcc); its coefficients go to row k of
     `coef` (nbatch, ldcoef), the layout evaluate_fields reads.  -> (coef, ierror, status (nbatch), info (nbatch, 10)); a
     problem without points has status 105 and its row of `coef` is left as it was."""
+    coef, rc, status, info, _, _, _ = _fit_many_host("fit_many", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, real32, ldcoef,
+                                                     coef, l1xdat)
+    return coef, rc, status, info
+
+
+def _fit_many_host(stem, ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, real32, ldcoef, coef, l1xdat, scalars=(), nclip=0,
+                   wout=None, with_cov=False, ldcov=None, cov=None):
+    """The host wrappers of the batch-fit family: the conversions and the outputs they share, then splpak_<stem>_f64 / _f32.
+    A variant adds `scalars` (between xtrap and the outputs), with nclip > 0 the weights `wout` (before coef) and `clip`
+    (nbatch, nclip) (last), with with_cov `cov` (nbatch, ldcov) after coef.
+    -> (coef, ierror, status, info, wout, clip, cov), None for what the variant does not have."""
     dt = np.float32 if real32 else np.float64
     rp = _fp if real32 else _dp
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    nbatch = offsets.size - 1
-    xdata = np.ascontiguousarray(xdata, dtype=dt)
-    if xdata.ndim == 1:
-        xdata = xdata.reshape(-1, 1)
+    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
     ydata = np.ascontiguousarray(ydata, dtype=dt)
     if wdata is not None:
         wdata = np.ascontiguousarray(wdata, dtype=dt)
@@ -838,19 +845,37 @@ def fit_many(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, r
     xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
     ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
     ldc = ncol if ldcoef is None else int(ldcoef)
+    n = max(nbatch, 1)
     if coef is None:
-        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    fn = lib().splpak_fit_many_f32 if real32 else lib().splpak_fit_many_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
-                   _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(status, _ip), _p(info, _dp)))
-    return coef, rc, status, info
+        coef = np.zeros((n, max(ldc, 1)), dtype=dt)
+    status = np.full(n, -999, dtype=np.int32)
+    info = np.zeros((n, 10))
+    args = [ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
+            _p(nodes, _ip), float(xtrap), *scalars]
+    clip = None
+    if nclip:
+        if wout is None:
+            wout = np.zeros(max(ydata.size, 1), dtype=dt)
+        clip = np.zeros((n, nclip))
+        args.append(_p(wout, rp))
+    args += [_p(coef, rp), ldc]
+    if with_cov:
+        ldv = ncol * ((7 ** max(int(ndim), 0) + 1) // 2) if ldcov is None else int(ldcov)
+        if cov is None:
+            cov = np.zeros((n, max(ldv, 1)), dtype=dt)
+        args += [_p(cov, rp), ldv]
+    args += [_p(status, _ip), _p(info, _dp)]
+    if nclip:
+        args.append(_p(clip, _dp))
+    rc = _check(getattr(lib(), f"splpak_{stem}_{'f32' if real32 else 'f64'}")(*args))
+    return coef, rc, status, info, wout, clip, cov
 
 
-def fit_many_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap=0.0, l1xdat=None, ldcoef=None, stream=0):
-    """fit_many on torch device tensors: xdata, ydata, wdata (or None) and coef on the device, offsets on the host.
-    -> (ierror, status (nbatch), info (nbatch, 10))."""
+def _fit_many_on_dev(stem, ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap, l1xdat, ldcoef, stream, scalars=(), nclip=0,
+                     wout=None, cov=None, ldcov=None):
+    """The _dev wrappers of the batch-fit family on torch device tensors, offsets on the host: splpak_<stem>_dev_f64 / _f32 by
+    xdata's dtype.  `scalars`, `wout` with `clip` (nbatch, nclip), and `cov` with `ldcov` as _fit_many_host places them.
+    -> (ierror, status, info, clip or None)."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     nbatch = offsets.size - 1
     real32 = str(xdata.dtype).endswith("float32")
@@ -859,13 +884,31 @@ def fit_many_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xt
     ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
     if l1xdat is None:
         l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    fn = lib().splpak_fit_many_dev_f32 if real32 else lib().splpak_fit_many_dev_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
-                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap),
-                   coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(status, _ip), _p(info, _dp), C.c_void_p(stream)))
-    return rc, status, info
+    n = max(nbatch, 1)
+    status = np.full(n, -999, dtype=np.int32)
+    info = np.zeros((n, 10))
+    args = [ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(), None if wdata is None else wdata.data_ptr(),
+            _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap), *scalars]
+    clip = None
+    if nclip:
+        clip = np.zeros((n, nclip))
+        args.append(wout.data_ptr())
+    args += [coef.data_ptr(), ncol if ldcoef is None else int(ldcoef)]
+    if cov is not None:
+        if ldcov is None:
+            ldcov = cov.stride(0) if cov.dim() > 1 else cov.shape[0]
+        args += [cov.data_ptr(), int(ldcov)]
+    args += [_p(status, _ip), _p(info, _dp)]
+    if nclip:
+        args.append(_p(clip, _dp))
+    rc = _check(getattr(lib(), f"splpak_{stem}_dev_{'f32' if real32 else 'f64'}")(*args, C.c_void_p(stream)))
+    return rc, status, info, clip
+
+
+def fit_many_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap=0.0, l1xdat=None, ldcoef=None, stream=0):
+    """fit_many on torch device tensors: xdata, ydata, wdata (or None) and coef on the device, offsets on the host.
+    -> (ierror, status (nbatch), info (nbatch, 10))."""
+    return _fit_many_on_dev("fit_many", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap, l1xdat, ldcoef, stream)[:3]
 
 
 def fit_many_clip(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, real32=False, ldcoef=None,
@@ -876,28 +919,9 @@ def fit_many_clip(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0
     -> (coef, wout, ierror, status (nbatch), info (nbatch, 10) of the last fit, clip (nbatch, 4) = (residual passes, points
     rejected, points counted by the last fit, S / cnt of the last pass)); wout (given, or zeros of ydata's length) holds the
     weights every problem ended with: 0 where a point was rejected."""
-    dt = np.float32 if real32 else np.float64
-    rp = _fp if real32 else _dp
-    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
-    ydata = np.ascontiguousarray(ydata, dtype=dt)
-    if wdata is not None:
-        wdata = np.ascontiguousarray(wdata, dtype=dt)
-    if l1xdat is None:
-        l1xdat = xdata.shape[1]
-    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
-    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
-    ldc = ncol if ldcoef is None else int(ldcoef)
-    if coef is None:
-        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
-    if wout is None:
-        wout = np.zeros(max(ydata.size, 1), dtype=dt)
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    clip = np.zeros((max(nbatch, 1), 4))
-    fn = lib().splpak_fit_many_clip_f32 if real32 else lib().splpak_fit_many_clip_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
-                   _p(nodes, _ip), float(xtrap), float(klo), float(khi), int(maxpass), _p(wout, rp), _p(coef, rp), ldc, _p(status, _ip),
-                   _p(info, _dp), _p(clip, _dp)))
+    coef, rc, status, info, wout, clip, _ = _fit_many_host("fit_many_clip", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, real32,
+                                                           ldcoef, coef, l1xdat, scalars=(float(klo), float(khi), int(maxpass)), nclip=4,
+                                                           wout=wout)
     return coef, wout, rc, status, info, clip
 
 
@@ -905,23 +929,8 @@ def fit_many_clip_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coe
                       l1xdat=None, ldcoef=None, stream=0):
     """fit_many_clip on torch device tensors: xdata, ydata, wdata (or None), coef and wout on the device, offsets on the host.
     -> (ierror, status (nbatch), info (nbatch, 10), clip (nbatch, 4))."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    nbatch = offsets.size - 1
-    real32 = str(xdata.dtype).endswith("float32")
-    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
-    rp = _fp if real32 else _dp
-    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
-    if l1xdat is None:
-        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    clip = np.zeros((max(nbatch, 1), 4))
-    fn = lib().splpak_fit_many_clip_dev_f32 if real32 else lib().splpak_fit_many_clip_dev_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
-                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap), float(klo),
-                   float(khi), int(maxpass), wout.data_ptr(), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), _p(status, _ip),
-                   _p(info, _dp), _p(clip, _dp), C.c_void_p(stream)))
-    return rc, status, info, clip
+    return _fit_many_on_dev("fit_many_clip", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap, l1xdat, ldcoef, stream,
+                            scalars=(float(klo), float(khi), int(maxpass)), nclip=4, wout=wout)
 
 
 def fit_many_clip_mad(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, regrow=0, real32=False,
@@ -931,28 +940,9 @@ def fit_many_clip_mad(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtr
     weight; bit for bit the loop fit_many -> residuals_many -> mad_many -> the rule -> fit_many.  Layouts as fit_many.
     -> (coef, wout, ierror, status (nbatch), info (nbatch, 10) of the last fit, clip (nbatch, 6) = (residual passes, points out
     at the end, points counted by the last fit, s and med of the last pass, points returned in total))."""
-    dt = np.float32 if real32 else np.float64
-    rp = _fp if real32 else _dp
-    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
-    ydata = np.ascontiguousarray(ydata, dtype=dt)
-    if wdata is not None:
-        wdata = np.ascontiguousarray(wdata, dtype=dt)
-    if l1xdat is None:
-        l1xdat = xdata.shape[1]
-    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
-    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
-    ldc = ncol if ldcoef is None else int(ldcoef)
-    if coef is None:
-        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
-    if wout is None:
-        wout = np.zeros(max(ydata.size, 1), dtype=dt)
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    clip = np.zeros((max(nbatch, 1), 6))
-    fn = lib().splpak_fit_many_clip_mad_f32 if real32 else lib().splpak_fit_many_clip_mad_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
-                   _p(nodes, _ip), float(xtrap), float(klo), float(khi), int(maxpass), int(regrow), _p(wout, rp), _p(coef, rp), ldc,
-                   _p(status, _ip), _p(info, _dp), _p(clip, _dp)))
+    coef, rc, status, info, wout, clip, _ = _fit_many_host("fit_many_clip_mad", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap,
+                                                           real32, ldcoef, coef, l1xdat,
+                                                           scalars=(float(klo), float(khi), int(maxpass), int(regrow)), nclip=6, wout=wout)
     return coef, wout, rc, status, info, clip
 
 
@@ -960,23 +950,8 @@ def fit_many_clip_mad_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes,
                           regrow=0, l1xdat=None, ldcoef=None, stream=0):
     """fit_many_clip_mad on torch device tensors: xdata, ydata, wdata (or None), coef and wout on the device, offsets on the host.
     -> (ierror, status (nbatch), info (nbatch, 10), clip (nbatch, 6))."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    nbatch = offsets.size - 1
-    real32 = str(xdata.dtype).endswith("float32")
-    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
-    rp = _fp if real32 else _dp
-    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
-    if l1xdat is None:
-        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    clip = np.zeros((max(nbatch, 1), 6))
-    fn = lib().splpak_fit_many_clip_mad_dev_f32 if real32 else lib().splpak_fit_many_clip_mad_dev_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
-                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap), float(klo),
-                   float(khi), int(maxpass), int(regrow), wout.data_ptr(), coef.data_ptr(), ncol if ldcoef is None else int(ldcoef),
-                   _p(status, _ip), _p(info, _dp), _p(clip, _dp), C.c_void_p(stream)))
-    return rc, status, info, clip
+    return _fit_many_on_dev("fit_many_clip_mad", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap, l1xdat, ldcoef, stream,
+                            scalars=(float(klo), float(khi), int(maxpass), int(regrow)), nclip=6, wout=wout)
 
 
 def mad_many(offsets, values, wsel=None, real32=False):
@@ -1021,27 +996,8 @@ def fit_many_cov(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.
     With wdata = 1 / sigma and no constraint rows Z is the covariance of the coefficients.
     -> (coef, cov, ierror, status (nbatch), info (nbatch, 10)); a problem of status 105 keeps its rows of coef and cov, one of
     status 107 has both zeroed."""
-    dt = np.float32 if real32 else np.float64
-    rp = _fp if real32 else _dp
-    offsets, nbatch, xdata = _many_host(offsets, xdata, dt)
-    ydata = np.ascontiguousarray(ydata, dtype=dt)
-    if wdata is not None:
-        wdata = np.ascontiguousarray(wdata, dtype=dt)
-    if l1xdat is None:
-        l1xdat = xdata.shape[1]
-    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, dt)
-    ncol = int(np.prod(np.maximum(nodes[:max(int(ndim), 0)].astype(np.int64), 1))) if nodes.size else 0
-    ldc = ncol if ldcoef is None else int(ldcoef)
-    ldv = ncol * ((7 ** max(int(ndim), 0) + 1) // 2) if ldcov is None else int(ldcov)
-    if coef is None:
-        coef = np.zeros((max(nbatch, 1), max(ldc, 1)), dtype=dt)
-    if cov is None:
-        cov = np.zeros((max(nbatch, 1), max(ldv, 1)), dtype=dt)
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    fn = lib().splpak_fit_many_cov_f32 if real32 else lib().splpak_fit_many_cov_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), _p(xdata, rp), int(l1xdat), _p(ydata, rp), _p(wdata, rp), _p(xmin, rp), _p(xmax, rp),
-                   _p(nodes, _ip), float(xtrap), _p(coef, rp), ldc, _p(cov, rp), ldv, _p(status, _ip), _p(info, _dp)))
+    coef, rc, status, info, _, _, cov = _fit_many_host("fit_many_cov", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap, real32,
+                                                       ldcoef, coef, l1xdat, with_cov=True, ldcov=ldcov, cov=cov)
     return coef, cov, rc, status, info
 
 
@@ -1049,24 +1005,8 @@ def fit_many_cov_dev(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef
                      stream=0):
     """fit_many_cov on torch device tensors: xdata, ydata, wdata (or None), coef and cov on the device, offsets on the host.
     -> (ierror, status (nbatch), info (nbatch, 10))."""
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    nbatch = offsets.size - 1
-    real32 = str(xdata.dtype).endswith("float32")
-    xmin, xmax, nodes = _grid(ndim, xmin, xmax, nodes, np.float32 if real32 else np.float64)
-    rp = _fp if real32 else _dp
-    ncol = int(np.prod(nodes[:max(int(ndim), 0)].astype(np.int64)))
-    if l1xdat is None:
-        l1xdat = xdata.shape[1] if xdata.dim() > 1 else 1
-    if ldcov is None:
-        ldcov = cov.stride(0) if cov.dim() > 1 else cov.shape[0]
-    status = np.full(max(nbatch, 1), -999, dtype=np.int32)
-    info = np.zeros((max(nbatch, 1), 10))
-    fn = lib().splpak_fit_many_cov_dev_f32 if real32 else lib().splpak_fit_many_cov_dev_f64
-    rc = _check(fn(ndim, nbatch, _p(offsets, _lp), xdata.data_ptr(), int(l1xdat), ydata.data_ptr(),
-                   None if wdata is None else wdata.data_ptr(), _p(xmin, rp), _p(xmax, rp), _p(nodes, _ip), float(xtrap),
-                   coef.data_ptr(), ncol if ldcoef is None else int(ldcoef), cov.data_ptr(), int(ldcov), _p(status, _ip), _p(info, _dp),
-                   C.c_void_p(stream)))
-    return rc, status, info
+    return _fit_many_on_dev("fit_many_cov", ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap, l1xdat, ldcoef, stream,
+                            cov=cov, ldcov=ldcov)[:3]
 
 
 def fit_many_lds_bytes(ndim, nodes) -> int:

@@ -1,11 +1,12 @@
-// Many small independent fits on one node grid (include/splpak_hip.h: splpak_fit_many_*): what the entries (fitmanyapi.hip)
-// and the kernel with its driver (fitmany.hip) share -- and the clipped fits (splpak_fit_many_clip_*: fitmanyclipapi.hip,
-// fitmanyclip.hip), which run the same fit inside a clipping loop, and the fits with their covariance (splpak_fit_many_cov_*:
-// fitmanycovapi.hip, fitmanycov.hip), which turn the band factor into the band of its inverse afterwards, and the robustly
-// clipped fits (splpak_fit_many_clip_mad_*: fitmanymadapi.hip, fitmanymad.hip): the loop on a median / MAD scale.
+// Many small independent fits on one node grid (include/splpak_hip.h: splpak_fit_many_* and the variants named after it):
+// what every variant's file (fitmany*.hip: its kernel, its launch and its entries) shares with the host side of a call
+// (fitmanyentry.hpp) and the device side of one fit (fitmanydev.hpp) -- the LDS map of a problem, the arguments and the result
+// block of a kernel, the workgroup shapes and the one timed launch.
 #pragma once
 #include "common.hpp"
 #include "../../include/splpak_hip.h"
+
+#include <type_traits>
 
 namespace splpak {
 
@@ -70,51 +71,10 @@ struct FitManyArgs {
     double xtrap;
     long long ldcoef;
     int compact;                   // coef of run r at r * ldcoef (host entries) instead of plist[r] * ldcoef
-    double *result;                // [nrun][FM_RESULT]
-};
-
-// The clipping loop around the fit (fitmanyclip.hip; the rule: include/splpak_hip.h, splpak_fit_many_clip_*).  Its result
-// block per problem: the FM_* slots of the LAST fit, FM_SPARE = the fits the problem ran, then the four clip numbers.
-enum { FMC_PASSES = FM_RESULT, FMC_REJECTED, FMC_COUNTED, FMC_V, FMC_RESULT };
-
-struct FitManyClipArgs {
-    FitManyArgs f;                 // f.result: [nrun][FMC_RESULT]
-    Grid gref;                     // the caller's order (build_grid without reorder): the residuals are evaluated in it
-    double klo2, khi2;             // klo^2, khi^2, formed once in double
-    int maxpass;
-};
-
-// The robust clipping loop (fitmanymad.hip; the rule: include/splpak_hip.h, splpak_fit_many_clip_mad_*).  Its result block per
-// problem: the FM_* slots of the LAST fit, FM_SPARE = the fits the problem ran, then the six clip numbers.
-enum { FMM_PASSES = FM_RESULT, FMM_OUT, FMM_COUNTED, FMM_S, FMM_MED, FMM_RETURNED, FMM_RESULT };
-
-struct FitManyMadArgs {
-    FitManyArgs f;                 // f.result: [nrun][FMM_RESULT]
-    Grid gref;                     // the caller's order, as FitManyClipArgs
-    double klo, khi;
-    int maxpass, regrow;
-    double *t;                     // the weighted residuals of a pass, one per point of the batch's span (the calling thread's scratch)
-    long long tbase;               // point i of the arrays (global index minus f.base) has t[i - tbase]
+    double *result;                // [nrun][FM_RESULT + what the variant's kernel adds]
 };
 
 extern thread_local long long t_fit_many_stats[8];
-
-// The device part on device arrays: one launch.  0 or SPLPAK_E_*; *seconds = the launch's device time.
-template <typename T>
-int fit_many_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, hipStream_t st, double *seconds);
-// .. with the selected inverse (fitmanycov.hip): cov of a problem at its coefficients' slot times ldcov, fit_many_cov_len words
-template <typename T>
-int fit_many_cov_launch(const FitManyArgs &a, const T *xdata, const T *ydata, const T *wdata, T *coef, T *cov, long long ldcov, hipStream_t st,
-                        double *seconds);
-// .. of the clipped fits: wout gets the weights each problem ended with (never the same array as wdata)
-template <typename T>
-int fit_many_clip_launch(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
-                         double *seconds);
-
-// .. of the robustly clipped fits
-template <typename T>
-int fit_many_mad_launch(const FitManyMadArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
-                        double *seconds);
 
 // workgroups of a batch launch: as many as fit on the device at once, or one per problem if that is fewer
 template <typename K>
@@ -127,6 +87,29 @@ unsigned many_blocks(K kernel, int threads, size_t lds, int nrun, int cus)
     }
     const long long most = (long long)cus * occ;
     return (unsigned)(nrun < 1 ? 1 : ((long long)nrun < most ? (long long)nrun : most));
+}
+
+// one shape of a batch launch: many_blocks workgroups of NT threads with `lds` bytes each, on st
+template <typename K, typename... A>
+hipError_t many_launch(K kernel, int NT, size_t lds, int nrun, int cus, hipStream_t st, unsigned *blocks, A... args)
+{
+    *blocks = many_blocks(kernel, NT, lds, nrun, cus);
+    hipLaunchKernelGGL(kernel, dim3(*blocks), dim3(NT), lds, st, args...);
+    return hipGetLastError();
+}
+
+// The workgroup shapes of the batch kernels: f(dimension D, threads NT), both as integral constants.  A grid of at most
+// FITMANY_SMALL_NCOL nodes has no work for more than one wave (a thread per band row): its workgroups are one wave, so that
+// four times as many problems are in flight on a CU.  The shape depends on the grid alone.
+template <typename F>
+auto many_shape_ladder(const FitManyShape &sh, F &&f)
+{
+    using std::integral_constant;
+    const bool small = sh.ncol <= FITMANY_SMALL_NCOL;
+    if (sh.ndim == 1 && small) return f(integral_constant<int, 1>{}, integral_constant<int, 64>{});
+    if (sh.ndim == 1) return f(integral_constant<int, 1>{}, integral_constant<int, FITMANY_THREADS>{});
+    if (small) return f(integral_constant<int, 2>{}, integral_constant<int, 64>{});
+    return f(integral_constant<int, 2>{}, integral_constant<int, FITMANY_THREADS>{});
 }
 
 // The one launch of a batch between two events: launch(cus, &blocks) enqueues it on st; st is synchronised once.  Fills

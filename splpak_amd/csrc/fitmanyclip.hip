@@ -14,10 +14,22 @@
 //                  the workgroup, ordered by the barrier fit_problem opens with.  `wout` is therefore a plain pointer here and the
 //                  first-weight decision is taken once, from `wdata`, before the loop.
 // r is formed twice per pass (the reject step needs v first).
-#include "fitmanydev.hpp"
+// Then the entries on host and device pointers: the call of splpak_fit_many_* (fitmanyentry.hpp) with the four clip conditions
+// in its second SPLPAK_E_BADARG group, `wout` beside the span and four clip numbers per problem.
 #include "fitmanyresid.hpp"
+#include "fitmanyentry.hpp"
 
 namespace splpak {
+
+// The result block of a problem: the FM_* slots of the LAST fit, FM_SPARE = the fits the problem ran, then the four clip numbers.
+enum { FMC_PASSES = FM_RESULT, FMC_REJECTED, FMC_COUNTED, FMC_V, FMC_RESULT };
+
+struct FitManyClipArgs {
+    FitManyArgs f;                 // f.result: [nrun][FMC_RESULT]
+    Grid gref;                     // the caller's order (build_grid without reorder): the residuals are evaluated in it
+    double klo2, khi2;             // klo^2, khi^2, formed once in double
+    int maxpass;
+};
 
 namespace {
 
@@ -40,12 +52,10 @@ fit_many_clip_kernel(FitManyClipArgs a, const T *__restrict__ xd, const T *__res
     const int tid = threadIdx.x, n = a.f.sh.ncol, l1xdat = a.f.l1xdat;
 
     for (int r = blockIdx.x; r < a.f.nrun; r += gridDim.x) {
-        const int k = a.f.plist[r];
-        const long long p0 = a.f.offsets[k] - a.f.base, np = a.f.offsets[k + 1] - a.f.offsets[k];
-        // the starting weights; the first-weight decision is taken here, from wdata, and never again
-        const bool weighted = wdata != nullptr && (double)wdata[p0] >= 0.0;
-        for (long long p = tid; p < np; p += NT) wout[p0 + p] = weighted ? wdata[p0 + p] : (T)1;
-        T *out = coef + (long long)(a.f.compact ? r : k) * a.f.ldcoef;
+        const Problem pr = problem_of(a.f, r);
+        const long long p0 = pr.p0, np = pr.np;
+        starting_weights<T, NT>(wdata, wout, p0, np);
+        T *out = coef + pr.slot() * a.f.ldcoef;
 
         FitOutcome o;
         int fits = 0, passes = 0;
@@ -56,15 +66,7 @@ fit_many_clip_kernel(FitManyClipArgs a, const T *__restrict__ xd, const T *__res
             ++fits;
             if (o.fail || j == a.maxpass) break;
 
-            // the coefficients as stored: rounded to T, in the caller's node order
-            for (int i = tid; i < n; i += NT) {
-                int in[D], refnode = 0;
-                node_of<D>(g, i, in);
-#pragma unroll
-                for (int d = 0; d < D; ++d) refnode += in[d] * g.refstride[d];
-                L.rho[refnode] = (double)(T)L.x[i];
-            }
-            __syncthreads();
+            coefficients_as_stored<D, T, NT>(g, L, n);
 
             // cnt and S over the points of non-zero weight
             double acc = 0.0;
@@ -121,8 +123,7 @@ fit_many_clip_kernel(FitManyClipArgs a, const T *__restrict__ xd, const T *__res
 
         if (tid == 0) {
             double *res = a.f.result + (long long)r * FMC_RESULT;
-            store_outcome(o, res);
-            res[FM_SPARE] = (double)fits;
+            store_loop_outcome(o, fits, res);
             res[FMC_PASSES] = (double)passes;
             res[FMC_REJECTED] = rejected;
             res[FMC_COUNTED] = o.rows;
@@ -131,34 +132,84 @@ fit_many_clip_kernel(FitManyClipArgs a, const T *__restrict__ xd, const T *__res
     }
 }
 
-template <int D, typename T, int NT>
-hipError_t launch_shape(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, int cus, hipStream_t st,
-                        unsigned *blocks)
-{
-    const size_t lds = (size_t)a.f.sh.bytes;
-    *blocks = many_blocks(fit_many_clip_kernel<D, T, NT>, NT, lds, a.f.nrun, cus);
-    hipLaunchKernelGGL((fit_many_clip_kernel<D, T, NT>), dim3(*blocks), dim3(NT), lds, st, a, xdata, ydata, wdata, wout, coef);
-    return hipGetLastError();
-}
-
-}  // namespace
-
+// the launch of fit_many_launch (fitmany.hip) on the loop's kernel: wout gets the weights each problem ended with
 template <typename T>
 int fit_many_clip_launch(const FitManyClipArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
                          double *seconds)
 {
-    const bool small = a.f.sh.ncol <= FITMANY_SMALL_NCOL;      // fit_many_launch's shapes
     return many_timed_launch(a.f.sh, st, seconds, [&](int cus, unsigned *blocks) {
-        if (a.f.g.ndim == 1 && small) return launch_shape<1, T, 64>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
-        if (a.f.g.ndim == 1) return launch_shape<1, T, FITMANY_THREADS>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
-        if (small) return launch_shape<2, T, 64>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
-        return launch_shape<2, T, FITMANY_THREADS>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
+        return many_shape_ladder(a.f.sh, [&](auto D, auto NT) {
+            return many_launch(fit_many_clip_kernel<D(), T, NT()>, NT(), (size_t)a.f.sh.bytes, a.f.nrun, cus, st, blocks, a, xdata, ydata, wdata,
+                               wout, coef);
+        });
     });
 }
 
-template int fit_many_clip_launch<double>(const FitManyClipArgs &, const double *, const double *, const double *, double *, double *,
-                                          hipStream_t, double *);
-template int fit_many_clip_launch<float>(const FitManyClipArgs &, const float *, const float *, const float *, float *, float *, hipStream_t,
-                                         double *);
+template <typename T>
+int32_t fit_many_clip_call(bool dev, const FitManyIn<T> &in, double klo, double khi, int32_t maxpass, T *wout, T *coef, int64_t ldcoef,
+                           int32_t *status, double *info, double *clip, void *stream)
+{
+    FitManyCall<T> c{in, dev, (hipStream_t)stream, coef, ldcoef, status, info, "a batch of clipped fits"};
+    c.has_wout = true;
+    c.wout = wout;
+    c.nextra = FMC_RESULT - FM_RESULT;
+    c.extra = clip;
+    c.refusal = clip_refusal(wout, in.wdata, maxpass, klo, khi);
+    return fit_many_entry(c, [&](const FitManyArgs &f, const T *xd, const T *yd, const T *wd, T *wo, T *cd, T *, long long, hipStream_t st,
+                                 double *seconds) {
+        FitManyClipArgs a{};
+        a.f = f;
+        // the residuals are evaluated on the grid in the caller's order (it was valid in the checks)
+        if (int r = fit_many_grid(in, false, a.gref)) return r;
+        a.klo2 = klo * klo;
+        a.khi2 = khi * khi;
+        a.maxpass = maxpass;
+        return fit_many_clip_launch<T>(a, xd, yd, wd, wo, cd, st, seconds);
+    });
+}
+
+}  // namespace
 
 }  // namespace splpak
+
+using namespace splpak;
+
+extern "C" {
+
+int32_t splpak_fit_many_clip_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata, int32_t l1xdat,
+                                 const double *ydata, const double *wdata, const double *xmin, const double *xmax, const int32_t *nodes,
+                                 double xtrap, double klo, double khi, int32_t maxpass, double *wout, double *coef, int64_t ldcoef,
+                                 int32_t *status, double *info, double *clip)
+{
+    return fit_many_clip_call<double>(false, {ndim, nbatch, offsets, xdata, l1xdat, ydata, wdata, xmin, xmax, nodes, xtrap}, klo, khi, maxpass, wout,
+                                      coef, ldcoef, status, info, clip, nullptr);
+}
+
+int32_t splpak_fit_many_clip_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xdata, int32_t l1xdat, const float *ydata,
+                                 const float *wdata, const float *xmin, const float *xmax, const int32_t *nodes, float xtrap, float klo,
+                                 float khi, int32_t maxpass, float *wout, float *coef, int64_t ldcoef, int32_t *status, double *info,
+                                 double *clip)
+{
+    return fit_many_clip_call<float>(false, {ndim, nbatch, offsets, xdata, l1xdat, ydata, wdata, xmin, xmax, nodes, xtrap}, klo, khi, maxpass, wout,
+                                     coef, ldcoef, status, info, clip, nullptr);
+}
+
+int32_t splpak_fit_many_clip_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata_dev, int32_t l1xdat,
+                                     const double *ydata_dev, const double *wdata_dev, const double *xmin, const double *xmax,
+                                     const int32_t *nodes, double xtrap, double klo, double khi, int32_t maxpass, double *wout_dev,
+                                     double *coef_dev, int64_t ldcoef, int32_t *status, double *info, double *clip, void *stream)
+{
+    return fit_many_clip_call<double>(true, {ndim, nbatch, offsets, xdata_dev, l1xdat, ydata_dev, wdata_dev, xmin, xmax, nodes, xtrap}, klo, khi,
+                                      maxpass, wout_dev, coef_dev, ldcoef, status, info, clip, stream);
+}
+
+int32_t splpak_fit_many_clip_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xdata_dev, int32_t l1xdat,
+                                     const float *ydata_dev, const float *wdata_dev, const float *xmin, const float *xmax,
+                                     const int32_t *nodes, float xtrap, float klo, float khi, int32_t maxpass, float *wout_dev,
+                                     float *coef_dev, int64_t ldcoef, int32_t *status, double *info, double *clip, void *stream)
+{
+    return fit_many_clip_call<float>(true, {ndim, nbatch, offsets, xdata_dev, l1xdat, ydata_dev, wdata_dev, xmin, xmax, nodes, xtrap}, klo, khi,
+                                     maxpass, wout_dev, coef_dev, ldcoef, status, info, clip, stream);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
-// One small fit on the LDS of its workgroup: the device side the batch kernels share (fitmany.hip: fit_many_kernel calls
-// fit_problem once per problem; fitmanyclip.hip: fit_many_clip_kernel calls it once per pass of its clipping loop).  The LDS
-// map is that of fitmany.hpp.
+// One small fit on the LDS of its workgroup: the device side the batch kernels share (fitmany.hip and fitmanycov.hip call
+// fit_problem once per problem; fitmanyclip.hip and fitmanymad.hip once per pass of their clipping loops), and problem_of,
+// with which each of them opens a problem.  The LDS map is that of fitmany.hpp.
 //
 // Phases of a problem, all on the workgroup's own LDS:
 //   1 assemble   the points are staged FITMANY_CHUNK at a time: a thread per point computes the window tables of basis.hpp,
@@ -316,6 +316,29 @@ __device__ inline void store_outcome(const FitOutcome &o, double *res)
     res[FM_RESERR] = sqrt(o.ssq);
     res[FM_STATUS] = o.fail ? 107.0 : 0.0;
     res[FM_SPARE] = 0.0;
+}
+
+// Run r of a launch: problem k of the batch, its np points from p0 on in the device arrays, and the slot of its coefficients
+// (and covariance): r where the problems that run lie back to back (the host entries), k otherwise.  (The slot is formed
+// where it is used, after the first-weight decision: formed with the rest, the kernels come out scheduled differently.)
+struct Problem {
+    int k;
+    long long p0, np;
+    int r, compact;
+    __device__ long long slot() const { return compact ? r : k; }
+};
+
+__device__ inline Problem problem_of(const FitManyArgs &a, int r)
+{
+    const int k = a.plist[r];
+    return {k, a.offsets[k] - a.base, a.offsets[k + 1] - a.offsets[k], r, a.compact};
+}
+
+// the first-weight decision of a problem (:581-588, :796): weights are given and the first of them is not negative
+template <typename T>
+__device__ inline bool first_weight_counts(const T *__restrict__ wd, long long p0)
+{
+    return wd != nullptr && (double)wd[p0] >= 0.0;
 }
 
 // 6 selected inverse (splpak_fit_many_cov_*): the entries of Z = N^-1 inside the band, by Takahashi's recurrence on the factor,

@@ -15,10 +15,25 @@
 //                  writer to other threads of the workgroup: global round trips inside the workgroup, ordered by barriers.
 //                  `wout` and a.t are therefore plain pointers here, and w0 is read again from `wdata` (never written).
 // No floating-point atomics; the selection's counts are integers.
+// Then the entries on host and device pointers: the call of splpak_fit_many_clip_* (any regrow is valid) with six clip numbers
+// per problem; the residuals' scratch is begun, and counted in the call's allocations, here.
 #include "fitmanyresid.hpp"
 #include "madselect.hpp"
+#include "fitmanyentry.hpp"
 
 namespace splpak {
+
+// The result block of a problem: the FM_* slots of the LAST fit, FM_SPARE = the fits the problem ran, then the six clip numbers.
+enum { FMM_PASSES = FM_RESULT, FMM_OUT, FMM_COUNTED, FMM_S, FMM_MED, FMM_RETURNED, FMM_RESULT };
+
+struct FitManyMadArgs {
+    FitManyArgs f;                 // f.result: [nrun][FMM_RESULT]
+    Grid gref;                     // the caller's order (build_grid without reorder): the residuals are evaluated in it
+    double klo, khi;
+    int maxpass, regrow;
+    double *t;                     // the weighted residuals of a pass, one per point of the batch's span (the calling thread's scratch)
+    long long tbase;               // point i of the arrays (global index minus f.base) has t[i - tbase]
+};
 
 namespace {
 
@@ -45,12 +60,10 @@ fit_many_mad_kernel(FitManyMadArgs a, const T *__restrict__ xd, const T *__restr
     unsigned *sel = reinterpret_cast<unsigned *>(L.stage);
 
     for (int r = blockIdx.x; r < a.f.nrun; r += gridDim.x) {
-        const int k = a.f.plist[r];
-        const long long p0 = a.f.offsets[k] - a.f.base, np = a.f.offsets[k + 1] - a.f.offsets[k];
-        // the starting weights; the first-weight decision is taken here, from wdata, and never again
-        const bool weighted = wdata != nullptr && (double)wdata[p0] >= 0.0;
-        for (long long p = tid; p < np; p += NT) wout[p0 + p] = weighted ? wdata[p0 + p] : (T)1;
-        T *out = coef + (long long)(a.f.compact ? r : k) * a.f.ldcoef;
+        const Problem pr = problem_of(a.f, r);
+        const long long p0 = pr.p0, np = pr.np;
+        const bool weighted = starting_weights<T, NT>(wdata, wout, p0, np);
+        T *out = coef + pr.slot() * a.f.ldcoef;
         double *tp = a.t + (p0 - a.tbase);
 
         FitOutcome o;
@@ -62,15 +75,7 @@ fit_many_mad_kernel(FitManyMadArgs a, const T *__restrict__ xd, const T *__restr
             ++fits;
             if (o.fail || j == a.maxpass) break;
 
-            // the coefficients as stored: rounded to T, in the caller's node order
-            for (int i = tid; i < n; i += NT) {
-                int in[D], refnode = 0;
-                node_of<D>(g, i, in);
-#pragma unroll
-                for (int d = 0; d < D; ++d) refnode += in[d] * g.refstride[d];
-                L.rho[refnode] = (double)(T)L.x[i];
-            }
-            __syncthreads();
+            coefficients_as_stored<D, T, NT>(g, L, n);
 
             // t of every point with w0 != 0 (a point of weight 0 is selected out, never multiplied), and the points counted
             int cnt_mine = 0;
@@ -125,8 +130,7 @@ fit_many_mad_kernel(FitManyMadArgs a, const T *__restrict__ xd, const T *__restr
 
         if (tid == 0) {
             double *res = a.f.result + (long long)r * FMM_RESULT;
-            store_outcome(o, res);
-            res[FM_SPARE] = (double)fits;
+            store_loop_outcome(o, fits, res);
             res[FMM_PASSES] = (double)passes;
             res[FMM_OUT] = nout;
             res[FMM_COUNTED] = o.rows;
@@ -137,34 +141,96 @@ fit_many_mad_kernel(FitManyMadArgs a, const T *__restrict__ xd, const T *__restr
     }
 }
 
-template <int D, typename T, int NT>
-hipError_t launch_shape(const FitManyMadArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, int cus, hipStream_t st,
-                        unsigned *blocks)
-{
-    const size_t lds = (size_t)a.f.sh.bytes;
-    *blocks = many_blocks(fit_many_mad_kernel<D, T, NT>, NT, lds, a.f.nrun, cus);
-    hipLaunchKernelGGL((fit_many_mad_kernel<D, T, NT>), dim3(*blocks), dim3(NT), lds, st, a, xdata, ydata, wdata, wout, coef);
-    return hipGetLastError();
-}
-
-}  // namespace
-
+// the launch of fit_many_launch (fitmany.hip) on the loop's kernel: wout gets the weights each problem ended with
 template <typename T>
 int fit_many_mad_launch(const FitManyMadArgs &a, const T *xdata, const T *ydata, const T *wdata, T *wout, T *coef, hipStream_t st,
                         double *seconds)
 {
-    const bool small = a.f.sh.ncol <= FITMANY_SMALL_NCOL;      // fit_many_launch's shapes
     return many_timed_launch(a.f.sh, st, seconds, [&](int cus, unsigned *blocks) {
-        if (a.f.g.ndim == 1 && small) return launch_shape<1, T, 64>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
-        if (a.f.g.ndim == 1) return launch_shape<1, T, FITMANY_THREADS>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
-        if (small) return launch_shape<2, T, 64>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
-        return launch_shape<2, T, FITMANY_THREADS>(a, xdata, ydata, wdata, wout, coef, cus, st, blocks);
+        return many_shape_ladder(a.f.sh, [&](auto D, auto NT) {
+            return many_launch(fit_many_mad_kernel<D(), T, NT()>, NT(), (size_t)a.f.sh.bytes, a.f.nrun, cus, st, blocks, a, xdata, ydata, wdata,
+                               wout, coef);
+        });
     });
 }
 
-template int fit_many_mad_launch<double>(const FitManyMadArgs &, const double *, const double *, const double *, double *, double *,
-                                         hipStream_t, double *);
-template int fit_many_mad_launch<float>(const FitManyMadArgs &, const float *, const float *, const float *, float *, float *, hipStream_t,
-                                        double *);
+template <typename T>
+int32_t fit_many_mad_call(bool dev, const FitManyIn<T> &in, double klo, double khi, int32_t maxpass, int32_t regrow, T *wout, T *coef,
+                          int64_t ldcoef, int32_t *status, double *info, double *clip, void *stream)
+{
+    FitManyCall<T> c{in, dev, (hipStream_t)stream, coef, ldcoef, status, info, "a batch of clipped fits"};
+    c.has_wout = true;
+    c.wout = wout;
+    c.nextra = FMM_RESULT - FM_RESULT;
+    c.extra = clip;
+    c.refusal = clip_refusal(wout, in.wdata, maxpass, klo, khi);
+    return fit_many_entry(c, [&](const FitManyArgs &f, const T *xd, const T *yd, const T *wd, T *wo, T *cd, T *, long long, hipStream_t st,
+                                 double *seconds) {
+        // the residuals of the span's points in the calling thread's scratch, held to the end of the launch (which waits for it)
+        const ManySpan sp = many_span(in.offsets, in.nbatch);
+        const size_t need_t[1] = {sizeof(double) * (size_t)sp.n};
+        const long long allocs_before = t_fit_many_mad_t.allocs;
+        const ScratchUse<1> use_t{t_fit_many_mad_t, st};
+        const hipError_t e = scratch_begin(t_fit_many_mad_t, need_t, st);
+        t_fit_many_stats[6] += t_fit_many_mad_t.allocs - allocs_before;
+        if (e != hipSuccess) return (int)many_status(e, c.what, 0);
+        FitManyMadArgs a{};
+        a.f = f;
+        if (int r = fit_many_grid(in, false, a.gref)) return r;
+        a.klo = klo;
+        a.khi = khi;
+        a.maxpass = maxpass;
+        a.regrow = regrow != 0;
+        a.t = t_fit_many_mad_t.as<double>(0);
+        a.tbase = sp.lo - f.base;
+        return fit_many_mad_launch<T>(a, xd, yd, wd, wo, cd, st, seconds);
+    });
+}
+
+}  // namespace
 
 }  // namespace splpak
+
+using namespace splpak;
+
+extern "C" {
+
+int32_t splpak_fit_many_clip_mad_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata, int32_t l1xdat,
+                                     const double *ydata, const double *wdata, const double *xmin, const double *xmax, const int32_t *nodes,
+                                     double xtrap, double klo, double khi, int32_t maxpass, int32_t regrow, double *wout, double *coef,
+                                     int64_t ldcoef, int32_t *status, double *info, double *clip)
+{
+    return fit_many_mad_call<double>(false, {ndim, nbatch, offsets, xdata, l1xdat, ydata, wdata, xmin, xmax, nodes, xtrap}, klo, khi, maxpass, regrow,
+                                     wout, coef, ldcoef, status, info, clip, nullptr);
+}
+
+int32_t splpak_fit_many_clip_mad_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xdata, int32_t l1xdat,
+                                     const float *ydata, const float *wdata, const float *xmin, const float *xmax, const int32_t *nodes,
+                                     float xtrap, float klo, float khi, int32_t maxpass, int32_t regrow, float *wout, float *coef, int64_t ldcoef,
+                                     int32_t *status, double *info, double *clip)
+{
+    return fit_many_mad_call<float>(false, {ndim, nbatch, offsets, xdata, l1xdat, ydata, wdata, xmin, xmax, nodes, xtrap}, klo, khi, maxpass, regrow,
+                                    wout, coef, ldcoef, status, info, clip, nullptr);
+}
+
+int32_t splpak_fit_many_clip_mad_dev_f64(int32_t ndim, int32_t nbatch, const int64_t *offsets, const double *xdata_dev, int32_t l1xdat,
+                                         const double *ydata_dev, const double *wdata_dev, const double *xmin, const double *xmax,
+                                         const int32_t *nodes, double xtrap, double klo, double khi, int32_t maxpass, int32_t regrow,
+                                         double *wout_dev, double *coef_dev, int64_t ldcoef, int32_t *status, double *info, double *clip,
+                                         void *stream)
+{
+    return fit_many_mad_call<double>(true, {ndim, nbatch, offsets, xdata_dev, l1xdat, ydata_dev, wdata_dev, xmin, xmax, nodes, xtrap}, klo, khi,
+                                     maxpass, regrow, wout_dev, coef_dev, ldcoef, status, info, clip, stream);
+}
+
+int32_t splpak_fit_many_clip_mad_dev_f32(int32_t ndim, int32_t nbatch, const int64_t *offsets, const float *xdata_dev, int32_t l1xdat,
+                                         const float *ydata_dev, const float *wdata_dev, const float *xmin, const float *xmax,
+                                         const int32_t *nodes, float xtrap, float klo, float khi, int32_t maxpass, int32_t regrow,
+                                         float *wout_dev, float *coef_dev, int64_t ldcoef, int32_t *status, double *info, double *clip,
+                                         void *stream)
+{
+    return fit_many_mad_call<float>(true, {ndim, nbatch, offsets, xdata_dev, l1xdat, ydata_dev, wdata_dev, xmin, xmax, nodes, xtrap}, klo, khi,
+                                    maxpass, regrow, wout_dev, coef_dev, ldcoef, status, info, clip, stream);
+}
+
+}  // extern "C"

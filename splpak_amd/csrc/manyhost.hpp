@@ -1,5 +1,5 @@
-// The host layer the batch families share (splpak_fit_many_*, splpak_eval_many_*, splpak_residuals_many_*; their entries:
-// fitmanyapi.hip, evalmanyapi.hip): the span of a batch's points, the copies a host entry stages through memory of the call,
+// The host layer the batch families share (splpak_fit_many_* and its variants through fitmanyentry.hpp; splpak_eval_many_*,
+// splpak_residuals_many_* and splpak_mad_many_* in evalmanyapi.hip): the span of a batch's points, the copies a host entry stages through memory of the call,
 // the calling thread's device scratch for the tables of a call, and the status after the device part.
 #pragma once
 #include "callstage.hpp"

@@ -513,6 +513,33 @@ module splpak_module
         end select
     end subroutine report_fit
 
+    !> .true., with ierror = -4 and `mess` reported, where an object cannot take the batch calls (one launch on one GPU):
+    !! under set_host or set_gpus(n > 1).  The caller returns at once.
+    logical function batch_refused(me,mess,ierror)
+        class(splpak_type),intent(in) :: me
+        character(len=*),intent(in) :: mess
+        integer,intent(inout) :: ierror
+        batch_refused = me%host .or. me%ngpus > 1
+        if (batch_refused) then
+            ierror = -4
+            call report(ierror,mess)
+        end if
+    end function batch_refused
+
+    !> The end of a batch call: ierror = rc, a fit's status reported as `initialize` reports it, a failure of the library
+    !! under the procedure's name.
+    subroutine report_batch(rc,who,ierror)
+        integer(c_int32_t),intent(in) :: rc
+        character(len=*),intent(in) :: who
+        integer,intent(out) :: ierror
+        ierror = int(rc)
+        if (rc > 0) then
+            call report_fit(ierror)
+        else if (rc < 0) then
+            call report_library_failure(ierror,who)
+        end if
+    end subroutine report_batch
+
     !> Unweighted fit; same arguments as the reference's splcc (:421-422).
     subroutine splcc(me,ndim,xdata,l1xdat,ydata,ndata,xmin,xmax,nodes, &
                      xtrap,coef,ncf,work,nwrk,ierror)
@@ -841,23 +868,14 @@ module splpak_module
         ierror = -4
         call report(ierror,' initialize_many - not available in the -DREAL128 build: call initialize for every problem')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' initialize_many - not available under set_host or set_gpus(n > 1): '// &
-                               'call initialize for every problem')
-            return
-        end if
+        if (batch_refused(me,' initialize_many - not available under set_host or set_gpus(n > 1): '// &
+                             'call initialize for every problem',ierror)) return
         pw = c_null_ptr
         if (present(wdata)) pw = c_loc(wdata)
         rc = c_fit_many(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
                         c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, c_loc(coef), int(ldcoef,c_int64_t), &
                         c_loc(ierrors), c_null_ptr)
-        ierror = int(rc)
-        if (rc > 0) then
-            call report_fit(ierror)
-        else if (rc < 0) then
-            call report_library_failure(ierror,'initialize_many')
-        end if
+        call report_batch(rc,'initialize_many',ierror)
 #endif
     end subroutine splpak_fit_many
 
@@ -891,11 +909,7 @@ module splpak_module
         ierror = -4
         call report(ierror,' initialize_many_clipped - not available in the -DREAL128 build')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' initialize_many_clipped - not available under set_host or set_gpus(n > 1)')
-            return
-        end if
+        if (batch_refused(me,' initialize_many_clipped - not available under set_host or set_gpus(n > 1)',ierror)) return
         pw = c_null_ptr
         if (present(wdata)) pw = c_loc(wdata)
         pc = c_null_ptr
@@ -903,12 +917,7 @@ module splpak_module
         rc = c_fit_many_clip(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
                              c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, klo, khi, int(maxpass,c_int32_t), &
                              c_loc(wout), c_loc(coef), int(ldcoef,c_int64_t), c_loc(ierrors), c_null_ptr, pc)
-        ierror = int(rc)
-        if (rc > 0) then
-            call report_fit(ierror)
-        else if (rc < 0) then
-            call report_library_failure(ierror,'initialize_many_clipped')
-        end if
+        call report_batch(rc,'initialize_many_clipped',ierror)
 #endif
     end subroutine splpak_fit_many_clipped
 
@@ -941,11 +950,7 @@ module splpak_module
         ierror = -4
         call report(ierror,' initialize_many_robust - not available in the -DREAL128 build')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' initialize_many_robust - not available under set_host or set_gpus(n > 1)')
-            return
-        end if
+        if (batch_refused(me,' initialize_many_robust - not available under set_host or set_gpus(n > 1)',ierror)) return
         pw = c_null_ptr
         if (present(wdata)) pw = c_loc(wdata)
         pc = c_null_ptr
@@ -953,12 +958,7 @@ module splpak_module
         rc = c_fit_many_clip_mad(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
                                  c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, klo, khi, int(maxpass,c_int32_t), &
                                  int(regrow,c_int32_t), c_loc(wout), c_loc(coef), int(ldcoef,c_int64_t), c_loc(ierrors), c_null_ptr, pc)
-        ierror = int(rc)
-        if (rc > 0) then
-            call report_fit(ierror)
-        else if (rc < 0) then
-            call report_library_failure(ierror,'initialize_many_robust')
-        end if
+        call report_batch(rc,'initialize_many_robust',ierror)
 #endif
     end subroutine splpak_fit_many_robust
 
@@ -980,11 +980,7 @@ module splpak_module
         ierror = -4
         call report(ierror,' mad_each - not available in the -DREAL128 build')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' mad_each - not available under set_host or set_gpus(n > 1)')
-            return
-        end if
+        if (batch_refused(me,' mad_each - not available under set_host or set_gpus(n > 1)',ierror)) return
         pw = c_null_ptr
         if (present(wsel)) pw = c_loc(wsel)
         rc = c_mad_many(int(nbatch,c_int32_t), c_loc(offsets), c_loc(values), pw, c_loc(stats))
@@ -1017,12 +1013,8 @@ module splpak_module
         ierror = -4
         call report(ierror,' evaluate_each - not available in the -DREAL128 build: call evaluate_many for every problem')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' evaluate_each - not available under set_host or set_gpus(n > 1): '// &
-                               'call evaluate_many for every problem')
-            return
-        end if
+        if (batch_refused(me,' evaluate_each - not available under set_host or set_gpus(n > 1): '// &
+                             'call evaluate_many for every problem',ierror)) return
         pd = c_null_ptr
         if (present(nderiv)) pd = c_loc(nderiv)
         rc = c_eval_many(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(x), int(ldx,c_int32_t), pd, c_loc(coef), &
@@ -1067,22 +1059,13 @@ module splpak_module
         ierror = -4
         call report(ierror,' initialize_many_cov - not available in the -DREAL128 build')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' initialize_many_cov - not available under set_host or set_gpus(n > 1)')
-            return
-        end if
+        if (batch_refused(me,' initialize_many_cov - not available under set_host or set_gpus(n > 1)',ierror)) return
         pw = c_null_ptr
         if (present(wdata)) pw = c_loc(wdata)
         rc = c_fit_many_cov(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
                             c_loc(ydata), pw, c_loc(xmin), c_loc(xmax), c_loc(nodes), xtrap, c_loc(coef), int(ldcoef,c_int64_t), &
                             c_loc(cov), int(ldcov,c_int64_t), c_loc(ierrors), c_null_ptr)
-        ierror = int(rc)
-        if (rc > 0) then
-            call report_fit(ierror)
-        else if (rc < 0) then
-            call report_library_failure(ierror,'initialize_many_cov')
-        end if
+        call report_batch(rc,'initialize_many_cov',ierror)
 #endif
     end subroutine splpak_fit_many_cov
 
@@ -1107,11 +1090,7 @@ module splpak_module
         ierror = -4
         call report(ierror,' variance_each - not available in the -DREAL128 build')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' variance_each - not available under set_host or set_gpus(n > 1)')
-            return
-        end if
+        if (batch_refused(me,' variance_each - not available under set_host or set_gpus(n > 1)',ierror)) return
         pd = c_null_ptr
         if (present(nderiv)) pd = c_loc(nderiv)
         rc = c_eval_many_var(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(x), int(ldx,c_int32_t), pd, &
@@ -1155,22 +1134,13 @@ module splpak_module
         ierror = -4
         call report(ierror,' residuals_each - not available in the -DREAL128 build')
 #else
-        if (me%host .or. me%ngpus > 1) then
-            ierror = -4
-            call report(ierror,' residuals_each - not available under set_host or set_gpus(n > 1)')
-            return
-        end if
+        if (batch_refused(me,' residuals_each - not available under set_host or set_gpus(n > 1)',ierror)) return
         pw = c_null_ptr
         if (present(wdata)) pw = c_loc(wdata)
         rc = c_residuals_many(int(ndim,c_int32_t), int(nbatch,c_int32_t), c_loc(offsets), c_loc(xdata), int(l1xdat,c_int32_t), &
                               c_loc(ydata), pw, c_loc(coef), int(ldcoef,c_int64_t), c_loc(xmin), c_loc(xmax), c_loc(nodes), &
                               c_loc(resid), c_loc(stats))
-        ierror = int(rc)
-        if (rc > 0) then
-            call report_fit(ierror)
-        else if (rc < 0) then
-            call report_library_failure(ierror,'residuals_each')
-        end if
+        call report_batch(rc,'residuals_each',ierror)
 #endif
     end subroutine splpak_residuals_each
 

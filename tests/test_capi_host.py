@@ -195,3 +195,31 @@ def test_rccl_library_missing_is_a_clean_error():
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-400:]
     assert "ERR" in r.stdout and "-5" in r.stdout and "librccl" in r.stdout
+
+
+FIT_MANY_SIGNATURES = {
+    "fit_many": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, real32=False, ldcoef=None, coef=None, l1xdat=None)",
+    "fit_many_dev": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, xtrap=0.0, l1xdat=None, ldcoef=None, stream=0)",
+    "fit_many_clip": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, real32=False, "
+                     "ldcoef=None, coef=None, l1xdat=None, wout=None)",
+    "fit_many_clip_dev": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, wout, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, "
+                         "l1xdat=None, ldcoef=None, stream=0)",
+    "fit_many_clip_mad": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, regrow=0, "
+                         "real32=False, ldcoef=None, coef=None, l1xdat=None, wout=None)",
+    "fit_many_clip_mad_dev": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, wout, xtrap=0.0, klo=3.0, khi=3.0, maxpass=5, "
+                             "regrow=0, l1xdat=None, ldcoef=None, stream=0)",
+    "fit_many_cov": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, xtrap=0.0, real32=False, ldcoef=None, coef=None, l1xdat=None, "
+                    "ldcov=None, cov=None)",
+    "fit_many_cov_dev": "(ndim, offsets, xdata, ydata, wdata, xmin, xmax, nodes, coef, cov, xtrap=0.0, l1xdat=None, ldcoef=None, ldcov=None, "
+                        "stream=0)",
+    "fit_many_cov_len": "(ndim, nodes) -> 'int'",
+    "fit_many_lds_bytes": "(ndim, nodes) -> 'int'",
+}
+
+
+@pytest.mark.parametrize("name", sorted(FIT_MANY_SIGNATURES))
+def test_fit_many_wrappers_keep_their_signatures(name):
+    """The batch-fit wrappers share private cores; callers pass their arguments by position, so the parameter order and the
+    defaults of every public one are pinned here, letter for letter."""
+    import inspect
+    assert str(inspect.signature(getattr(capi, name))) == FIT_MANY_SIGNATURES[name]
