@@ -69,7 +69,20 @@ extern "C" {
  * |dx|/|x| is below 1e-11 (2 steps at 64^3: corrections 9e-5, 1e-8, then an estimated 2e-12); a solve that is still contracting after the nominal
  * number of steps continues (up to 30), and one that then still misses 1e-10, or whose corrections
  * stop contracting while above 1e-8, is reported as 107 ("suprls failure") with an explanatory
- * splpak_last_error_message -- never as a silent success. */
+ * splpak_last_error_message -- never as a silent success.
+ * Data that is not finite.  A NaN or a +-Inf in ydata, or in a weight that is counted -- not the 0 of a point that is skipped,
+ * not a negative first weight (which means "no weights"; a NaN first weight is not negative: the weights count) --, ends that
+ * fit in 107 with a message, by the pivot test of the factorisation or by the refinement rule, whose corrections are then not
+ * finite: never in 0.  The reference returns 0 and coefficients that are all NaN for such data.  `coef` is zeroed where the
+ * factorisation refused and holds the unrefined values, which are not finite, otherwise -- for the point fit; where an entry
+ * below says what its own 107 leaves in `coef` (the refits, the grid fits, the batch fits), that statement holds.  The plan
+ * (the cached one of the one-shot entries too) stays usable: the next fit has the bits it has on a fresh plan.  This holds for
+ * splpak_fit_f64 / _f32, splpak_plan_fit_dev on every solver route, splpak_plan_refit_dev and splpak_refit_* (a refit's 107
+ * leaves the fit resident), splpak_fit_multi_f64 (every rank ends; the message is that of rank 0), splpak_fit_grid_* and
+ * splpak_fit_grid_weighted_* (a value under a non-zero weight; a weight that is not finite is SPLPAK_E_BADARG there), and per
+ * problem for splpak_fit_many_* and splpak_fit_many_cov_* (status 107, its coef and cov zeroed, every other problem of the
+ * batch the bits it has without it).  Coordinates that are not finite are not covered; the clipping entries and
+ * splpak_mad_many_* keep their own statement (unspecified). */
 int32_t splpak_fit_f64(int32_t ndim, const double *xdata, int32_t l1xdat,
                        const double *ydata, const double *wdata, int64_t ndata,
                        const double *xmin, const double *xmax, const int32_t *nodes,

@@ -381,11 +381,11 @@ void rank_main(MRank *me)
     (void)hipSetDevice(me->dev);
     double *coef = me->r == 0 ? me->mp->coef0 : me->coef;
     me->rc = splpak_plan_fit_dev(me->p, me->x, me->l1, me->y, me->w, me->ndata, coef, me->st, me->info);
-    if (me->rc < 0) {
+    if (me->rc != 0) {          // (the message is this thread's: the caller's thread gets it from splpak_mplan_fit_dev)
         char buf[400];
         splpak_last_error_message(buf, sizeof buf);
         me->err = buf;
-        me->mp->abort.store(1);
+        if (me->rc < 0) me->mp->abort.store(1);
     }
 }
 
@@ -672,7 +672,7 @@ int32_t splpak_mplan_fit_dev(splpak_mplan *mp, const double *const *xdata_dev, i
     int rc = 0;
     for (MRank *m : mp->ranks) {
         if (m->rc < 0 && (rc >= 0 || !m->err.empty())) { rc = m->rc; if (!m->err.empty()) set_error(m->err); }
-        else if (rc == 0 && m->rc > 0) rc = m->rc;
+        else if (rc == 0 && m->rc > 0) { rc = m->rc; if (!m->err.empty()) set_error(m->err); }      // (107: with its message)
     }
     if (info) std::memcpy(info, mp->ranks[0]->info, sizeof(double) * 10);
     return rc;

@@ -179,7 +179,7 @@ residuals_many_kernel(Grid g, int nbatch, const long long *__restrict__ offsets,
     const NDeriv nd{};
     for (int k = blockIdx.x; k < nbatch; k += gridDim.x) {
         const long long p0 = offsets[k] - base, np = offsets[k + 1] - offsets[k];
-        const bool weighted = wd != nullptr && np > 0 && (double)wd[p0] >= 0.0;      // (fitmany.hip: a negative first weight = no weights)
+        const bool weighted = wd != nullptr && np > 0 && !((double)wd[p0] < 0.0);    // (fitmany.hip: a negative first weight = no weights; a NaN is not negative)
         const T *cf = coef + (long long)k * ldcoef;
         double acc = 0.0, mx = -1.0;
         long long mp = LLONG_MAX;

@@ -335,10 +335,11 @@ __device__ inline Problem problem_of(const FitManyArgs &a, int r)
 }
 
 // the first-weight decision of a problem (:581-588, :796): weights are given and the first of them is not negative
+// (a NaN is not negative: the weights count, and the problem ends in 107 instead of being fitted without them)
 template <typename T>
 __device__ inline bool first_weight_counts(const T *__restrict__ wd, long long p0)
 {
-    return wd != nullptr && (double)wd[p0] >= 0.0;
+    return wd != nullptr && !((double)wd[p0] < 0.0);
 }
 
 // 6 selected inverse (splpak_fit_many_cov_*): the entries of Z = N^-1 inside the band, by Takahashi's recurrence on the factor,

@@ -243,7 +243,7 @@ int32_t splpak_fit_f32(int32_t ndim, const float *xdata, int32_t l1xdat, const f
     if (have) {
         X.assign(xdata, xdata + (size_t)ndata * l1xdat);
         Y.assign(ydata, ydata + (size_t)ndata);
-        if (wdata && wdata[0] >= 0.0f) W.assign(wdata, wdata + (size_t)ndata);
+        if (wdata && !(wdata[0] < 0.0f)) W.assign(wdata, wdata + (size_t)ndata);      // (as splpak_fit_f64: a NaN is not negative)
         Cf.resize((size_t)ncol);
         if (hist_out) H.resize((size_t)ncol);
     }

@@ -535,7 +535,7 @@ bj_build_kernel(Grid g, BjGeom bg, MassBands mb, const double *__restrict__ ctab
 template <typename T>
 __global__ void __launch_bounds__(256)
 bj_apply_kernel(Grid g, BjGeom bg, const T *__restrict__ dinv, const T *__restrict__ dinvt, const double *__restrict__ v,
-                double *__restrict__ z)
+                double *__restrict__ z, double unscale)
 {
     __shared__ double vb[256], ub[256];
     const int b = blockIdx.x, i = threadIdx.x, wave = i >> 6;
@@ -556,7 +556,15 @@ bj_apply_kernel(Grid g, BjGeom bg, const T *__restrict__ dinv, const T *__restri
         a0 = fma((double)M[(size_t)j * 256 + i], ub[j], a0);
         a1 = fma((double)M[(size_t)(j + 1) * 256 + i], ub[j + 1], a1);
     }
-    if (node >= 0) z[node] += a0 + a1;
+    if (node >= 0) z[node] += unscale * (a0 + a1);
+}
+
+// (float)(scale x), kept inside the range of a float: the identity padding of a box does not follow the weights (1 x scale may lie
+// beyond it; its rows meet zeros of v only, and Inf x 0 would be NaN).  A NaN stays a NaN.
+__device__ __forceinline__ float bj_narrow(double x, double scale)
+{
+    const double big = 3.4028234663852886e38, v = scale * x;
+    return v != v ? (float)v : (float)fmin(fmax(v, -big), big);
 }
 
 // The apply from ONE single-precision copy of L^-1 (round 6, second form): the ten 64 x 64 blocks of its lower triangle, packed block
@@ -565,18 +573,18 @@ bj_apply_kernel(Grid g, BjGeom bg, const T *__restrict__ dinv, const T *__restri
 // products read from the straight and the transposed copy (the pass is bound by these bytes).  Sums in a fixed order.
 constexpr int BJ_LD = 65;          // floats per LDS row of a block (odd: the row-wise reads of the first product spread over the banks)
 __global__ void __launch_bounds__(256)
-bj_pack_kernel(long long nblk, const double *__restrict__ dinv, float *__restrict__ pk)
+bj_pack_kernel(long long nblk, const double *__restrict__ dinv, float *__restrict__ pk, double scale)
 {   // pk[box][blk(I, J) = I (I + 1) / 2 + J][i][j] = Linv[64 I + i][64 J + j]   (dinv: row-major Linv)
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= nblk * 40960) return;
     const long long b = e / 40960;
     const int r = (int)(e % 40960), blk = r >> 12, i = (r >> 6) & 63, j = r & 63;
     const int I = blk < 1 ? 0 : (blk < 3 ? 1 : (blk < 6 ? 2 : 3)), J = blk - I * (I + 1) / 2;
-    pk[e] = (float)dinv[b * 65536 + (long long)(64 * I + i) * 256 + 64 * J + j];
+    pk[e] = bj_narrow(dinv[b * 65536 + (long long)(64 * I + i) * 256 + 64 * J + j], scale);
 }
 
 __global__ void __launch_bounds__(256)
-bj_apply_packed_kernel(Grid g, BjGeom bg, const float *__restrict__ pk, const double *__restrict__ v, double *__restrict__ z)
+bj_apply_packed_kernel(Grid g, BjGeom bg, const float *__restrict__ pk, const double *__restrict__ v, double *__restrict__ z, double unscale)
 {
     __shared__ float sblk[4 * 64 * BJ_LD];
     __shared__ double vb[256], ub[64], red[256];
@@ -625,16 +633,20 @@ bj_apply_packed_kernel(Grid g, BjGeom bg, const float *__restrict__ pk, const do
         if (tid < 64) zs[64 * J + tid] = ((red[tid] + red[64 + tid]) + red[128 + tid]) + red[192 + tid];
         __syncthreads();
     }
-    if (node >= 0) z[node] += zs[tid];
+    if (node >= 0) z[node] += unscale * zs[tid];
 }
 
 // single-precision copies of the box inverses for the apply (a preconditioner: its rounding changes nothing the iteration converges
-// to; half the bytes of a pass that is bound by reading them -- 0.48 -> 0.25 ms per iteration at 32^4)
+// to; half the bytes of a pass that is bound by reading them -- 0.48 -> 0.25 ms per iteration at 32^4).
+// `scale`, a power of two near the square root of a diagonal entry of N (PcgState::bj_scale), brings L^-1 to order 1 before it is
+// narrowed: the entries follow the weights (x 1 / w), and those of weights below 2^-134 or above 2^128 left the range of a float --
+// Inf in every z, or boxes of zeros.  The apply multiplies by scale^-2; both are exact, so the bits are those of scale = 1
+// wherever that was in range.
 __global__ void __launch_bounds__(256)
-to_f32_kernel(long long n, const double *__restrict__ a, const double *__restrict__ b, float *__restrict__ fa, float *__restrict__ fb)
+to_f32_kernel(long long n, const double *__restrict__ a, const double *__restrict__ b, float *__restrict__ fa, float *__restrict__ fb, double scale)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { fa[i] = (float)a[i]; fb[i] = (float)b[i]; }
+    if (i < n) { fa[i] = bj_narrow(a[i], scale); fb[i] = bj_narrow(b[i], scale); }
 }
 
 // out[0] = sum of squares of v[0 .. n) with n read from the device (n = offset[ncell]): partial sums by block, then one block adds them
@@ -672,6 +684,7 @@ struct PcgState {
     BjGeom bg{};
     double *bj_blocks = nullptr, *bj_inv16 = nullptr, *bj_dinv = nullptr, *bj_dinvt = nullptr, *bj_scal = nullptr;
     float *bj_dinv32 = nullptr, *bj_dinvt32 = nullptr;     // single-precision copies for the apply (NULL: the f64 ones)
+    double bj_scale = 1.0;                                 // the power of two the single-precision copies are multiplied by (to_f32_kernel)
     float *bj_pk32 = nullptr;                              // the packed single-precision lower triangle of L^-1 (the default apply)
     void *bj_jobs = nullptr;
     int *bj_info = nullptr;
@@ -947,14 +960,20 @@ hipError_t pcg_prepare(splpak_plan *p, PcgState *s, double sumw2, bool smooth, b
         }
         e = block_chol_run(s->bj_jobs, s->bg.nb, s->bj_info, s->bj_scal, st);
         if (e != hipSuccess) return e;
+        {   // 2^(e / 2) with 2^e the mean of w^2 per column, the magnitude of a diagonal entry of N (1 where that is no number)
+            const double mean = sumw2 / (double)g.ncol;
+            int ex = 0;
+            s->bj_scale = 1.0;
+            if (mean > 0.0 && std::isfinite(mean)) { (void)std::frexp(mean, &ex); s->bj_scale = std::ldexp(1.0, ex / 2); }
+        }
         if (s->bj_pk32) {
             const long long nn = (long long)s->bg.nb * 40960;
-            hipLaunchKernelGGL(bj_pack_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, (long long)s->bg.nb, (const double *)s->bj_dinv, s->bj_pk32);
+            hipLaunchKernelGGL(bj_pack_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, (long long)s->bg.nb, (const double *)s->bj_dinv, s->bj_pk32, s->bj_scale);
         }
         if (s->bj_dinv32) {
             const long long nn = (long long)s->bg.nb * 65536;
             hipLaunchKernelGGL(to_f32_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, nn, (const double *)s->bj_dinv, (const double *)s->bj_dinvt,
-                               s->bj_dinv32, s->bj_dinvt32);
+                               s->bj_dinv32, s->bj_dinvt32, s->bj_scale);
         }
         int hinfo = 0;
         e = hipMemcpyAsync(&hinfo, s->bj_info, sizeof(int), hipMemcpyDeviceToHost, st);
@@ -1022,11 +1041,11 @@ static hipError_t pcg_precondition(PcgState *s, const double *r, double *z, hipS
     }
     if (part == 1) return hipGetLastError();
     if (s->bj_ready && s->bj_pk32)
-        hipLaunchKernelGGL(bj_apply_packed_kernel, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const float *)s->bj_pk32, r, z);
+        hipLaunchKernelGGL(bj_apply_packed_kernel, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const float *)s->bj_pk32, r, z, 1.0 / (s->bj_scale * s->bj_scale));
     else if (s->bj_ready && s->bj_dinv32)
-        hipLaunchKernelGGL(bj_apply_kernel<float>, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const float *)s->bj_dinv32, (const float *)s->bj_dinvt32, r, z);
+        hipLaunchKernelGGL(bj_apply_kernel<float>, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const float *)s->bj_dinv32, (const float *)s->bj_dinvt32, r, z, 1.0 / (s->bj_scale * s->bj_scale));
     else if (s->bj_ready)
-        hipLaunchKernelGGL(bj_apply_kernel<double>, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const double *)s->bj_dinv, (const double *)s->bj_dinvt, r, z);
+        hipLaunchKernelGGL(bj_apply_kernel<double>, dim3((unsigned)s->bg.nb), dim3(256), 0, st, g, s->bg, (const double *)s->bj_dinv, (const double *)s->bj_dinvt, r, z, 1.0);
     return hipGetLastError();
 }
 

@@ -283,13 +283,14 @@ ROUTES = {
 }
 
 
-def _plan(label, monkeypatch):
+def _plan(label, monkeypatch, xtrap=1.0, scale=1.0):
+    """The plan of ROUTES[label] on the box [0, scale]^nd."""
     nodes, env, code = ROUTES[label]
     nd = len(nodes)
     with monkeypatch.context() as mp:
         for k, v in env.items():
             mp.setenv(k, v)
-        plan = capi.Plan(nd, nodes, [0.0] * nd, [1.0] * nd, 1.0, M)
+        plan = capi.Plan(nd, nodes, [0.0] * nd, [scale] * nd, xtrap, M)
     got = plan.factorisation()[0]
     if got != code:
         plan.close()
