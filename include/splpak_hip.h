@@ -21,6 +21,19 @@
  *     (same GPU as the plan) in the `_dev` / plan entry points.
  *   - there is NO CPU fallback: without a usable HIP device every compute entry
  *     point fails with SPLPAK_E_NODEVICE.
+ *   - sizes: every count and every distance that is `int64_t` here (nq, ndata, offsets[], npts[], ldcoef, ldout, ldy,
+ *     ldv, ldw, ldcov) may reach and pass 2^31 and 2^32 elements, and so may the products the `int32_t` strides form
+ *     with a 64-bit index (query i at xq + i*ldxq, point p at xdata + p*l1xdat, row i of the derivatives at
+ *     out + i*ldout): caller memory is addressed with 64-bit offsets throughout.  tests/test_large_index.py runs the
+ *     device entries at such sizes -- the REAL32 instances past 2^31 and 2^32 (the kernels are templates over the
+ *     storage type; the *_f64 entries are not run that large), and past 2^31 alone: splpak_eval_derivs_dev_f64,
+ *     splpak_plan_refit_dev, the residual array of splpak_residuals_many_*, splpak_mad_many_*, both clipped batch fits
+ *     and the sample count of splpak_fit_grid_*.  splpak_plan_fit_dev is run past 2^32 words on the binning's routes 1
+ *     and 2; the strided read of its route 3 (grids of more than 1 048 320 cells) is 64-bit by reading only.
+ *     The limits that do exist are stated at their entries:
+ *     max_ndata of a plan <= 2^31 - 1025, a problem of a batch < 2^31 points, a grid call's tiles < 2^31 per launch,
+ *     coefficient indices (ncol) in `int`, and the persistent region path of the evaluation, which numbers queries
+ *     with 32 bits and leaves batches of 2^32 queries or more to the next path (same bits).
  */
 #ifndef SPLPAK_HIP_H
 #define SPLPAK_HIP_H
@@ -217,14 +230,17 @@ void    splpak_plan_set_refine(splpak_plan *plan, int32_t max_steps, double tol)
  * pointers ignored); coef_dev receives ncol coefficients (identical on every rank).  A rank whose
  * arguments are rejected still takes part in the first reduction, which carries an error flag: that
  * rank returns its status, the others SPLPAK_E_COMM -- nobody is left waiting in a collective.  Synchronises `stream` before returning (the error
- * flag and the refinement's convergence test are read back).  info as above. */
+ * flag and the refinement's convergence test are read back).  info as above.
+ * Sizes: ndata <= the plan's max_ndata <= 2^31 - 1025 (32-bit binning offsets), but ndata*l1xdat may pass 2^31 and 2^32
+ * words: point i is read at xdata_dev + i*l1xdat with a 64-bit i, and the result does not depend on l1xdat. */
 int32_t splpak_plan_fit_dev(splpak_plan *plan, const double *xdata_dev, int32_t l1xdat,
                             const double *ydata_dev, const double *wdata_dev,
                             int64_t ndata, double *coef_dev, void *stream, double *info);
 /* New values on the points of the plan's last fit.  Only the solve depends on ydata: the binned points, the histogram, the
  * data-sparse flags, the constraint rows, N = A^T W^2 A + C^T C, its factor and the iteration's preconditioner are functions of
  * xdata, wdata and the grid, and a successful single-rank fit leaves them in the plan.  Field k is the `ndata` values (of that
- * fit) at ydata_dev + k*ldy, in that fit's point order; its ncol coefficients go to coef_dev + k*ldcoef.  For every field
+ * fit) at ydata_dev + k*ldy, in that fit's point order; its ncol coefficients go to coef_dev + k*ldcoef (k*ldy and k*ldcoef
+ * beyond 2^31 and 2^32 words are supported, field by field and in batched sweeps).  For every field
  * the values are gathered into the binned order, A^T W^2 y is one pass over the rows, and the solve, the refinement against
  * the rows, the diagnostics and the decisions that end in 107 are the fit's own.  Two or more fields on a held factor of the
  * single-GPU nested dissection are solved in chunks of up to 8 fields that share every sweep of the factor (option
@@ -372,7 +388,10 @@ int32_t splpak_fit_multi_f64(int32_t ngpus, int32_t ndim, const double *xdata, i
 
 /* Batched evaluation on resident data (asynchronous on `stream`; no validation
  * beyond the reference's 101..104, which is done on the host from the small
- * arguments). */
+ * arguments).  Sizes: nq and nq*ldxq beyond 2^31 and 2^32 are supported -- query i is read at xq_dev + i*ldxq with a
+ * 64-bit i by the direct kernel and by every sorted path (their chunks start at xq_dev + c0*ldxq, c0 64-bit).  One limit:
+ * the persistent region path numbers the queries of a call with 32 bits, so a call of more than 2^32 - 8192 queries
+ * falls through to the run path or the region sort, which work through the batch in chunks and return the same bits. */
 int32_t splpak_eval_dev_f64(int32_t ndim, int64_t nq, const double *xq_dev, int32_t ldxq,
                             const int32_t *nderiv /* host, may be NULL */,
                             const double *coef_dev, const double *xmin, const double *xmax,
@@ -390,6 +409,7 @@ int32_t splpak_eval_dev_f32(int32_t ndim, int64_t nq, const float *xq_dev, int32
  * (:1089-1240) per point.  order = 1 or 2.  Row i of `out` (ldout apart, ldout >= number of entries):
  *   [ f, df/dx_1 .. df/dx_ndim, (order 2:) d2f/dx_1dx_1, d2f/dx_1dx_2, .., d2f/dx_1dx_ndim, d2f/dx_2dx_2, .. ]
  * i.e. the upper triangle of the Hessian row by row.  Each entry equals splde with the matching nderiv.
+ * Sizes: nq*ldout (and nq*ldxq) beyond 2^31 and 2^32 elements are supported, row i is addressed with a 64-bit i.
  * Status: 0, 101/102/103 as splde (`out` is zeroed), or a negative library status. */
 int32_t splpak_eval_derivs_f64(int32_t ndim, int64_t nq, const double *xq, int32_t ldxq, int32_t order,
                                const double *coef, const double *xmin, const double *xmax,
@@ -411,7 +431,8 @@ int32_t splpak_eval_derivs_dev_f64(int32_t ndim, int64_t nq, const double *xq_de
  *          `coef` uses (:227-228) -- each what splde (splfe when nderiv == NULL) returns at
  *          (axes_1[i0], axes_2[i1], ...): the very values splpak_eval_* computes for that point.
  * No query list is formed and nothing is sorted: 8 bytes of device memory traffic per output (4 for REAL32) and the
- * coefficients; output counts beyond 2^31 are fine.
+ * coefficients; output counts beyond 2^31 and 2^32 are fine in both tile forms (64-bit output indices; the limit is the
+ * tile count of a launch, below 2^31: at 64 x 8 x 8 outputs per 3-D tile that is 8.8e12 outputs).
  * Status as splpak_eval_f64: 101/102/103 return without computing, `out` set to 0 (101 -- no dimensions, so no
  * shape: out[0] alone); 104 (nderiv outside 0..2) is reported but the values are computed with nderiv clamped to
  * 0..2 (:1190-1194).  SPLPAK_E_BADARG: a null pointer, a negative npts[d], a product of npts beyond int64;
@@ -450,7 +471,8 @@ int32_t splpak_debug_eval_grid_stats(int64_t out2[2]);
  *          idx = i0 + npts[0]*(i1 + npts[1]*(i2 + ...)) is the ordering of splpak_eval_grid_*, and e runs over the entries
  *          of splpak_eval_derivs_* in its order: f, df/dx_1 .. df/dx_ndim, (order 2:) the upper triangle of the Hessian
  *          row by row.  Each plane is a volume as splpak_eval_grid_* writes it.  The words between the planes,
- *          [prod npts, ldout), are neither read nor written.
+ *          [prod npts, ldout), are neither read nor written.  As for splpak_eval_grid_*, prod npts and e*ldout beyond 2^31
+ *          and 2^32 elements are supported; the tiles of one launch stay below 2^31 (larger shapes are refused).
  * Plane e >= 1 holds the very values (identical bits) of splpak_eval_grid_* called with entry e's nderiv pattern: the
  * same factor tables and the same order of summation, whichever outputs share a partial sum.  Plane 0 is summed in that
  * order on the GENERAL-form factor tables (what every nderiv != NULL call uses), whereas splpak_eval_grid_* with
@@ -547,7 +569,8 @@ int32_t splpak_debug_integrate_grid_stats(int64_t out8[8]);
  *   waxes       the same layout, one weight per axis coordinate; NULL: all 1 (there is no negative-first-weight sentinel);
  *   values      field k's prod npts samples at values + k*ldv, dimension 1 fastest (what splpak_eval_grid_* writes);
  *   coef        field k's ncol coefficients go to coef + k*ldcoef (the layout of splpak_refit_* and splpak_eval_fields_*).
- * The words between the fields are neither read nor written.
+ * The words between the fields are neither read nor written.  Sizes: k*ldv (weighted entries: k*ldw) and k*ldcoef beyond
+ * 2^31 and 2^32 elements are supported, and so is a sample count prod npts beyond 2^31.
  * xtrap.  With xtrap == 0 the reference adds no constraint rows (:862).  With xtrap != 0 it adds them for data-sparse nodes
  * (:921-1046); this entry then answers only when there are none, which it decides from per-axis nearest-node histograms:
  * every coordinate must be counted in range -- k = int(dxin_d (x - xmin_d) + 0.5), truncated toward zero, in 0 .. nodes_d - 1
@@ -718,6 +741,10 @@ int32_t splpak_debug_fit_grid_weighted_stats(int64_t out8[8]);
  * Determinism.  Every sum has one owner and a fixed order -- the owner of a band row walks the problem's points in index order
  * -- and there are no floating-point atomics.  The bits of problem k depend on its own points, values, weights and the grid
  * alone: not on nbatch, its position in the batch, its neighbours, the host / _dev entry, or the workgroup that ran it.
+ * Sizes.  offsets[] (the points of the whole batch), p*l1xdat, k*ldcoef and, in the variants, k*ldcov and the index into wout
+ * may pass 2^31 and 2^32: points, rows of coef and cov are addressed with 64-bit offsets (splpak_eval_many_*,
+ * splpak_residuals_many_* and splpak_mad_many_* likewise).  The limits: nbatch is an int32_t and ONE problem has fewer than
+ * 2^31 points.  splpak_fit_many_clip_mad_* keeps one double per point of the batch's span in device scratch.
  * Status.  Decided on the host before any device work, the first failing check wins, coef and status untouched:
  *   SPLPAK_E_BADARG (offsets, nodes, xmin or xmax null); 101; SPLPAK_E_UNSUPPORTED (ndim > 2); 102; 103; 104 (ldcoef < ncol);
  *   SPLPAK_E_BADARG (nbatch < 1, offsets that decrease, a problem of 2^31 points or more, l1xdat < ndim, xdata, ydata or coef
@@ -1113,7 +1140,8 @@ int32_t splpak_debug_eval_many_stats(int64_t out8[8]);
  *   nderiv one pattern for all fields (NULL: values).
  * out[k*ldout + i] is the very value splpak_eval_* returns for query i with field k's coefficients (identical bits: the
  * same factor table and the same sum over the window, field by field; no partial sum is shared between fields).  The
- * words of `coef` and `out` between the fields are neither read nor written.
+ * words of `coef` and `out` between the fields are neither read nor written.  Sizes: k*ldcoef, k*ldout and nq*ldxq
+ * beyond 2^31 and 2^32 elements are supported on every route (the limits of splpak_eval_dev_* apply to nq).
  * Status, decided on the host before any device work, the first failing check wins:
  *   SPLPAK_E_BADARG       nodes, xmin or xmax null; then nfields < 1, nq < 0 or ldout < nq;
  *   101, then SPLPAK_E_UNSUPPORTED (ndim > 4), then 102 / 103 as splpak_eval_f64 -- on 101 / 102 / 103 the nq results of
