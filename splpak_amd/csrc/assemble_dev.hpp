@@ -94,6 +94,44 @@ __device__ inline double constraint_entry(const Grid &g, const double *__restric
     return rowwt * basm;                                          // :1011
 }
 
+// acc - (C^T t)_i for node i (coordinates in): over the data-sparse neighbours n of i (3^D offsets, dimension 0 fastest) and their rows,
+// row(n, pair)[i] * t[n][pair] with t = C x from constraint_dots_kernel (tbuf: [ncol][D (D + 1) / 2]) -- the constraint term of the
+// residual passes' gathers (residual.hip rho_gather_kernel, rows3tile.hip rows3_gather_kernel), one order of the subtractions
+template <int D>
+__device__ inline double constraint_term(const Grid &g, const int *in, const double *__restrict__ dcw, const unsigned char *__restrict__ spf,
+                                         const double *__restrict__ ctab, const double *__restrict__ tbuf, double acc)
+{
+    constexpr int NE = (D == 1) ? 3 : (D == 2) ? 9 : (D == 3) ? 27 : 81;
+    constexpr int NP = D * (D + 1) / 2;
+    for (int ne = 0; ne < NE; ++ne) {
+        int nn[D], offi[D], t = ne, ncol_n = 0;
+        bool ok = true;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const int o = t % 3 - 1;
+            t /= 3;
+            nn[d] = in[d] + o;
+            offi[d] = -o;
+            ok = ok && nn[d] >= 0 && nn[d] <= g.nodes[d] - 1;
+            ncol_n += nn[d] * g.colstride[d];
+        }
+        if (!ok) continue;
+        if (spf[ncol_n] == 0) continue;
+        SparseNode sn;
+        sn.sparse = true;
+        sn.dcwght = dcw[ncol_n];
+        int pair = 0;
+        for (int idm = 0; idm < D; ++idm)
+            for (int jdm = idm; jdm < D; ++jdm, ++pair) {
+                int nder[D];
+                const double rowwt = constraint_pattern<D>(g, nn, idm, jdm, sn.dcwght, nder);
+                const double ci = constraint_entry<D>(g, ctab, nn, offi, nder, rowwt);
+                if (ci != 0.0) acc -= ci * tbuf[(long long)ncol_n * NP + pair];
+            }
+    }
+    return acc;
+}
+
 // workgroups of `threads` for a grid-stride loop over n items
 inline unsigned grid_for(long long n, int threads, long long maxblocks = 256LL * 16)
 {

@@ -166,6 +166,10 @@ hipError_t launch_count_sparse(const Grid &g, const unsigned char *spf, double *
 hipError_t launch_residual(const Grid &g, const SortScratch &s, const double *xvec, double *rcell,
                            const double *dcw, const unsigned char *spf, const double *ctab, bool constraints,
                            double *tbuf, double *rho, double *ssq, double *e2buf, hipStream_t st);
+// the constraint rows' step of that pass on its own (the tiled 3-D pass, rows3tile.hip): tbuf[n][pair] = row(n, pair) . x on the
+// data-sparse nodes, 0 elsewhere; e2nodes != NULL: the node's share of the squared constraint residuals
+hipError_t launch_constraint_dots(const Grid &g, const double *dcw, const unsigned char *spf, const double *ctab, const double *xvec,
+                                  double *tbuf, double *e2nodes, hipStream_t st);
 // out[0] = max_i |rho_i| / ((|N||x|)_i + |rhs_i|): componentwise backward error with respect to the rows -- the denominators
 // den[i] first (they need the coefficients only: beside the residual pass, on another stream), then the maximum of the ratios
 hipError_t launch_backward_denominators(const Grid &g, const double *nst, const double *xvec, const double *rhs, double *den, hipStream_t st);

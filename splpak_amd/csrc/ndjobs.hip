@@ -210,6 +210,14 @@ bool nd_build_factor_jobs(NdState *s)
     return true;
 }
 
+// Real columns of block k of a front of own width w, as the solves' sweeps take them (FwdJob / DotJob, ndstate.hpp).
+// A/B switch SPLPAK_ND_SOLVE_PADDED: all 256, the identity padding of the last block included, as before -- the same bits.
+static int solve_block_cols(int w, int k)
+{
+    if (splpak::opt_get("SPLPAK_ND_SOLVE_PADDED")) return 256;
+    return std::max(1, std::min(256, w - k * 256));
+}
+
 // Job tables of the SOLVES: per tree depth (all fronts of the depth, whatever their pipeline) and block step.
 bool nd_build_solve_jobs(NdState *s)
 {
@@ -232,14 +240,15 @@ bool nd_build_solve_jobs(NdState *s)
                 if (k >= f.nsteps) continue;
                 const double *below = s->factor + s->poff[(size_t)id] + (long long)k * 256 + (long long)k * 256 * f.ld + 256;
                 const int nrows = f.fp - (k + 1) * 256;
+                const int ncols = solve_block_cols(f.w, k);
                 double *Vf = s->V + f.vofs, *Yf = s->Y + f.vofs;
                 T.mv.push(MvJob{s->dinv + (long long)(s->lblk[(size_t)id] + k) * 65536, Vf + k * 256, Yf + k * 256});
                 int nsplit = 0;
                 double *partp = s->part + partofs;
                 if (nrows > 0) {
-                    T.fwd.push(FwdJob{below, Yf + k * 256, Vf + (k + 1) * 256, f.ld, nrows, 0}, nrows / 64);
+                    T.fwd.push(FwdJob{below, Yf + k * 256, Vf + (k + 1) * 256, f.ld, nrows, ncols, 0}, nrows / 64);
                     nsplit = (nrows + DOT_RPS - 1) / DOT_RPS;
-                    T.dot.push(DotJob{below, Vf + (k + 1) * 256, partp, f.ld, nrows, nsplit, DOT_RPS, 0}, 16 * nsplit);
+                    T.dot.push(DotJob{below, Vf + (k + 1) * 256, partp, f.ld, nrows, nsplit, DOT_RPS, ncols, 0}, 16 * nsplit);
                     partofs += (long long)nsplit * 256;
                 }
                 T.bwd.push(BwdJob{s->dinvt + (long long)(s->lblk[(size_t)id] + k) * 65536, Yf + k * 256, partp, Vf + k * 256, nsplit, 0});
@@ -370,6 +379,7 @@ bool nd_build_top_jobs(NdState *s)
             const int ncols = std::max(1, std::min(256, f.w - k * 256));
             const int ksl = (k == f.nsteps - 1) ? 4 * ((ncols + 15) / 16) : 64;
             const int nrows = f.fp - (k + 1) * 256;
+            const int scols = solve_block_cols(f.w, k);
             if (o == me) {
                 double *diag = s->factor + top_col(s, ti, k).off;
                 const long long lb = T.toplblk[(size_t)T.tbase[ti] + (size_t)k];
@@ -380,10 +390,10 @@ bool nd_build_top_jobs(NdState *s)
                 int nsplit = 0;
                 if (nrows > 0) {
                     single(T.trsm, sq, TrsmJob{diag, diag + 256, i16, ldk, nrows, 0, (ncols + 15) / 16, 0}, nrows / 16);
-                    single(T.fwd, sq, FwdJob{diag + 256, Yf + k * 256, Vf + (k + 1) * 256, ldk, nrows, 0}, nrows / 64);
+                    single(T.fwd, sq, FwdJob{diag + 256, Yf + k * 256, Vf + (k + 1) * 256, ldk, nrows, scols, 0}, nrows / 64);
                     nsplit = (nrows + DOT_RPS - 1) / DOT_RPS;
                     if ((long long)nsplit * 256 > s->part_cap) { set_error("nested dissection: partial-sum buffer too small"); return false; }
-                    single(T.dot, sq, DotJob{diag + 256, Vf + (k + 1) * 256, s->part, ldk, nrows, nsplit, DOT_RPS, 0}, 16 * nsplit);
+                    single(T.dot, sq, DotJob{diag + 256, Vf + (k + 1) * 256, s->part, ldk, nrows, nsplit, DOT_RPS, scols, 0}, 16 * nsplit);
                 }
                 single(T.bwd, sq, BwdJob{s->dinvt + lb * 65536, Yf + k * 256, s->part, Vf + k * 256, nsplit, 0});
             }

@@ -761,15 +761,20 @@ nd_fwd_kernel(const FwdJob *__restrict__ jobs, int njobs)
     const int rp = tid & 31, cg = tid >> 5;
     const int r = wg * 64 + 2 * rp;
     const double *__restrict__ Lr = j.L + r + (long long)(cg * 16) * j.ld;
-    d2_t l[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) l[c] = *reinterpret_cast<const d2_t *>(Lr + (long long)c * j.ld);
+    // a column group at or beyond the block's real columns loads nothing: its sixteen columns are identity padding (zero here, below
+    // the diagonal) against y entries that are exactly zero -- every product it left out was +0.0 added to +0.0: the same bits
+    const bool real = cg * 16 < j.ncols;
     double s0 = 0.0, s1 = 0.0;
+    if (real) {
+        d2_t l[16];
 #pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const double yv = sy[cg * 16 + c];
-        s0 += l[c][0] * yv;
-        s1 += l[c][1] * yv;
+        for (int c = 0; c < 16; ++c) l[c] = *reinterpret_cast<const d2_t *>(Lr + (long long)c * j.ld);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const double yv = sy[cg * 16 + c];
+            s0 += l[c][0] * yv;
+            s1 += l[c][1] * yv;
+        }
     }
     part[cg][2 * rp] = s0;
     part[cg][2 * rp + 1] = s1;
@@ -796,6 +801,13 @@ nd_dot_kernel(const DotJob *__restrict__ jobs, int njobs)
     const int c0 = cg * 16 + wave * 4;
     const int rbeg = split * j.rps;
     const int rend = rbeg + j.rps < j.nrows ? rbeg + j.rps : j.nrows;
+    if (c0 >= j.ncols) {      // four columns of identity padding: nothing to read, and nd_bwd_kernel reads every entry of `part`
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) j.part[(long long)split * NBLK + c0 + c] = 0.0;
+        }
+        return;
+    }
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     const double *__restrict__ Lc = j.L + lane + (long long)c0 * j.ld;
     // four row groups (20 loads) in flight per round: the rolled loop paid one memory round trip per 64 rows, 16 in a row
@@ -970,9 +982,10 @@ nd_fwd_many_kernel(const FwdJob *__restrict__ jobs, int njobs, BatchVec w)
     const int rp = tid & 31, cg = tid >> 5;
     const int r = wg * 64 + 2 * rp;
     const double *__restrict__ Lr = j.L + r + (long long)(cg * 16) * j.ld;
+    const bool real = cg * 16 < j.ncols;      // (as in nd_fwd_kernel: a group of padding columns loads nothing and adds +0.0)
     d2_t l[16];
 #pragma unroll
-    for (int c = 0; c < 16; ++c) l[c] = *reinterpret_cast<const d2_t *>(Lr + (long long)c * j.ld);
+    for (int c = 0; c < 16; ++c) l[c] = real ? *reinterpret_cast<const d2_t *>(Lr + (long long)c * j.ld) : d2_t{0.0, 0.0};
     __syncthreads();
 #pragma unroll
     for (int f0 = 0; f0 < R; f0 += RC) {
@@ -981,11 +994,13 @@ nd_fwd_many_kernel(const FwdJob *__restrict__ jobs, int njobs, BatchVec w)
         for (int ff = 0; ff < RC; ++ff) {
             if (ff < nf) {
                 double s0 = 0.0, s1 = 0.0;
+                if (real) {
 #pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const double yv = sy[f0 + ff][cg * 16 + c];
-                    s0 += l[c][0] * yv;
-                    s1 += l[c][1] * yv;
+                    for (int c = 0; c < 16; ++c) {
+                        const double yv = sy[f0 + ff][cg * 16 + c];
+                        s0 += l[c][0] * yv;
+                        s1 += l[c][1] * yv;
+                    }
                 }
                 part[ff][cg][2 * rp] = s0;
                 part[ff][cg][2 * rp + 1] = s1;
@@ -1017,6 +1032,17 @@ nd_dot_many_kernel(const DotJob *__restrict__ jobs, int njobs, BatchVec w)
     const int c0 = cg * 16 + wave * 4;
     const int rbeg = split * j.rps;
     const int rend = rbeg + j.rps < j.nrows ? rbeg + j.rps : j.nrows;
+    if (c0 >= j.ncols) {      // (as in nd_dot_kernel: padding columns are not read, their entries of every `part` are 0.0)
+        if (lane == 0) {
+#pragma unroll
+            for (int f = 0; f < R; ++f) {
+                double *__restrict__ pp = batch_at(w.part, w.pstride, f, j.part, w.part0);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) pp[(long long)split * NBLK + c0 + c] = 0.0;
+            }
+        }
+        return;
+    }
     double acc[R][4];
 #pragma unroll
     for (int f = 0; f < R; ++f)

@@ -48,8 +48,10 @@ struct TrinvJob { const double *L; const double *inv16; double *dinv; double *di
 // child's Schur buffer -> parent's panel (columns < wpp) / Schur buffer
 struct AddJob { const double *S; const int *pm; double *P; double *Sp; long long lds, ldp, ldsp; int h, nt, wpp, tile0; };
 struct MvJob { const double *M; const double *v; double *out; };
-struct FwdJob { const double *L; const double *y; double *v; long long ld; int nrows; int wg0; };
-struct DotJob { const double *L; const double *x; double *part; long long ld; int nrows; int nsplit; int rps; int wg0; };
+// ncols: the block's REAL columns (256 except in a front's last block, whose columns from w on are identity padding: zero below
+// the unit diagonal, and the vector entries that meet them are exactly zero) -- the sweeps read no further (ndkernels.hip)
+struct FwdJob { const double *L; const double *y; double *v; long long ld; int nrows; int ncols; int wg0; };
+struct DotJob { const double *L; const double *x; double *part; long long ld; int nrows; int nsplit; int rps; int ncols; int wg0; };
 struct BwdJob { const double *Mt; const double *y; const double *part; double *x; int nsplit; int pad; };
 struct MapJob { double *child; double *par; const int *pm; int h; int pad; };
 struct FrontDev { long long panel_off, ld, bofs; int own0, w, wp, h; int top; int pad; };   // panel_off < 0: not stored on this rank; top >= 0: first entry of the (distributed) front in the TopColDev table

@@ -50,6 +50,7 @@ const Known KNOWN[] = {
     {"SPLPAK_ND_ROOT_LA", 0},
     {"SPLPAK_ND_SMALL_GRID", 0},
     {"SPLPAK_ND_SMALL_QUEUE", 0},
+    {"SPLPAK_ND_SOLVE_PADDED", 0},
     {"SPLPAK_ND_SPLIT", 1},
     {"SPLPAK_ND_SQUARE", 0},
     {"SPLPAK_ND_STAGED_INIT", 0},

@@ -184,10 +184,12 @@ int splpak::plan_create_dist(int ndim, const int *nodes, const double *xmin, con
     p->xtrap = xtrap;
     p->max_ndata = max_ndata;
     bool ok = sort_scratch_alloc(p, g, max_ndata, &p->s);
-    {   // per-cell shares of the residual passes of residual.hip: 1-D .. 3-D grids; a 4-D grid's passes go tile by tile (rowsop.hip)
-        // and leave this scratch out (1.45 GB at 32^4) unless the A/B switches ask for the cell-by-cell forms
-        const bool tiled = g.ndim == 4 && rows_tiles && !splpak::opt_get("SPLPAK_RESIDUAL_CELLS");
+    {   // per-cell shares of the residual passes of residual.hip: 1-D and 2-D grids; a 3-D or 4-D grid's passes go tile by tile
+        // (rows3tile.hip, rowsop.hip) and leave this scratch out (1.45 GB at 32^4, 116 MB at 64^3) unless the A/B switches ask for
+        // the cell-by-cell forms
+        const bool tiled = g.ndim >= 3 && rows_tiles && !splpak::opt_get("SPLPAK_RESIDUAL_CELLS");
         if (!tiled) ok = ok && dev_alloc(p, &p->rcell, (size_t)g.ncell * g.nb);
+        if (g.ndim == 3 && rows_tiles) ok = ok && dev_alloc(p, &p->rows3.partial, (size_t)rows3_tiles(g, &p->rows3));
     }
     ok = ok && dev_alloc(p, &p->tbuf, (size_t)g.ncol * (g.ndim * (g.ndim + 1) / 2));
     ok = ok && dev_alloc(p, &p->dcw, (size_t)g.ncol);

@@ -40,6 +40,9 @@ struct HostBarrier {
     }
 };
 struct RowsOp;         // the rows of a 4-D fit applied to a vector, tile by tile (rowsop.hip)
+// the data rows of a 3-D fit applied to a vector, tile by tile (rows3tile.hip): tiles per dimension and their partial sums
+// ([ntiles][nodes of a tile], the plan's own allocation); partial == NULL: the cell-by-cell passes of residual.hip
+struct Rows3Tiles { int nt[3] = {1, 1, 1}; long long ntiles = 0; double *partial = nullptr; };
 struct PcgState;       // iterative solve of the least-squares problem (pcg.hip)
 struct NdGroup;        // the ranks of a one-process multi-GPU nested-dissection factorisation (ndstate.hpp, ndtop.hip)
 }  // namespace splpak
@@ -105,6 +108,8 @@ struct splpak_plan {
     // no factorisation fits, or by request), 3 the iteration first and the factorisation when it stagnates
     splpak::Options opt;                      // the switches as they were when the plan was created (+ splpak_plan_set_option)
     splpak::RowsOp *rowsop = nullptr;         // 4-D grids: the tiled residual pass (NULL: the cell-by-cell passes of residual.hip)
+    splpak::Rows3Tiles rows3;                 // 3-D grids: the tiled data rows of the residual passes.  (Not `rowsop`: the lazy assembly, the
+                                              // rows-only denominators and the solver choice key on that one, and stay 4-D.)
     splpak::PcgState *pcg = nullptr;
     int solver_mode = 0;
     double factor_flop = 0.0;     // flop of the plan's factorisation where known (nested dissection), else 0
@@ -215,9 +220,18 @@ hipError_t rowsop_backward_denominators(const Grid &g, RowsOp *r, const SortScra
 // rho = A^T W (W y - W A x) [- C^T C x] of the plan's binned points (rows.ys == NULL: y = 0), by whichever pass the plan has
 hipError_t rowsop_residual(const Grid &g, RowsOp *r, const SortScratch &rows, const double *xvec, const double *dcw, const unsigned char *spf,
                            const double *ctab, bool constraints, double *rho, double *ssq, double *e2buf, hipStream_t st);
+// rows3tile.hip
+long long rows3_tiles(const Grid &g, Rows3Tiles *r);
+hipError_t rows3_apply(const Grid &g, const Rows3Tiles &r, const SortScratch &rows, const double *xvec, const double *dcw,
+                       const unsigned char *spf, const double *ctab, bool constraints, double *tbuf, double *rho, hipStream_t st,
+                       double *e2tiles = nullptr, double *e2nodes = nullptr);
+hipError_t rows3_residual(const Grid &g, const Rows3Tiles &r, const SortScratch &rows, const double *xvec, const double *dcw,
+                          const unsigned char *spf, const double *ctab, bool constraints, double *tbuf, double *rho, double *ssq,
+                          double *e2buf, hipStream_t st);
 inline hipError_t plan_rows_residual(splpak_plan *p, const SortScratch &rows, const double *xvec, bool constraints, double *rho, hipStream_t st)
 {
     if (p->rowsop) return rowsop_apply(p->g, p->rowsop, rows, xvec, p->dcw, p->spf, p->ctab, constraints, rho, st);
+    if (p->rows3.partial) return rows3_apply(p->g, p->rows3, rows, xvec, p->dcw, p->spf, p->ctab, constraints, p->tbuf, rho, st);
     return launch_residual(p->g, rows, xvec, p->rcell, p->dcw, p->spf, p->ctab, constraints, p->tbuf, rho, nullptr, nullptr, st);
 }
 // ndkernels.hip: batched Cholesky + triangular inverses of independent dense 256 x 256 blocks

@@ -120,6 +120,9 @@ int plan_diagnostics_pass(splpak_plan *p, bool rows_fit, hipStream_t st, hipEven
     if (p->rowsop && (!p->rcell || !splpak::opt_get("SPLPAK_RESIDUAL_CELLS")))      // (4-D: tile by tile, as the refinement's passes; 8.3 -> 1 ms at 32^4)
         SPLPAK_HIP_TRY(rowsop_residual(g, p->rowsop, p->s, p->xvec, p->dcw, p->spf, p->ctab, smooth && p->rank == 0, p->rho, scalR, p->e2buf, st),
                        SPLPAK_E_NODEVICE);
+    else if (p->rows3.partial && (!p->rcell || !splpak::opt_get("SPLPAK_RESIDUAL_CELLS")))      // (3-D: the data rows tile by tile, likewise)
+        SPLPAK_HIP_TRY(rows3_residual(g, p->rows3, p->s, p->xvec, p->dcw, p->spf, p->ctab, smooth && p->rank == 0, p->tbuf, p->rho, scalR,
+                                      p->e2buf, st), SPLPAK_E_NODEVICE);
     else
         SPLPAK_HIP_TRY(launch_residual(g, p->s, p->xvec, p->rcell, p->dcw, p->spf, p->ctab, smooth && p->rank == 0,
                                        p->tbuf, p->rho, scalR, p->e2buf, st), SPLPAK_E_NODEVICE);

@@ -12,6 +12,8 @@
 //   constraint_dots_kernel t = C x on the data-sparse nodes (with constraints)
 //   rho_gather_kernel      per node: the shares of the cells that contain it, minus C^T t
 //   sum_fixed_kernel       the sum of squared row residuals, when asked for (sums.hip)
+// 3-D plans run the data rows tile by tile instead (rows3tile.hip), 4-D plans the whole pass (rowsop.hip): for them this form stays
+// behind SPLPAK_ROWS_TILES=0 / SPLPAK_RESIDUAL_CELLS=1.
 // Backward error:
 //   backward_denominators_kernel, backward_error_kernel
 #include "assemble_dev.hpp"
@@ -278,8 +280,6 @@ rho_gather_kernel(Grid g, const int *__restrict__ offset, const double *__restri
                   const double *__restrict__ tbuf, double *__restrict__ rho)
 {
     constexpr int NB = 1 << (2 * D);
-    constexpr int NE = (D == 1) ? 3 : (D == 2) ? 9 : (D == 3) ? 27 : 81;
-    constexpr int NP = D * (D + 1) / 2;
     const int node = blockIdx.x * blockDim.x + threadIdx.x;
     if (node >= g.ncol) return;
     int in[D];
@@ -292,34 +292,7 @@ rho_gather_kernel(Grid g, const int *__restrict__ offset, const double *__restri
         cr.get(g, in, e, cell, r);
         if (offset[cell] != offset[cell + 1]) acc += rcell[(long long)cell * NB + r];
     }
-    if (tbuf) {
-        for (int ne = 0; ne < NE; ++ne) {
-            int nn[D], offi[D], t = ne, ncol_n = 0;
-            bool ok = true;
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                const int o = t % 3 - 1;
-                t /= 3;
-                nn[d] = in[d] + o;
-                offi[d] = -o;
-                ok = ok && nn[d] >= 0 && nn[d] <= g.nodes[d] - 1;
-                ncol_n += nn[d] * g.colstride[d];
-            }
-            if (!ok) continue;
-            if (spf[ncol_n] == 0) continue;
-            SparseNode sn;
-            sn.sparse = true;
-            sn.dcwght = dcw[ncol_n];
-            int pair = 0;
-            for (int idm = 0; idm < D; ++idm)
-                for (int jdm = idm; jdm < D; ++jdm, ++pair) {
-                    int nder[D];
-                    const double rowwt = constraint_pattern<D>(g, nn, idm, jdm, sn.dcwght, nder);
-                    const double ci = constraint_entry<D>(g, ctab, nn, offi, nder, rowwt);
-                    if (ci != 0.0) acc -= ci * tbuf[(long long)ncol_n * NP + pair];
-                }
-        }
-    }
+    if (tbuf) acc = constraint_term<D>(g, in, dcw, spf, ctab, tbuf, acc);
     rho[node] = acc;
 }
 
@@ -455,6 +428,14 @@ hipError_t launch_residual(const Grid &g, const SortScratch &s, const double *xv
     return hipGetLastError();
 }
 
+
+hipError_t launch_constraint_dots(const Grid &g, const double *dcw, const unsigned char *spf, const double *ctab, const double *xvec,
+                                  double *tbuf, double *e2nodes, hipStream_t st)
+{
+    dim3 gn((unsigned)((g.ncol + 3) / 4)), bl(256);
+    DISPATCH_D(g.ndim, hipLaunchKernelGGL(constraint_dots_kernel<D>, gn, bl, 0, st, g, dcw, spf, ctab, xvec, tbuf, e2nodes));
+    return hipGetLastError();
+}
 
 hipError_t launch_backward_denominators(const Grid &g, const double *nst, const double *xvec, const double *rhs, double *den, hipStream_t st)
 {

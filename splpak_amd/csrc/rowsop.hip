@@ -479,7 +479,8 @@ size_t rowsop_bytes(const RowsOp *r) { return r ? r->bytes : 0; }
 // 4-D grids only; NULL for the others.  (A 3-D form of the tile kernel -- 64 window functions, a lane each in the transposed product --
 // was built and measured in round 6: 22.4 ms of solves + refinement per fit at config 3 against 22.5 ms with the wave-per-cell pass of
 // residual.hip, and 59.6 against 47.9 ms at 1e8 points (440 points per cell: the wave-per-cell pass takes 64 points per trip, the
-// tile kernel 16).  Removed again.)
+// tile kernel 16).  Removed again.  The 3-D data rows now go tile by tile with BOTH products on the matrix pipe: rows3tile.hip, a
+// handle of the plan's own -- this one stays NULL in 3-D, the lazy assembly and the solver choice key on it.)
 int rowsop_create(const Grid &g, bool side_stream, RowsOp **out)
 {   // side_stream: the plan has no factorisation.  (Beside a nested-dissection plan's streams -- one of them bound to eight reserved CUs --
     //  the operator's own stream made the iteration SLOWER: 181 against 112 ms per fit at 24^4; the runtime maps streams onto a few
