@@ -848,11 +848,59 @@ def test_headline_pipeline_variants_match_golden(name):
         res[label] = coef
     assert relmax(res["pinned"], res["unpinned"]) <= 1e-13
     assert relmax(res["serial"], res["unpinned"]) <= 1e-13
+    _pipeline_variants_have_equal_bits(name, inp["ndim"], inp["xdata"], inp["ydata"], inp["wdata"], inp["xmin"], inp["xmax"],
+                                       inp["nodes"], inp["xtrap"])
+
+
+# the four-stream pipeline of csrc/bandchol.hip pinned, unpinned and on one stream.  (SPLPAK_NO_LOOKAHEAD=1 alone, the "serial" of
+# the refined comparisons above, leaves the narrow limit at its default: on these grids that is the two-ended form on serial chains,
+# another launch split, which tests/test_band_scheduling.py does not compare with the pipeline bit for bit either.)
+PIPELINE_SCHEDULES = (("pinned", {"SPLPAK_PIN_BW": "1"}), ("unpinned", {"SPLPAK_NARROW_BW": "1", "SPLPAK_PIN_BW": "1000000"}),
+                      ("serial", {"SPLPAK_NARROW_BW": "1", "SPLPAK_PIN_BW": "1000000", "SPLPAK_NO_LOOKAHEAD": "1"}))
+
+
+def _pipeline_variants_have_equal_bits(what, nd, x, y, w, xmin, xmax, nodes, xtrap):
+    """Fits WITHOUT refinement (the coefficients are the factorisation's one solve) under the three schedules of the pipeline:
+    identical bits and smallest pivots -- tests/test_band_scheduling.py established no exception for this family."""
+    import torch
+    dev = torch.device("cuda", 0)
+    xt = torch.tensor(np.ascontiguousarray(x), dtype=torch.float64, device=dev)
+    yt = torch.tensor(y, dtype=torch.float64, device=dev)
+    wt = None if w is None else torch.tensor(w, dtype=torch.float64, device=dev)
+    res = {}
+    for label, env in PIPELINE_SCHEDULES:
+        env = dict(env, SPLPAK_ND="0", SPLPAK_SOLVER="direct", SPLPAK_NO_TWOEND="1")
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            plan = capi.Plan(nd, nodes, xmin, xmax, xtrap, xt.shape[0])
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+        try:
+            code, text = plan.factorisation()
+            assert code == 0, (label, code, text)
+            plan.set_refine(0, 1e-11)
+            coef = torch.zeros(plan.ncol, dtype=torch.float64, device=dev)
+            ierr, info = plan.fit(xt, yt, wt, coef)
+            torch.cuda.synchronize()
+            assert ierr == 0 and info[2] == 0 and info[4] > 0, (label, ierr, info)
+            res[label] = (coef.cpu().numpy(), float(info[4]))
+        finally:
+            plan.close()
+    for label in ("pinned", "serial"):
+        same = np.array_equal(res[label][0], res["unpinned"][0])
+        print(f"{what} without refinement [{label} / unpinned]: equal bits {same}, min pivot {res[label][1]!r} / {res['unpinned'][1]!r}")
+        assert same and res[label][1] == res["unpinned"][1], (what, label, relmax(res[label][0], res["unpinned"][0]))
 
 
 def test_pinned_pipeline_24cubed_property():
     """The pinned pipeline on the 24^3 grid (13 824 columns, band 8 blocks wide, 54 steps): data from
-    the spline space is reproduced to 1e-10 (xtrap = 0) and matches the unpinned pipeline."""
+    the spline space is reproduced to 1e-10 (xtrap = 0) and matches the unpinned pipeline; without refinement
+    pinned, unpinned and serial give identical bits."""
     import os
     import torch
     from splpak_amd.synth import synth_points, synth_queries
@@ -875,6 +923,7 @@ def test_pinned_pipeline_24cubed_property():
         assert info[9] < 1e-9
         out[label] = c
     assert relmax(out["pinned"], out["unpinned"]) <= 1e-13
+    _pipeline_variants_have_equal_bits("24^3", nd, x, f(x), None, [0.0] * nd, [1.0] * nd, [nod] * nd, 0.0)
 
 
 def test_c3_full_size_properties():
